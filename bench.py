@@ -53,6 +53,8 @@ def parse():
     ap.add_argument("--vcycle-deadline", type=int, default=180, help="N>1: seconds before the V-cycle leg is abandoned")
     ap.add_argument("--deadline", type=int, default=900,
                     help="N>1: seconds before the whole run is abandoned (a hung collective must not hang the node)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed step left as DIR/<name>.npy (float64, at most 64 MB in all)")
     return ap.parse_args()
 
 
@@ -219,6 +221,40 @@ def rank_census(rank, world, local_dev, transport_note, group=None):
     return {"world_size": world, "distinct_devices": len({r["uid"] for r in allr}), "per_rank": allr,
             "library_rccl_ranks": sum(1 for r in allr if r["rccl_comm_of_the_library"]),
             "transport": "none (single rank)" if world == 1 else (transport_note or "RCCL send/recv (torch.distributed)")}
+
+
+DUMP_CELLS = 1 << 20         # --dump-outputs: cells written per job (5 variables + the cell number, FP64: 48 MB)
+DUMP_SEED = 20240917
+
+
+def dump_outputs(lev, out_dir, world, rank):
+    """--dump-outputs: what the timed steps hand their caller, the conserved state uold of the rank's brick after the last
+    timed step (FP64).  Whole as state[nvar,nz,ny,nx] up to DUMP_CELLS cells (shared out over the ranks); above that the
+    same seeded sample of cells in every run of the same size: state_sample[nvar,S] at the flat (z,y,x) cell numbers
+    state_sample_cells[S].  state_sum[nvar]: every variable summed over all cells of the brick.  N>1: one set per rank,
+    the file names end in _rank<r>.  Returns the names written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    u = lev.interior(lev.uold)
+    nvar, nz, ny, nx = u.shape
+    ncell = nz * ny * nx
+    budget = DUMP_CELLS // world
+    arrays = {}
+    if ncell <= budget:
+        arrays["state"] = u.cpu().numpy()
+    else:
+        cells = np.sort(np.random.default_rng(DUMP_SEED).choice(ncell, size=budget, replace=False))
+        c = torch.from_numpy(cells).to(u.device)
+        arrays["state_sample"] = u[:, c // (ny * nx), (c // nx) % ny, c % nx].cpu().numpy()
+        arrays["state_sample_cells"] = cells.astype(np.float64)
+    arrays["state_sum"] = u.sum(dim=(1, 2, 3)).cpu().numpy()
+    suffix = "_rank%d" % rank if world > 1 else ""
+    names = []
+    for name, a in arrays.items():
+        names.append(name + suffix + ".npy")
+        np.save(os.path.join(out_dir, names[-1]), np.ascontiguousarray(a, dtype=np.float64))
+    return names
 
 
 BYTES_PER_DOF_VCYCLE = 227   # SURVEY.md 8d: 202 B fine level + 178/7 B coarse hierarchy
@@ -877,6 +913,8 @@ def main():
     kern_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps
     if os.environ.get("RAMSES_AMD_BENCH_STEPS"):      # debugging aid: the kernel time of every timed step
         sys.stderr.write("bench.py rank %d: ms per step %s\n" % (rank, " ".join("%.3f" % a.elapsed_time(b) for a, b in ev)))
+    # the state of the last timed step, before anything below sweeps the level again
+    dumped = dump_outputs(lev, args.dump_outputs, world, rank) if args.dump_outputs else None
 
     # N>1: where a step's time goes (untimed extra steps of the serial schedule, an event after every stage; max over ranks)
     breakdown = None
@@ -960,6 +998,8 @@ def main():
                          "kernel": "godunov_sweep_kernel", "kernel_ms": kern_ms,
                          "algorithmic_bytes_per_launch": cells * BYTES_PER_CELL_UPDATE},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if world == 1 and args.fast:
             # the other build of the same kernel, for the record: strict arithmetic
             # (bit-identical to the reference), a few launches after the timed region

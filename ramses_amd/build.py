@@ -113,6 +113,18 @@ def _stale(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
+def _workers():
+    """parallel hipcc jobs: MAX_JOBS when set, else the CPUs this process may run on (not the whole machine's count)"""
+    try:
+        return max(1, int(os.environ["MAX_JOBS"]))
+    except (KeyError, ValueError):
+        pass
+    try:
+        return max(1, len(os.sched_getaffinity(0)))
+    except AttributeError:
+        return os.cpu_count() or 2
+
+
 def build(force=False, verbose=False):
     global BUILD, LIB
     if os.environ.get("RAMSES_AMD_BUILD_VARIANT"):
@@ -146,7 +158,7 @@ def build(force=False, verbose=False):
         return r.stdout
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 2)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), _workers())) as ex:
             list(ex.map(run, jobs))
     if jobs or _stale(LIB, objs):
         run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"])

@@ -4,7 +4,8 @@ the whole parity chain -- to what the reference's test-suite expects.
 
 The checker restates tests/visu/visu_ramses.py::check_solution (:495-667):
 per-variable fsum(log10|x|) for density/pressure, fsum(|x|) otherwise, compared
-with relative tolerance 3e-13.  Needs the reference tree (build container only)."""
+with relative tolerance 3e-13.  The cases' namelists and -ref.dat files are stored
+under tests/golden/reference_hydro/; the programs are built by oracle/build_ref.sh."""
 import math
 import os
 import shutil
@@ -12,8 +13,8 @@ import shutil
 import numpy as np
 import pytest
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASE_DIR = os.path.join(ROOT, "tests", "golden", "reference_hydro")
 
 
 def _read_ref_dat(path):
@@ -52,15 +53,13 @@ def test_reference_golden(name, ndim, tol, variant):
     if variant and name == "implosion" and os.environ.get("RAMSES_AMD_LONG_TESTS") != "1":
         pytest.skip("50 s; the 2-D shims are exercised by the build, the 1-D ones by sod-tube and barotrop (RAMSES_AMD_LONG_TESTS=1 runs it)")
     binary = os.path.join(ROOT, "oracle", "_ref", "ramses%dd%s" % (ndim, variant))
-    case = os.path.join(REF, "tests", "hydro", name)
-    if not (os.path.exists(binary) and os.path.isdir(case)):
-        pytest.skip("needs the reference tree and oracle/_ref/ramses%dd%s (oracle/build_ref.sh ramses %d serial [PATCHDIR])"
-                    % (ndim, variant, ndim))
+    if not os.path.exists(binary):
+        pytest.skip("needs oracle/_ref/ramses%dd%s (oracle/build_ref.sh ramses %d serial [PATCHDIR])" % (ndim, variant, ndim))
     from oracle import ramses_snapshot as rs
     old = os.environ.get("RAMSES_AMD")
     os.environ["RAMSES_AMD"] = "0"
     try:
-        work, out = rs.run_reference(open(os.path.join(case, name + ".nml")).read(), ndim=ndim, binary=binary)
+        work, out = rs.run_reference(open(os.path.join(CASE_DIR, name + ".nml")).read(), ndim=ndim, binary=binary)
     finally:
         if old is None:
             os.environ.pop("RAMSES_AMD", None)
@@ -71,7 +70,7 @@ def test_reference_golden(name, ndim, tol, variant):
         leaf = rs.load_leaf_cells(os.path.join(work, outs[-1]))
     finally:
         shutil.rmtree(work, ignore_errors=True)
-    gold = _read_ref_dat(os.path.join(case, name + "-ref.dat"))
+    gold = _read_ref_dat(os.path.join(CASE_DIR, name + "-ref.dat"))
     data = {"density": leaf["prim"][0], "pressure": leaf["prim"][ndim + 1], "level": leaf["level"].astype(float)}
     for d, ax in enumerate("xyz"[:ndim]):
         data["velocity_" + ax] = leaf["prim"][1 + d]
