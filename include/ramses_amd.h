@@ -46,13 +46,15 @@ enum { RAMSES_AMD_RIEMANN_LLF = 0, RAMSES_AMD_RIEMANN_HLLC = 1,
 /* scheme= of &HYDRO_PARAMS (hydro/umuscl.f90:73-94) */
 enum { RAMSES_AMD_SCHEME_MUSCL = 0, RAMSES_AMD_SCHEME_PLMDE = 1 };
 
+#define RAMSES_AMD_MAX_NENER 2
+
 /* Solver knobs = the &HYDRO_PARAMS namelist group
  * (hydro/read_hydro_params.f90:43-54, defaults hydro/hydro_parameters.f90:75-89).
  * Replaces the module variables of hydro_parameters that the reference's
  * unsplit() reads implicitly. */
 typedef struct ramses_amd_hydro_params {
   int32_t ndim;           /* NDIM of the RAMSES build (3 supported on device) */
-  int32_t nvar;           /* NVAR (= ndim+2, NENER=0)                         */
+  int32_t nvar;           /* NVAR = ndim+2+nener (+ passive scalars)          */
   double gamma;
   double smallr;
   double smallc;
@@ -68,7 +70,16 @@ typedef struct ramses_amd_hydro_params {
    * build), 1 = fast (FMA contraction + reciprocal reuse; <=1e-12 relative
    * L-infinity of the strict path, the tolerance north_star states). */
   int32_t fast_math;
-  int32_t reserved;
+  /* NENER of the RAMSES build: non-thermal energies (cosmic rays, radiation
+   * pressure) in variables ndim+3 .. ndim+2+nener, passive scalars after
+   * them.  0 = none (what every caller that zeroed the former `reserved`
+   * field gets).  1 or 2 on the uniform brick paths only (staged, resident,
+   * MPI-resident; muscl; llf, hll, hllc; no gravity, no difmag): every other
+   * entry point returns RAMSES_AMD_EUNSUPPORTED for nener > 0. */
+  int32_t nener;
+  /* gamma_rad(1:nener) of &HYDRO_PARAMS (hydro/hydro_parameters.f90:79);
+   * read for irad < nener only */
+  double gamma_rad[RAMSES_AMD_MAX_NENER];
 } ramses_amd_hydro_params;
 
 /* Geometry of one level brick on the device. */
@@ -144,6 +155,21 @@ int ramses_amd_courant_brick(const ramses_amd_hydro_params *p,
                              const ramses_amd_brick *b, const double *d_uold,
                              const double *d_grav, double dx, double *d_out,
                              void *stream);
+/* With nener > 0 the courant kernel is cmpdt with the non-thermal energies
+ * (godunov_utils.f90:5-123) and out[3] = eint less them (courant_fine.f90:113-118). */
+
+/* ---------------------------------------------------------------------------
+ * The pdV term of the non-thermal energies (add_pdv_source_terms,
+ * hydro/godunov_fine.f90:294-481, which set_uold calls whenever nener > 0):
+ *   unew(e_irad) -= (gamma_rad-1) * uold(e_irad) * div(u) * dt,
+ *   div(u) = sum over idim of (v(right)-v(left))/(2 dx), v = uold momentum / max(rho, smallr),
+ * on a fully refined brick, before set_uold's swap.  ng = 0: periodic wrap;
+ * ng >= 2: the ghost layers of uold must be current (they are what the sweep
+ * read).  nener must be 1 or 2.
+ * ------------------------------------------------------------------------- */
+int ramses_amd_pdv_brick(const ramses_amd_hydro_params *p, const ramses_amd_brick *b,
+                         const double *d_uold, double *d_unew, double dx, double dt,
+                         void *stream);
 
 /* ---------------------------------------------------------------------------
  * Periodic ghost fill of a brick with ng>=2 from its own interior (the
@@ -628,6 +654,8 @@ int ramses_amd_resident_godunov_f90(const ramses_amd_hydro_params *p, int ilevel
                                     int64_t ncoarse, int nx_loc, const double *uold, double dx,
                                     double dt);
 int ramses_amd_resident_set_uold_f90(int ilevel);
+/* set_uold of a NENER > 0 resident level: the pdV term (ramses_amd_pdv_brick) on the pending result, then the swap */
+int ramses_amd_resident_set_uold_pdv_f90(const ramses_amd_hydro_params *p, int ilevel, double dx, double dt);
 int ramses_amd_resident_sync_host_f90(double *uold);
 int ramses_amd_resident_invalidate(void);
 
@@ -784,6 +812,7 @@ int ramses_amd_halo_plan(int ilevel, int ngrid, const int *igrid, const double *
  *   ramses_amd_mpires_godunov       set_unew + godunov_fine           hydro/godunov_fine.f90:5-130
  *   ramses_amd_mpires_reverse_unew  make_virtual_reverse_dp(unew(1,1:nvar),l)   amr/virtual_boundaries.f90:693-983
  *   ramses_amd_mpires_set_uold      set_uold (buffer swap)            hydro/godunov_fine.f90:135-232
+ *   ramses_amd_mpires_set_uold_pdv  the same with the pdV term of the non-thermal energies first (NENER > 0)
  *   ramses_amd_mpires_halo_forward  make_virtual_fine_dp(uold(1,1:nvar),l) over RCCL   :373-528
  *   ramses_amd_mpires_halo_stage_out / _stage_in   the same with the caller's MPI as transport (pinned host buffers)
  *   ramses_amd_mpires_which         +ivar / -ivar when xx is uold(1,ivar) / unew(1,ivar) of the level, else 0
@@ -799,6 +828,8 @@ int ramses_amd_mpires_courant(const ramses_amd_hydro_params *p, double dx, doubl
 int ramses_amd_mpires_godunov(const ramses_amd_hydro_params *p, double dx, double dt);
 int ramses_amd_mpires_reverse_unew(void);
 int ramses_amd_mpires_set_uold(void);
+/* set_uold of a NENER > 0 level: ramses_amd_pdv_brick on the rank's brick, then the swap (nener = 0: refused) */
+int ramses_amd_mpires_set_uold_pdv(const ramses_amd_hydro_params *p, double dx, double dt);
 int ramses_amd_mpires_halo_forward(void);
 int ramses_amd_mpires_halo_stage_out(double **h_send, const int64_t **send_off, double **h_recv, const int64_t **recv_off);
 int ramses_amd_mpires_halo_stage_out_f90(int64_t *h_send_addr, int64_t *h_recv_addr, int64_t *send_off, int64_t *recv_off, int ncpu);

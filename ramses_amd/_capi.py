@@ -10,6 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # RAMSES_AMD_LIB: load another build of the same library (kernel A/B measurements)
 LIB_PATH = os.environ.get("RAMSES_AMD_LIB") or os.path.join(HERE, "lib", "libramses_amd.so")
 
+# gamma_rad's default, hydro/hydro_parameters.f90:79 (the reference writes 1.33333333334d0, not 4/3)
+GAMMA_RAD = 1.33333333334
 RIEMANN = {"llf": 0, "hllc": 1, "hll": 2, "acoustic": 3, "exact": 4}
 SCHEME = {"muscl": 0, "plmde": 1}
 
@@ -27,7 +29,8 @@ class HydroParams(C.Structure):
         ("slope_theta", C.c_double),
         ("scheme", C.c_int32), ("niter_riemann", C.c_int32),
         ("difmag", C.c_double), ("courant_factor", C.c_double),
-        ("fast_math", C.c_int32), ("reserved", C.c_int32),
+        ("fast_math", C.c_int32), ("nener", C.c_int32),
+        ("gamma_rad", C.c_double * 2),     # RAMSES_AMD_MAX_NENER
     ]
 
 
@@ -56,6 +59,7 @@ SYMBOLS = [
     ("ramses_amd_godunov_tune", _i, [_i, _i]),
     ("ramses_amd_courant_init", _i, [_PP, _d, _vp, _vp]),
     ("ramses_amd_courant_brick", _i, [_PP, _PB, _vp, _vp, _d, _vp, _vp]),
+    ("ramses_amd_pdv_brick", _i, [_PP, _PB, _vp, _vp, _d, _d, _vp]),
     ("ramses_amd_fill_ghosts_periodic", _i, [_PB, _vp, _i, _i, _vp]),
     ("ramses_amd_halo_slab_size", _i64, [_PB, _i, _i]),
     ("ramses_amd_halo_pack", _i, [_PB, _vp, _i, _i, _vp, _vp]),
@@ -140,6 +144,7 @@ SYMBOLS = [
     ("ramses_amd_resident_courant_f90", _i, [_PP, _i, _i, _vp, _vp, _i64, _i64, _i, _vp, _d, _d, _vp]),
     ("ramses_amd_resident_godunov_f90", _i, [_PP, _i, _i, _vp, _vp, _i64, _i64, _i, _vp, _d, _d]),
     ("ramses_amd_resident_set_uold_f90", _i, [_i]),
+    ("ramses_amd_resident_set_uold_pdv_f90", _i, [_PP, _i, _d, _d]),
     ("ramses_amd_resident_sync_host_f90", _i, [_vp]),
     ("ramses_amd_resident_invalidate", _i, []),
     # MPI: one rank per GPU
@@ -179,6 +184,7 @@ SYMBOLS = [
     ("ramses_amd_mpires_godunov", _i, [_PP, _d, _d]),
     ("ramses_amd_mpires_reverse_unew", _i, []),
     ("ramses_amd_mpires_set_uold", _i, []),
+    ("ramses_amd_mpires_set_uold_pdv", _i, [_PP, _d, _d]),
     ("ramses_amd_mpires_halo_forward", _i, []),
     ("ramses_amd_mpires_halo_stage_out", _i, [_vp, _vp, _vp, _vp]),
     ("ramses_amd_mpires_halo_stage_out_f90", _i, [_vp, _vp, _vp, _vp, _i]),
@@ -284,12 +290,14 @@ def check(rc):
 
 def make_params(ndim=3, nvar=None, gamma=1.4, smallr=1e-10, smallc=1e-10, slope_type=1,
                 slope_theta=1.5, riemann="llf", scheme="muscl", niter_riemann=10,
-                difmag=0.0, courant_factor=0.5, fast_math=False):
-    """Defaults are the reference's (hydro/hydro_parameters.f90:75-89)."""
-    return HydroParams(ndim, nvar if nvar else ndim + 2, gamma, smallr, smallc, slope_type,
+                difmag=0.0, courant_factor=0.5, fast_math=False, nener=0, gamma_rad=(GAMMA_RAD, GAMMA_RAD)):
+    """Defaults are the reference's (hydro/hydro_parameters.f90:75-89).  nener: NENER of the build
+    (non-thermal energies in variables ndim+3 .. ndim+2+nener); nvar defaults to ndim+2+nener."""
+    gr = (C.c_double * 2)(*(list(gamma_rad) + [GAMMA_RAD, GAMMA_RAD])[:2])
+    return HydroParams(ndim, nvar if nvar else ndim + 2 + nener, gamma, smallr, smallc, slope_type,
                        RIEMANN[riemann] if isinstance(riemann, str) else riemann, slope_theta,
                        SCHEME[scheme] if isinstance(scheme, str) else scheme, niter_riemann,
-                       difmag, courant_factor, 1 if fast_math else 0, 0)
+                       difmag, courant_factor, 1 if fast_math else 0, int(nener), gr)
 
 
 def dense_brick(nx, ny, nz, ng):

@@ -140,6 +140,7 @@ static int godunov_brick_region(const ramses_amd_hydro_params *p, const ramses_a
   if (!d_uold || !d_unew) return fail(RAMSES_AMD_EINVAL, "uold/unew device pointers are NULL");
   if (d_uold == d_unew) return fail(RAMSES_AMD_EINVAL, "uold and unew must be distinct buffers");
   if (int rc = check_ndim(p, b)) return rc;
+  if (int rc = check_nener(p, d_grav != nullptr)) return rc;
   if (p->nvar < 5 || p->nvar > 7) return fail(RAMSES_AMD_EUNSUPPORTED, "device sweep implements NVAR=5..7 (up to two passive scalars; got %d)", p->nvar);
   if (p->nvar != 5 && p->scheme != RAMSES_AMD_SCHEME_MUSCL) return fail(RAMSES_AMD_EUNSUPPORTED, "passive scalars with scheme='plmde' are not on the device yet");
   if (p->scheme != RAMSES_AMD_SCHEME_MUSCL && p->scheme != RAMSES_AMD_SCHEME_PLMDE) return fail(RAMSES_AMD_EINVAL, "unknown scheme %d", p->scheme);
@@ -169,9 +170,14 @@ static int godunov_brick_region(const ramses_amd_hydro_params *p, const ramses_a
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   for (int region = region_first; region <= region_last; region++) {
     A.region = region;
-    hipError_t e = p->fast_math
-                       ? fastmode::launch_godunov_sweep(A, slope_type, p->riemann, g_tile_rows, p->scheme, p->nvar, d_grav != nullptr, s)
-                       : strictmode::launch_godunov_sweep(A, slope_type, p->riemann, g_tile_rows, p->scheme, p->nvar, d_grav != nullptr, s);
+    hipError_t e;
+    if (p->nener > 0)
+      e = p->fast_math ? fastmode::launch_godunov_sweep_nener(A, slope_type, p->riemann, p->nvar, p->nener, s)
+                       : strictmode::launch_godunov_sweep_nener(A, slope_type, p->riemann, p->nvar, p->nener, s);
+    else
+      e = p->fast_math
+              ? fastmode::launch_godunov_sweep(A, slope_type, p->riemann, g_tile_rows, p->scheme, p->nvar, d_grav != nullptr, s)
+              : strictmode::launch_godunov_sweep(A, slope_type, p->riemann, g_tile_rows, p->scheme, p->nvar, d_grav != nullptr, s);
     if (e != hipSuccess) return hipfail(e, "godunov sweep launch");
   }
   return 0;
@@ -211,6 +217,7 @@ int ramses_amd_courant_brick(const ramses_amd_hydro_params *p, const ramses_amd_
   if (int rc = check_brick(b)) return rc;
   if (int rc = check_ndim(p, b)) return rc;
   if (p->nvar < 5) return fail(RAMSES_AMD_EUNSUPPORTED, "device courant needs the 5 hydro variables (passive scalars do not enter cmpdt)");
+  if (int rc = check_nener(p, d_grav != nullptr)) return rc;
   CourantArgs A;
   A.uold = d_uold; A.grav = d_grav; A.out = d_out;
   A.nx = b->nx; A.ny = b->ny; A.nz = b->nz; A.ng = b->ng;
@@ -220,8 +227,29 @@ int ramses_amd_courant_brick(const ramses_amd_hydro_params *p, const ramses_amd_
   A.dt_init = p->courant_factor * dx / p->smallc;
   A.ndimf = (double)p->ndim;
   A.P = make_const(p);
-  hipError_t e = launch_courant(A, d_grav != nullptr, reinterpret_cast<hipStream_t>(stream));
+  hipError_t e = launch_courant(A, d_grav != nullptr, p->nener, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hipfail(e, "courant launch");
+  return 0;
+}
+
+int ramses_amd_pdv_brick(const ramses_amd_hydro_params *p, const ramses_amd_brick *b, const double *d_uold,
+                         double *d_unew, double dx, double dt, void *stream) {
+  if (!p || !d_uold || !d_unew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (int rc = check_brick(b)) return rc;
+  if (d_uold == d_unew) return fail(RAMSES_AMD_EINVAL, "uold and unew must be distinct buffers");
+  if (p->nener < 1 || p->nener > RAMSES_AMD_MAX_NENER)
+    return fail(RAMSES_AMD_EINVAL, "pdv_brick: the pdV term belongs to the non-thermal energies (NENER=1 or 2, got %d)", p->nener);
+  if (int rc = check_nener(p, false)) return rc;
+  if (!(dx > 0.0) || !(dt >= 0.0)) return fail(RAMSES_AMD_EINVAL, "dx must be >0 and dt >=0");
+  PdvArgs A;
+  A.uold = d_uold; A.unew = d_unew;
+  A.nx = b->nx; A.ny = b->ny; A.nz = b->nz; A.ng = b->ng;
+  A.pitch_y = b->pitch_y; A.pitch_z = b->pitch_z; A.pitch_var = b->pitch_var;
+  A.dx = dx; A.dt = dt; A.smallr = p->smallr;
+  const HydroConst P = make_const(p);
+  A.gm1_rad[0] = P.gm1_rad[0]; A.gm1_rad[1] = P.gm1_rad[1];
+  hipError_t e = launch_pdv(A, p->nener, reinterpret_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return hipfail(e, "pdv launch");
   return 0;
 }
 

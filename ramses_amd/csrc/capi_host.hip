@@ -42,6 +42,7 @@ struct HostCtx {
   bool res_valid = false, res_host_stale = false, res_new_ready = false;
   bool res_grav_valid = false;   // bf holds the acceleration f(:,1:3) of the resident level
   int res_level = 0, res_ngrid = 0, res_nvar = 0;
+  int res_nener = 0;        // NENER of the last params: set_uold must then add the pdV term (ramses_amd_resident_set_uold_pdv_f90)
   long res_ncell = 0, res_ncoarse = 0, res_ngridmax = 0;
   const double *res_host_uold = nullptr;
 };
@@ -175,6 +176,7 @@ int ramses_amd_godunov_fine_amr_device(const ramses_amd_hydro_params *p, int ile
                                        double *d_divu, double *d_enew, double dx, double dt,
                                        int nvector, int interpol_var, int interpol_type,
                                        void *d_work, int *d_err, void *stream) {
+  if (int rc_ = refuse_nener(p, "ramses_amd_godunov_fine_amr_device")) return rc_;
   if ((d_divu == nullptr) != (d_enew == nullptr)) return fail(RAMSES_AMD_EINVAL, "pressure_fix needs both divu and enew");
   if (!p || !d_igrid || !d_son || !d_nbor || !d_father || !d_uold || !d_unew || !d_work || !d_err) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = amr_check(p, ilevel, nvector, interpol_var, interpol_type)) return rc;
@@ -208,6 +210,7 @@ int ramses_amd_godunov_fine_amr_host(const ramses_amd_hydro_params *p, int ileve
                                      const double *uold, double *unew, const double *f,
                                      double *divu, double *enew, double dx, double dt,
                                      int nvector, int interpol_var, int interpol_type) {
+  if (int rc_ = refuse_nener(p, "ramses_amd_godunov_fine_amr_host")) return rc_;
   if (!p || !igrid || !son || !nbor || !father || !uold || !unew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if ((divu == nullptr) != (enew == nullptr)) return fail(RAMSES_AMD_EINVAL, "pressure_fix needs both divu and enew");
   if (int rc = amr_check(p, ilevel, nvector, interpol_var, interpol_type)) return rc;
@@ -272,6 +275,7 @@ int ramses_amd_godunov_fine_amr_f90(const ramses_amd_hydro_params *p, int ilevel
                                     const double *uold, double *unew, const double *f_or_dummy, int has_f,
                                     double *divu_or_dummy, double *enew_or_dummy, int has_pfix,
                                     double dx, double dt, int nvector, int interpol_var, int interpol_type) {
+  if (int rc_ = refuse_nener(p, "ramses_amd_godunov_fine_amr_f90")) return rc_;
   return ramses_amd_godunov_fine_amr_host(p, ilevel, ngrid, igrid, son, nbor, father, ngridmax, ncoarse, uold, unew,
                                           has_f ? f_or_dummy : nullptr, has_pfix ? divu_or_dummy : nullptr,
                                           has_pfix ? enew_or_dummy : nullptr, dx, dt, nvector, interpol_var, interpol_type);
@@ -314,6 +318,7 @@ int64_t ramses_amd_lowdim_reference_sweeps(void) { long n = 0; for (int l = 0; l
 int ramses_amd_godunov_fine_lowdim_f90(const ramses_amd_hydro_params *p, int ilevel, int ngrid, const int *igrid, int nbound,
                                        const int *igrid_bound, const double *xg, int64_t ngridmax, int64_t ncoarse, const int *skip,
                                        const int *nloc, const double *uold, double *unew, double dx, double dt) {
+  if (int rc_ = refuse_nener(p, "ramses_amd_godunov_fine_lowdim_f90")) return rc_;
   if (!p || !igrid || !xg || !skip || !nloc || !uold || !unew || (nbound > 0 && !igrid_bound)) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   const int ndim = p->ndim;
   if (ndim != 1 && ndim != 2) return fail(RAMSES_AMD_EINVAL, "ramses_amd_godunov_fine_lowdim_f90 is the entry of NDIM=1 and NDIM=2 builds (got NDIM=%d)", ndim);
@@ -602,6 +607,7 @@ static int resident_ensure(const ramses_amd_hydro_params *p, int ilevel, int ngr
   if ((long)ngrid * 8 != N)
     return fail(RAMSES_AMD_EUNSUPPORTED, "level %d is not fully refined on this rank (ngrid=%d, need %ld)", ilevel, ngrid, N / 8);
   HostCtx &H = g_host;
+  H.res_nener = p->nener;
   const long ncell = ncoarse + 8 * ngridmax;
   const int nvar = p->nvar;
   if (H.res_valid && H.res_level == ilevel && H.res_ngrid == ngrid && H.res_nvar == nvar && H.res_ncell == ncell &&
@@ -677,7 +683,7 @@ int ramses_amd_resident_godunov_f90(const ramses_amd_hydro_params *p, int ilevel
 }
 
 // set_uold on the resident level: the new state becomes the current one
-int ramses_amd_resident_set_uold_f90(int ilevel) {
+static int resident_swap(int ilevel) {
   HostCtx &H = g_host;
   if (!H.res_valid || H.res_level != ilevel) return fail(RAMSES_AMD_EINVAL, "set_uold: level %d is not resident", ilevel);
   if (!H.res_new_ready) return fail(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending on level %d", ilevel);
@@ -685,6 +691,25 @@ int ramses_amd_resident_set_uold_f90(int ilevel) {
   H.res_new_ready = false;
   H.res_host_stale = true;
   return 0;
+}
+int ramses_amd_resident_set_uold_f90(int ilevel) {
+  if (g_host.res_nener > 0)
+    return fail(RAMSES_AMD_EINVAL, "set_uold: the resident level carries NENER=%d non-thermal energies: their pdV term is "
+                "ramses_amd_resident_set_uold_pdv_f90's", g_host.res_nener);
+  return resident_swap(ilevel);
+}
+
+// set_uold of a NENER > 0 resident level: the pdV term of the non-thermal energies (add_pdv_source_terms,
+// hydro/godunov_fine.f90:166) on the pending result, from the state it was swept from; then the swap
+int ramses_amd_resident_set_uold_pdv_f90(const ramses_amd_hydro_params *p, int ilevel, double dx, double dt) {
+  HostCtx &H = g_host;
+  if (!H.res_valid || H.res_level != ilevel) return fail(RAMSES_AMD_EINVAL, "set_uold: level %d is not resident", ilevel);
+  if (!H.res_new_ready) return fail(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending on level %d", ilevel);
+  const int n = 1 << ilevel;
+  ramses_amd_brick b;
+  ramses_amd_brick_dense(&b, n, n, n, 0);
+  if (int rc = ramses_amd_pdv_brick(p, &b, H.bold.as<double>(), H.bnew.as<double>(), dx, dt, nullptr)) return rc;
+  return resident_swap(ilevel);
 }
 
 // refresh the host array from the resident level (no-op when it is current)

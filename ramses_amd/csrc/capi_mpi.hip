@@ -300,6 +300,7 @@ struct PinBuf {
 struct MpiRes {
   bool valid = false, host_stale = false, new_ready = false;
   int level = 0, ngrid = 0, nvar = 0, ncpu = 0, myid = 0;
+  int nener = 0;        // NENER of the level: set_uold must add the pdV term (ramses_amd_mpires_set_uold_pdv)
   long ncell = 0, ncoarse = 0, ngridmax = 0;
   const double *h_uold = nullptr, *h_unew = nullptr;
   HaloPlan plan;
@@ -403,6 +404,8 @@ int ramses_amd_mpires_setup(const ramses_amd_hydro_params *p, int ilevel, int ng
                             const int *rc_igrid) {
   if (!p || !igrid || !xg || !uold || !unew || !em_ngrid || !rc_ngrid) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   if (p->ndim != 3 || p->nvar < 5 || p->nvar > 7) return failf(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3, NVAR=5..7");
+  if (p->nener < 0 || p->nener > RAMSES_AMD_MAX_NENER || p->nvar < 5 + p->nener)
+    return failf(RAMSES_AMD_EUNSUPPORTED, "NENER=%d with NVAR=%d: the device path implements NENER=0, 1, 2 with NVAR >= 5+NENER", p->nener, p->nvar);
   if (nx_loc != 1) return failf(RAMSES_AMD_EUNSUPPORTED, "device path needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
   if (ncpu < 1 || myid < 1 || myid > ncpu) return failf(RAMSES_AMD_EINVAL, "bad ncpu/myid");
   MpiRes &M = g_mr;
@@ -411,7 +414,7 @@ int ramses_amd_mpires_setup(const ramses_amd_hydro_params *p, int ilevel, int ng
   if (!build_halo_plan(ilevel, ngrid, igrid, xg, ngridmax, ncpu, em_ngrid, em_igrid, rc_ngrid, rc_igrid, M.plan))
     return failf(RAMSES_AMD_EUNSUPPORTED, "%s", M.plan.error.c_str());
   HaloPlan &P = M.plan;
-  M.level = ilevel; M.ngrid = ngrid; M.nvar = p->nvar; M.ncpu = ncpu; M.myid = myid;
+  M.level = ilevel; M.ngrid = ngrid; M.nvar = p->nvar; M.ncpu = ncpu; M.myid = myid; M.nener = p->nener;
   M.ncoarse = ncoarse; M.ngridmax = ngridmax; M.ncell = ncoarse + 8 * ngridmax;
   M.h_uold = uold; M.h_unew = unew;
   M.brick.nx = P.nx; M.brick.ny = P.ny; M.brick.nz = P.nz; M.brick.ng = 2;
@@ -473,7 +476,9 @@ int ramses_amd_mpires_setup(const ramses_amd_hydro_params *p, int ilevel, int ng
   }
   {
     const char *e = getenv("RAMSES_AMD_OVERLAP");
-    M.overlap = !(e && e[0] == '0');
+    // (NENER > 0: set_uold adds the pdV term to unew after the sweep, so the new state's halo cannot leave behind the
+    //  interior sweep; the exchange waits for set_uold)
+    M.overlap = !(e && e[0] == '0') && p->nener == 0;
     // every emission oct must be produced by the shell launch: within one oct of a face shared with a peer
     for (int m = 0; m < nem && M.overlap; m++) {
       bool edge = false;
@@ -575,13 +580,31 @@ int ramses_amd_mpires_reverse_unew(void) {
   return 0;
 }
 
-int ramses_amd_mpires_set_uold(void) {
-  NEED_VALID("set_uold");
-  MpiRes &M = g_mr;
+static int mpires_swap(MpiRes &M) {
   if (!M.new_ready) return failf(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending");
   Buf t = M.bold; M.bold = M.bnew; M.bnew = t;
   M.new_ready = false; M.host_stale = true;
   return 0;
+}
+int ramses_amd_mpires_set_uold(void) {
+  NEED_VALID("set_uold");
+  MpiRes &M = g_mr;
+  if (M.nener > 0)
+    return failf(RAMSES_AMD_EINVAL, "set_uold: the level carries NENER=%d non-thermal energies: their pdV term is "
+                 "ramses_amd_mpires_set_uold_pdv's", M.nener);
+  return mpires_swap(M);
+}
+
+// set_uold of a NENER > 0 level: the pdV term of the non-thermal energies (add_pdv_source_terms, hydro/godunov_fine.f90:
+// 166, 294-481) on unew from uold -- whose ghost octs are the ones the sweep read -- then the swap of set_uold
+int ramses_amd_mpires_set_uold_pdv(const ramses_amd_hydro_params *p, double dx, double dt) {
+  NEED_VALID("set_uold");
+  MpiRes &M = g_mr;
+  if (!M.new_ready) return failf(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending");
+  if (int rc = join_comm(M)) return rc;
+  if (M.prefetched) return failf(RAMSES_AMD_EINVAL, "set_uold with pdV: the new state's halo already left (overlap with NENER > 0)");
+  if (int rc = ramses_amd_pdv_brick(p, &M.brick, M.bold.as<double>(), M.bnew.as<double>(), dx, dt, M.s_comp)) return rc;
+  return mpires_swap(M);
 }
 
 // make_virtual_fine_dp(uold(1,1:nvar),ilevel) over RCCL: pack -> one grouped send/recv -> unpack -> periodic self-fill

@@ -55,7 +55,37 @@ static inline HydroConst make_const(const ramses_amd_hydro_params *p) {
   P.oneovergamma = 1.0 / p->gamma;
   P.slope_theta = p->slope_theta;
   P.niter_riemann = p->niter_riemann;
+  for (int i = 0; i < 2; i++) {
+    const bool on = i < p->nener;
+    P.gamma_rad[i] = on ? p->gamma_rad[i] : 0.0;
+    P.gm1_rad[i] = on ? p->gamma_rad[i] - 1.0 : 0.0;   // (gamma_rad(irad)-one)
+  }
   return P;
+}
+
+// NENER > 0 (non-thermal energies) runs on the uniform brick paths only: every other entry point refuses it by name
+static inline int refuse_nener(const ramses_amd_hydro_params *p, const char *who) {
+  if (p && p->nener != 0)
+    return fail(RAMSES_AMD_EUNSUPPORTED, "%s: NENER=%d (non-thermal energies) is implemented on the uniform brick paths only "
+                "(staged, resident and MPI-resident bricks), not on AMR levels or tiles", who, p->nener);
+  return 0;
+}
+// what a brick sweep with NENER > 0 needs: nener 1 or 2, NVAR >= 5+nener, 3-D, muscl, llf / hll / hllc, no gravity, no difmag
+static inline int check_nener(const ramses_amd_hydro_params *p, bool grav) {
+  if (p->nener == 0) return 0;
+  if (p->nener < 0 || p->nener > RAMSES_AMD_MAX_NENER)
+    return fail(RAMSES_AMD_EUNSUPPORTED, "NENER=%d: the device path implements NENER=0, 1, 2", p->nener);
+  if (p->nvar < 5 + p->nener) return fail(RAMSES_AMD_EUNSUPPORTED, "NENER=%d needs NVAR >= %d (got %d)", p->nener, 5 + p->nener, p->nvar);
+  if (p->ndim != 3) return fail(RAMSES_AMD_EUNSUPPORTED, "NENER>0 needs NDIM=3 (got %d)", p->ndim);
+  if (p->scheme != RAMSES_AMD_SCHEME_MUSCL) return fail(RAMSES_AMD_EUNSUPPORTED, "NENER>0 with scheme='plmde' is not on the device");
+  if (p->riemann != RAMSES_AMD_RIEMANN_LLF && p->riemann != RAMSES_AMD_RIEMANN_HLL && p->riemann != RAMSES_AMD_RIEMANN_HLLC)
+    return fail(RAMSES_AMD_EUNSUPPORTED, "NENER>0 with riemann=%d: the reference's acoustic and exact solvers have no NENER branch "
+                "(llf, hll, hllc only)", p->riemann);
+  if (grav) return fail(RAMSES_AMD_EUNSUPPORTED, "NENER>0 with gravity is not on the device");
+  if (p->difmag > 0.0) return fail(RAMSES_AMD_EUNSUPPORTED, "NENER>0 with difmag>0 is not on the device");
+  for (int i = 0; i < p->nener; i++)
+    if (!(p->gamma_rad[i] > 1.0)) return fail(RAMSES_AMD_EINVAL, "gamma_rad(%d)=%g must be > 1", i + 1, p->gamma_rad[i]);
+  return 0;
 }
 
 // capi_host.hip: the staged entry points reuse the staging buffers of the resident level; refuses while that level holds

@@ -16,6 +16,11 @@ namespace ramses_amd {
 constexpr int RIEMANN_LLF = 0, RIEMANN_HLLC = 1, RIEMANN_HLL = 2,
               RIEMANN_ACOUSTIC = 3, RIEMANN_EXACT = 4;
 
+// NENER: the non-thermal energies occupy variables 5 .. 5+NE-1 (ndim+3 .. ndim+2+nener of the reference); passive scalars
+// start at 5+NE.  Every NE > 0 term below sits in an `if constexpr` (HLLC: a routine of its own), so the NE = 0
+// instantiations are the code they were.
+constexpr int MAX_NENER = 2;
+
 // Constants derived once on the host from &HYDRO_PARAMS.
 struct HydroConst {
   double gamma;
@@ -31,6 +36,9 @@ struct HydroConst {
   double oneovergamma; // 1/gamma
   double slope_theta;
   int niter_riemann;
+  // non-thermal energies (NENER > 0, hydro/hydro_parameters.f90:79): appended, so that no field above moves
+  double gamma_rad[MAX_NENER];
+  double gm1_rad[MAX_NENER];   // gamma_rad-1
 };
 
 #define RA_DEV __device__ __forceinline__
@@ -79,11 +87,12 @@ RA_DEV double dsqrt(double x) { return __builtin_sqrt(x); }
 #endif
 
 // ---------------------------------------------------------------------------
-// ctoprim (hydro/umuscl.f90:861-965) for one cell, 3-D, NENER=0.
-// u = (rho, mx, my, mz, E [, scalars]); g = gravity (or 0); q = (rho,u,v,w,P[,s])
-// The sound speed is not produced: only scheme='plmde' reads it.
+// ctoprim (hydro/umuscl.f90:861-965) for one cell, 3-D.
+// u = (rho, mx, my, mz, E [, non-thermal energies] [, scalars]); g = gravity (or 0);
+// q = (rho,u,v,w,P [, non-thermal pressures (gamma_rad-1)*e] [,s])
+// The sound speed is not produced: only scheme='plmde' reads it (NE = 0 only).
 // ---------------------------------------------------------------------------
-template <int NV, bool GRAV>
+template <int NV, bool GRAV, int NE = 0>
 RA_DEV void ctoprim_cell(const double (&u)[NV], const double (&g)[3],
                          double dtxhalf, const HydroConst &P, double (&q)[NV]) {
   const double rho = dmaxd(u[0], P.smallr);
@@ -97,12 +106,27 @@ RA_DEV void ctoprim_cell(const double (&u)[NV], const double (&g)[3],
   double k2 = vx * vx;
   k2 = __builtin_fma(vy, vy, k2);
   k2 = __builtin_fma(vz, vz, k2);
-  const double eint = dmaxd(__builtin_fma(u[4], oneoverrho, -0.5 * k2), P.smalle);
+  double eint;
+  if constexpr (NE == 0) {
+    eint = dmaxd(__builtin_fma(u[4], oneoverrho, -0.5 * k2), P.smalle);
+  } else {
+    double erad = u[5] * oneoverrho;
+    if constexpr (NE > 1) erad = __builtin_fma(u[6], oneoverrho, erad);
+    eint = dmaxd(__builtin_fma(u[4], oneoverrho, -0.5 * k2) - erad, P.smalle);
+  }
 #else
   double eken = 0.5 * vx * vx;
   eken = eken + 0.5 * vy * vy;
   eken = eken + 0.5 * vz * vz;
-  const double eint = dmaxd(u[4] * oneoverrho - eken, P.smalle);
+  double eint;
+  if constexpr (NE == 0) {
+    eint = dmaxd(u[4] * oneoverrho - eken, P.smalle);
+  } else {
+    // erad = 0 + sum of e_irad/rho (umuscl.f90:903-909)
+    double erad = u[5] * oneoverrho;
+    if constexpr (NE > 1) erad = erad + u[6] * oneoverrho;
+    eint = dmaxd(u[4] * oneoverrho - eken - erad, P.smalle);
+  }
 #endif
   q[0] = rho;
   q[4] = P.gm1 * rho * eint;
@@ -121,7 +145,9 @@ RA_DEV void ctoprim_cell(const double (&u)[NV], const double (&g)[3],
     q[1] = vx; q[2] = vy; q[3] = vz;
   }
 #pragma unroll
-  for (int n = 5; n < NV; n++) q[n] = u[n] * oneoverrho;
+  for (int n = 0; n < NE; n++) q[5 + n] = P.gm1_rad[n] * u[5 + n];
+#pragma unroll
+  for (int n = 5 + NE; n < NV; n++) q[n] = u[n] * oneoverrho;
 }
 
 // sound speed of ctoprim (umuscl.f90:924-930), needed by PLMDE only
@@ -236,8 +262,10 @@ RA_DEV void slope3_var(const double (&nb)[27], double (&d)[3]) {
 // trace3d (hydro/umuscl.f90:483-708) for one cell.
 // dq[d][n]: slope of variable n along d.  Outputs qm[d][n] (state on the +d
 // face of the cell) and qp[d][n] (state on the -d face).
+// NE > 0: the non-thermal pressures e (q[5..5+NE)) -- their gradients push the
+// velocities, e is advected and compressed with gamma_rad (umuscl.f90:583-593).
 // ---------------------------------------------------------------------------
-template <int NV>
+template <int NV, int NE = 0>
 RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
                          double dtdx, double dtdy, double dtdz,
                          const HydroConst &P, double (&qm)[3][NV],
@@ -258,15 +286,32 @@ RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
   };
   const double sr0 = adv(drx, dry, drz, div, r);
   const double sp0 = adv(dpx, dpy, dpz, div * P.gamma, p);
-  const double su0 = adv(dux, duy, duz, dpx, rinv);
-  const double sv0 = adv(dvx, dvy, dvz, dpy, rinv);
-  const double sw0 = adv(dwx, dwy, dwz, dpz, rinv);
+  double su0 = adv(dux, duy, duz, dpx, rinv);
+  double sv0 = adv(dvx, dvy, dvz, dpy, rinv);
+  double sw0 = adv(dwx, dwy, dwz, dpz, rinv);
+  double se0[NE > 0 ? NE : 1];
+#pragma unroll
+  for (int i = 0; i < NE; i++) {
+    su0 = __builtin_fma(-dq[0][5 + i], rinv, su0);
+    sv0 = __builtin_fma(-dq[1][5 + i], rinv, sv0);
+    sw0 = __builtin_fma(-dq[2][5 + i], rinv, sw0);
+    se0[i] = adv(dq[0][5 + i], dq[1][5 + i], dq[2][5 + i], div * P.gamma_rad[i], q[5 + i]);
+  }
 #else
   const double sr0 = -u * drx - v * dry - w * drz - (div)*r;
   const double sp0 = -u * dpx - v * dpy - w * dpz - (div)*P.gamma * p;
-  const double su0 = -u * dux - v * duy - w * duz - (dpx) / r;
-  const double sv0 = -u * dvx - v * dvy - w * dvz - (dpy) / r;
-  const double sw0 = -u * dwx - v * dwy - w * dwz - (dpz) / r;
+  double su0 = -u * dux - v * duy - w * duz - (dpx) / r;
+  double sv0 = -u * dvx - v * dvy - w * dvz - (dpy) / r;
+  double sw0 = -u * dwx - v * dwy - w * dwz - (dpz) / r;
+  double se0[NE > 0 ? NE : 1];
+#pragma unroll
+  for (int i = 0; i < NE; i++) {
+    const double dex = dq[0][5 + i], dey = dq[1][5 + i], dez = dq[2][5 + i];
+    su0 = su0 - (dex) / r;
+    sv0 = sv0 - (dey) / r;
+    sw0 = sw0 - (dez) / r;
+    se0[i] = -u * dex - v * dey - w * dez - (div)*P.gamma_rad[i] * q[5 + i];
+  }
 #endif
   const double s0[5] = {sr0, su0, sv0, sw0, sp0};
   const double dtd[3] = {dtdx, dtdy, dtdz};
@@ -292,10 +337,24 @@ RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
 #endif
     if (qp[d][0] < P.smallr) qp[d][0] = r;
     if (qm[d][0] < P.smallr) qm[d][0] = r;
+#pragma unroll
+    for (int i = 0; i < NE; i++) {
+      const int n = 5 + i;
+#ifdef RAMSES_AMD_FAST
+      const double base = __builtin_fma(se0[i], hdt, q[n]);
+      qp[d][n] = __builtin_fma(-0.5, dq[d][n], base);
+      qm[d][n] = __builtin_fma(0.5, dq[d][n], base);
+#else
+      const double hd = 0.5 * dq[d][n];
+      const double st = se0[i] * dtd[d] * 0.5;
+      qp[d][n] = q[n] - hd + st;
+      qm[d][n] = q[n] + hd + st;
+#endif
+    }
   }
   // passive scalars, umuscl.f90:681-706
 #pragma unroll
-  for (int n = 5; n < NV; n++) {
+  for (int n = 5 + NE; n < NV; n++) {
     const double a = q[n];
     const double sa0 = -u * dq[0][n] - v * dq[1][n] - w * dq[2][n];
 #pragma unroll
@@ -385,16 +444,22 @@ RA_DEV void tracexyz_cell(const double (&q)[NV], const double (&dq)[3][NV], doub
 // back in the same order: (rho, mom_n, E, mom_t1, mom_t2, scalars...).
 // f[NV] = internal-energy flux (only used with pressure_fix).
 // ---------------------------------------------------------------------------
-template <int NV>
+template <int NV, int NE = 0>
 RA_DEV void riemann_llf(const double (&ql)[NV], const double (&qr)[NV],
                         const HydroConst &P, double (&f)[NV + 1]) {
   // godunov_utils.f90:660-820
   const double rl = dmaxd(ql[0], P.smallr), ul = ql[1];
   const double pl = dmaxd(ql[2], rl * P.smallp);
-  const double cl = dsqrt(ddiv(P.gamma * pl, rl));
+  double cl = P.gamma * pl;
+#pragma unroll
+  for (int n = 0; n < NE; n++) cl = cl + P.gamma_rad[n] * ql[5 + n];
+  cl = dsqrt(ddiv(cl, rl));
   const double rr = dmaxd(qr[0], P.smallr), ur = qr[1];
   const double pr = dmaxd(qr[2], rr * P.smallp);
-  const double cr = dsqrt(ddiv(P.gamma * pr, rr));
+  double cr = P.gamma * pr;
+#pragma unroll
+  for (int n = 0; n < NE; n++) cr = cr + P.gamma_rad[n] * qr[5 + n];
+  cr = dsqrt(ddiv(cr, rr));
   const double cmax = dmaxd(__builtin_fabs(ul) + cl, __builtin_fabs(ur) + cr);
   double uL[NV + 1], uR[NV + 1], fL[NV + 1], fR[NV + 1];
   uL[0] = ql[0]; uR[0] = qr[0];
@@ -406,27 +471,45 @@ RA_DEV void riemann_llf(const double (&ql)[NV], const double (&qr)[NV],
   uL[2] = uL[2] + 0.5 * ql[0] * (ql[4] * ql[4]);
   uR[2] = uR[2] + 0.5 * qr[0] * (qr[4] * qr[4]);
 #pragma unroll
-  for (int n = 3; n < NV; n++) { uL[n] = ql[0] * ql[n]; uR[n] = qr[0] * qr[n]; }
+  for (int n = 0; n < NE; n++) {
+    uL[2] = uL[2] + ql[5 + n] / P.gm1_rad[n];
+    uR[2] = uR[2] + qr[5 + n] / P.gm1_rad[n];
+  }
+#pragma unroll
+  for (int n = 3; n < NV; n++) {
+    if (n >= 5 && n < 5 + NE) { uL[n] = ql[n] / P.gm1_rad[n - 5]; uR[n] = qr[n] / P.gm1_rad[n - 5]; }
+    else { uL[n] = ql[0] * ql[n]; uR[n] = qr[0] * qr[n]; }
+  }
   uL[NV] = ql[2] * P.entho; uR[NV] = qr[2] * P.entho;
   fL[0] = ql[1] * uL[0]; fR[0] = qr[1] * uR[0];
   fL[1] = ql[1] * uL[1] + ql[2]; fR[1] = qr[1] * uR[1] + qr[2];
+#pragma unroll
+  for (int n = 0; n < NE; n++) { fL[1] = fL[1] + ql[5 + n]; fR[1] = fR[1] + qr[5 + n]; }
   fL[2] = ql[1] * (uL[2] + ql[2]); fR[2] = qr[1] * (uR[2] + qr[2]);
+#pragma unroll
+  for (int n = 0; n < NE; n++) { fL[2] = fL[2] + ql[1] * ql[5 + n]; fR[2] = fR[2] + qr[1] * qr[5 + n]; }
 #pragma unroll
   for (int n = 3; n <= NV; n++) { fL[n] = ql[1] * uL[n]; fR[n] = qr[1] * uR[n]; }
 #pragma unroll
   for (int n = 0; n <= NV; n++) f[n] = 0.5 * (fL[n] + fR[n] - cmax * (uR[n] - uL[n]));
 }
 
-template <int NV>
+template <int NV, int NE = 0>
 RA_DEV void riemann_hll(const double (&ql)[NV], const double (&qr)[NV],
                         const HydroConst &P, double (&f)[NV + 1]) {
   // godunov_utils.f90:825-983
   const double rl = dmaxd(ql[0], P.smallr), ul = ql[1];
   const double pl = dmaxd(ql[2], rl * P.smallp);
-  const double cl = dsqrt(ddiv(P.gamma * pl, rl));
+  double cl = P.gamma * pl;
+#pragma unroll
+  for (int n = 0; n < NE; n++) cl = cl + P.gamma_rad[n] * ql[5 + n];
+  cl = dsqrt(ddiv(cl, rl));
   const double rr = dmaxd(qr[0], P.smallr), ur = qr[1];
   const double pr = dmaxd(qr[2], rr * P.smallp);
-  const double cr = dsqrt(ddiv(P.gamma * pr, rr));
+  double cr = P.gamma * pr;
+#pragma unroll
+  for (int n = 0; n < NE; n++) cr = cr + P.gamma_rad[n] * qr[5 + n];
+  cr = dsqrt(ddiv(cr, rr));
   const double SL = dmind(dmind(ul, ur) - dmaxd(cl, cr), 0.0);
   const double SR = dmaxd(dmaxd(ul, ur) + dmaxd(cl, cr), 0.0);
   double uL[NV + 1], uR[NV + 1], fL[NV + 1], fR[NV + 1];
@@ -439,11 +522,23 @@ RA_DEV void riemann_hll(const double (&ql)[NV], const double (&qr)[NV],
   uL[2] = uL[2] + 0.5 * ql[0] * (ql[4] * ql[4]);
   uR[2] = uR[2] + 0.5 * qr[0] * (qr[4] * qr[4]);
 #pragma unroll
-  for (int n = 3; n < NV; n++) { uL[n] = ql[0] * ql[n]; uR[n] = qr[0] * qr[n]; }
+  for (int n = 0; n < NE; n++) {
+    uL[2] = uL[2] + ql[5 + n] / P.gm1_rad[n];
+    uR[2] = uR[2] + qr[5 + n] / P.gm1_rad[n];
+  }
+#pragma unroll
+  for (int n = 3; n < NV; n++) {
+    if (n >= 5 && n < 5 + NE) { uL[n] = ql[n] / P.gm1_rad[n - 5]; uR[n] = qr[n] / P.gm1_rad[n - 5]; }
+    else { uL[n] = ql[0] * ql[n]; uR[n] = qr[0] * qr[n]; }
+  }
   uL[NV] = ql[2] * P.entho; uR[NV] = qr[2] * P.entho;
   fL[0] = uL[1]; fR[0] = uR[1];
   fL[1] = ql[2] + uL[1] * ql[1]; fR[1] = qr[2] + uR[1] * qr[1];
+#pragma unroll
+  for (int n = 0; n < NE; n++) { fL[1] = fL[1] + ql[5 + n]; fR[1] = fR[1] + qr[5 + n]; }
   fL[2] = ql[1] * (uL[2] + ql[2]); fR[2] = qr[1] * (uR[2] + qr[2]);
+#pragma unroll
+  for (int n = 0; n < NE; n++) { fL[2] = fL[2] + ql[1] * ql[5 + n]; fR[2] = fR[2] + qr[1] * qr[5 + n]; }
 #pragma unroll
   for (int n = 3; n <= NV; n++) { fL[n] = ql[1] * uL[n]; fR[n] = qr[1] * uR[n]; }
 #pragma unroll
@@ -497,6 +592,95 @@ RA_DEV void riemann_hllc(const double (&ql)[NV], const double (&qr)[NV],
   f[2] = (etoto + Ptoto) * uo;
 #pragma unroll
   for (int n = 3; n < NV; n++) f[n] = ustar > 0 ? ro * uo * ql[n] : ro * uo * qr[n];
+  f[NV] = uo * eo;
+}
+
+// HLLC with NE > 0 non-thermal energies (godunov_utils.f90:988-1209, the NENER branches): total pressure and energy carry
+// them, each is advected with its own star state.  A routine of its own: the NE = 0 one above stays the code it was.
+template <int NV, int NE>
+RA_DEV void riemann_hllc_nener(const double (&ql)[NV], const double (&qr)[NV],
+                               const HydroConst &P, double (&f)[NV + 1]) {
+  const double rl = dmaxd(ql[0], P.smallr);
+  const double Pl = dmaxd(ql[2], rl * P.smallp);
+  const double ul = ql[1];
+  const double el = Pl * P.entho;
+  double ecinl = 0.5 * rl * ul * ul;
+  ecinl = ecinl + 0.5 * rl * (ql[3] * ql[3]);
+  ecinl = ecinl + 0.5 * rl * (ql[4] * ql[4]);
+  double etotl = el + ecinl;
+  // NE > 0: total pressure and energy carry the non-thermal parts (godunov_utils.f90:1036-1049)
+  double eradl[NE > 0 ? NE : 1], eradr[NE > 0 ? NE : 1];
+  double Ptotl = Pl;
+#pragma unroll
+  for (int n = 0; n < NE; n++) { eradl[n] = ql[5 + n] / P.gm1_rad[n]; etotl = etotl + eradl[n]; }
+#pragma unroll
+  for (int n = 0; n < NE; n++) Ptotl = Ptotl + ql[5 + n];
+  const double rr = dmaxd(qr[0], P.smallr);
+  const double Pr = dmaxd(qr[2], rr * P.smallp);
+  const double ur = qr[1];
+  const double er = Pr * P.entho;
+  double ecinr = 0.5 * rr * ur * ur;
+  ecinr = ecinr + 0.5 * rr * (qr[3] * qr[3]);
+  ecinr = ecinr + 0.5 * rr * (qr[4] * qr[4]);
+  double etotr = er + ecinr;
+  double Ptotr = Pr;
+#pragma unroll
+  for (int n = 0; n < NE; n++) { eradr[n] = qr[5 + n] / P.gm1_rad[n]; etotr = etotr + eradr[n]; }
+#pragma unroll
+  for (int n = 0; n < NE; n++) Ptotr = Ptotr + qr[5 + n];
+  double cfastl = P.gamma * Pl;
+#pragma unroll
+  for (int n = 0; n < NE; n++) cfastl = cfastl + P.gamma_rad[n] * ql[5 + n];
+  cfastl = dsqrt(dmaxd(ddiv(cfastl, rl), P.smallc2));
+  double cfastr = P.gamma * Pr;
+#pragma unroll
+  for (int n = 0; n < NE; n++) cfastr = cfastr + P.gamma_rad[n] * qr[5 + n];
+  cfastr = dsqrt(dmaxd(ddiv(cfastr, rr), P.smallc2));
+  const double SL = dmind(ul, ur) - dmaxd(cfastl, cfastr);
+  const double SR = dmaxd(ul, ur) + dmaxd(cfastl, cfastr);
+  const double rcl = rl * (ul - SL);
+  const double rcr = rr * (SR - ur);
+  // (ddiv: the IEEE division in the strict build, v_rcp_f64 + a Newton step in the fast one; the conversions
+  //  e = p/(gamma_rad-1) above stay IEEE divisions in both, as in the LLF and HLL solvers)
+  const double ustar = ddiv(rcr * ur + rcl * ul + (Ptotl - Ptotr), rcr + rcl);
+  const double Ptotstar = ddiv(rcr * Ptotl + rcl * Ptotr + rcl * rcr * (ul - ur), rcr + rcl);
+  const double rstarl = ddiv(rl * (SL - ul), SL - ustar);
+  const double etotstarl = ddiv((SL - ul) * etotl - Ptotl * ul + Ptotstar * ustar, SL - ustar);
+  const double estarl = ddiv(el * (SL - ul), SL - ustar);
+  double eradstarl[NE > 0 ? NE : 1], eradstarr[NE > 0 ? NE : 1], erado[NE > 0 ? NE : 1];
+#pragma unroll
+  for (int n = 0; n < NE; n++) eradstarl[n] = ddiv(eradl[n] * (SL - ul), SL - ustar);
+  const double rstarr = ddiv(rr * (SR - ur), SR - ustar);
+  const double etotstarr = ddiv((SR - ur) * etotr - Ptotr * ur + Ptotstar * ustar, SR - ustar);
+  const double estarr = ddiv(er * (SR - ur), SR - ustar);
+#pragma unroll
+  for (int n = 0; n < NE; n++) eradstarr[n] = ddiv(eradr[n] * (SR - ur), SR - ustar);
+  double ro, uo, Ptoto, etoto, eo;
+  if (SL > 0.0) {
+    ro = rl; uo = ul; Ptoto = Ptotl; etoto = etotl; eo = el;
+#pragma unroll
+    for (int n = 0; n < NE; n++) erado[n] = eradl[n];
+  } else if (ustar > 0.0) {
+    ro = rstarl; uo = ustar; Ptoto = Ptotstar; etoto = etotstarl; eo = estarl;
+#pragma unroll
+    for (int n = 0; n < NE; n++) erado[n] = eradstarl[n];
+  } else if (SR > 0.0) {
+    ro = rstarr; uo = ustar; Ptoto = Ptotstar; etoto = etotstarr; eo = estarr;
+#pragma unroll
+    for (int n = 0; n < NE; n++) erado[n] = eradstarr[n];
+  } else {
+    ro = rr; uo = ur; Ptoto = Ptotr; etoto = etotr; eo = er;
+#pragma unroll
+    for (int n = 0; n < NE; n++) erado[n] = eradr[n];
+  }
+  f[0] = ro * uo;
+  f[1] = ro * uo * uo + Ptoto;
+  f[2] = (etoto + Ptoto) * uo;
+#pragma unroll
+  for (int n = 3; n < NV; n++) {
+    if (n >= 5 && n < 5 + NE) f[n] = uo * erado[n - 5];
+    else f[n] = ustar > 0 ? ro * uo * ql[n] : ro * uo * qr[n];
+  }
   f[NV] = uo * eo;
 }
 
@@ -614,12 +798,17 @@ RA_DEV void riemann_exact(const double (&ql)[NV], const double (&qr)[NV],
   gdnv_to_flux<NV>(qg, P, f);
 }
 
-template <int RS, int NV>
+// (NE > 0: LLF, HLL and HLLC only -- the reference's acoustic and exact solvers have no NENER branch)
+template <int RS, int NV, int NE = 0>
 RA_DEV void riemann_solve(const double (&ql)[NV], const double (&qr)[NV],
                           const HydroConst &P, double (&f)[NV + 1]) {
-  if (RS == RIEMANN_LLF) riemann_llf<NV>(ql, qr, P, f);
-  else if (RS == RIEMANN_HLLC) riemann_hllc<NV>(ql, qr, P, f);
-  else if (RS == RIEMANN_HLL) riemann_hll<NV>(ql, qr, P, f);
+  static_assert(NE == 0 || RS == RIEMANN_LLF || RS == RIEMANN_HLLC || RS == RIEMANN_HLL, "NENER > 0: llf, hll, hllc");
+  if (RS == RIEMANN_LLF) riemann_llf<NV, NE>(ql, qr, P, f);
+  else if (RS == RIEMANN_HLLC) {
+    if constexpr (NE > 0) riemann_hllc_nener<NV, NE>(ql, qr, P, f);
+    else riemann_hllc<NV>(ql, qr, P, f);
+  }
+  else if (RS == RIEMANN_HLL) riemann_hll<NV, NE>(ql, qr, P, f);
   else if (RS == RIEMANN_ACOUSTIC) riemann_acoustic<NV>(ql, qr, P, f);
   else riemann_exact<NV>(ql, qr, P, f);
 }
@@ -631,7 +820,7 @@ RA_DEV void riemann_solve(const double (&ql)[NV], const double (&qr)[NV],
 // (rho, mx, my, mz, E, ...), unscaled; eflux = internal energy flux,
 // unorm = half*(uL_n+uR_n)  (the reference's tmp(:,1:2)).
 // ---------------------------------------------------------------------------
-template <int RS, int NV, int DIR>
+template <int RS, int NV, int DIR, int NE = 0>
 RA_DEV void interface_flux(const double (&qL)[NV], const double (&qR)[NV],
                            const HydroConst &P, double (&flux)[NV],
                            double &unorm, double &eflux) {
@@ -646,7 +835,7 @@ RA_DEV void interface_flux(const double (&qL)[NV], const double (&qR)[NV],
   a[4] = qL[lt2]; b[4] = qR[lt2];
 #pragma unroll
   for (int n = 5; n < NV; n++) { a[n] = qL[n]; b[n] = qR[n]; }
-  riemann_solve<RS, NV>(a, b, P, f);
+  riemann_solve<RS, NV, NE>(a, b, P, f);
   flux[0] = f[0];
   flux[ln] = f[1];
   flux[lt1] = f[3];
@@ -758,7 +947,7 @@ RA_DEV void hllc_flux_fast(const double (&qL)[5], const double (&qR)[5],
 // FUSE_HLLC = false: the sweep of a level in tiles and its surface pass (which must agree with each other flux by flux) take
 // the generic HLLC routine -- their kernels carry the tile bookkeeping on top and the fused flux's live values spill there:
 // 256^3 level in tiles 1.005 ms fused, 0.830 ms generic; shell level 2.40 / 1.98 ms (profiles/r06_hllc_fast.txt)
-template <int RS, int NV, int DIR, bool FUSE_HLLC = true>
+template <int RS, int NV, int DIR, bool FUSE_HLLC = true, int NE = 0>
 RA_DEV void scaled_interface_flux(const double (&qL)[NV], const double (&qR)[NV],
                                   const HydroConst &P, double dt, double dx, double rdx,
                                   double dtdx, bool DXPOW2, double (&flux)[NV]) {
@@ -776,7 +965,7 @@ RA_DEV void scaled_interface_flux(const double (&qL)[NV], const double (&qR)[NV]
   }
 #endif
   double un_, ef_;
-  interface_flux<RS, NV, DIR>(qL, qR, P, flux, un_, ef_);
+  interface_flux<RS, NV, DIR, NE>(qL, qR, P, flux, un_, ef_);
 #pragma unroll
   for (int n = 0; n < NV; n++) {
 #ifdef RAMSES_AMD_FAST
@@ -805,7 +994,7 @@ RA_DEV void scaled_interface_flux_tmp(const double (&qL)[NV], const double (&qR)
 // ---------------------------------------------------------------------------
 // cmpdt (hydro/godunov_utils.f90:5-120) for one cell, 3-D.
 // ---------------------------------------------------------------------------
-template <int NV, bool GRAV>
+template <int NV, bool GRAV, int NE = 0>
 RA_DEV double cmpdt_cell(const double (&u)[NV], const double (&g)[3], double dx,
                          double courant_factor, const HydroConst &P, double ndimf = 3.0) {
   const double rho = dmaxd(u[0], P.smallr);
@@ -814,8 +1003,12 @@ RA_DEV double cmpdt_cell(const double (&u)[NV], const double (&g)[3], double dx,
   e = e - 0.5 * rho * (vx * vx);
   e = e - 0.5 * rho * (vy * vy);
   e = e - 0.5 * rho * (vz * vz);
+#pragma unroll
+  for (int n = 0; n < NE; n++) e = e - u[5 + n];
   double pc = dmaxd(P.gm1 * e, rho * P.smallp);
   pc = P.gamma * pc;
+#pragma unroll
+  for (int n = 0; n < NE; n++) pc = pc + P.gamma_rad[n] * (P.gm1_rad[n] * u[5 + n]);
   pc = __builtin_sqrt(pc / rho);
   pc = ndimf * pc;   // dble(ndim)*c: 1-D/2-D problems embedded in a brick keep their own NDIM
   pc = pc + __builtin_fabs(vx);

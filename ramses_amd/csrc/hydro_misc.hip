@@ -26,9 +26,11 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-template <bool GRAV>
-__global__ __launch_bounds__(256) void courant_kernel(CourantArgs A) {
-  constexpr int NV = 5;
+// NE > 0: cmpdt with the non-thermal energies and eint_loc less them (courant_fine.f90:113-118); the kernel
+// of NE = 0 (courant_kernel) is the body instantiated as before
+template <bool GRAV, int NE>
+__device__ __forceinline__ void courant_body(const CourantArgs &A) {
+  constexpr int NV = 5 + NE;
   const HydroConst &P = A.P;
   const long nrow = (long)A.ny * A.nz;
   double dtmin = A.dt_init;
@@ -47,7 +49,7 @@ __global__ __launch_bounds__(256) void courant_kernel(CourantArgs A) {
 #pragma unroll
         for (int d = 0; d < 3; d++) g[d] = A.grav[base + i + (long)d * A.pitch_var];
       }
-      dtmin = __builtin_fmin(dtmin, cmpdt_cell<NV, GRAV>(u, g, A.dx, A.courant_factor, P, A.ndimf));
+      dtmin = __builtin_fmin(dtmin, cmpdt_cell<NV, GRAV, NE>(u, g, A.dx, A.courant_factor, P, A.ndimf));
       mass += u[0] * A.vol;
       etot += u[4] * A.vol;
       double ei = u[4] * A.vol;
@@ -55,6 +57,8 @@ __global__ __launch_bounds__(256) void courant_kernel(CourantArgs A) {
       ei -= 0.5 * (u[1] * u[1]) / rho * A.vol;
       ei -= 0.5 * (u[2] * u[2]) / rho * A.vol;
       ei -= 0.5 * (u[3] * u[3]) / rho * A.vol;
+#pragma unroll
+      for (int n = 0; n < NE; n++) ei -= u[5 + n] * A.vol;
       eint += ei;
     }
   }
@@ -74,6 +78,16 @@ __global__ __launch_bounds__(256) void courant_kernel(CourantArgs A) {
   }
 }
 
+template <bool GRAV>
+__global__ __launch_bounds__(256) void courant_kernel(CourantArgs A) {
+  courant_body<GRAV, 0>(A);
+}
+
+template <int NE>
+__global__ __launch_bounds__(256) void courant_nener_kernel(CourantArgs A) {
+  courant_body<false, NE>(A);
+}
+
 __global__ void courant_init_kernel(double *out, double dt_init) {
   out[0] = dt_init; out[1] = 0.0; out[2] = 0.0; out[3] = 0.0;
 }
@@ -83,13 +97,78 @@ hipError_t launch_courant_init(double *out, double dt_init, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_courant(const CourantArgs &A, bool grav, hipStream_t s) {
+hipError_t launch_courant(const CourantArgs &A, bool grav, int nener, hipStream_t s) {
   const long nrow = (long)A.ny * A.nz;
   int grid = (int)((nrow + 3) / 4);
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
-  if (grav) hipLaunchKernelGGL(courant_kernel<true>, dim3(grid), dim3(256), 0, s, A);
+  if (nener == 1 && !grav) hipLaunchKernelGGL(courant_nener_kernel<1>, dim3(grid), dim3(256), 0, s, A);
+  else if (nener == 2 && !grav) hipLaunchKernelGGL(courant_nener_kernel<2>, dim3(grid), dim3(256), 0, s, A);
+  else if (nener != 0) return hipErrorInvalidValue;
+  else if (grav) hipLaunchKernelGGL(courant_kernel<true>, dim3(grid), dim3(256), 0, s, A);
   else hipLaunchKernelGGL(courant_kernel<false>, dim3(grid), dim3(256), 0, s, A);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The pdV term of the non-thermal energies (add_pdv_source_terms, hydro/godunov_fine.f90:294-481, loop :422-429) on a
+// fully refined brick, before set_uold's swap:
+//   divu = sum over idim of (veld - velg)/(dx_g + dx_d),  vel = uold(mom)/max(uold(rho), smallr) of the two neighbours
+//   unew(e_irad) = unew(e_irad) - (gamma_rad-1)*uold(e_irad)*divu*dt
+// Every neighbour of a cell of a fully refined level exists (dx_g = dx_d = dx).  One lane per cell along x, one wavefront
+// per row segment of 64 cells: the six neighbour loads of a lane are coalesced row reads (x +- 1 are the lanes beside it).
+// ng = 0: periodic wrap; ng >= 2: the ghost layers of uold hold the neighbours.
+// ---------------------------------------------------------------------------
+template <int NE>
+__global__ __launch_bounds__(256) void pdv_kernel(PdvArgs A) {
+  const long nrow = (long)A.ny * A.nz;
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const long nwaves = (long)gridDim.x * 4;
+  const double dxs = A.dx + A.dx;
+  for (long row = wave; row < nrow; row += nwaves) {
+    const int k = (int)(row / A.ny), j = (int)(row % A.ny);
+    for (int i = lane; i < A.nx; i += 64) {
+      long c, nb[6];
+      if (A.ng == 0) {
+        const int im = i == 0 ? A.nx - 1 : i - 1, ip = i == A.nx - 1 ? 0 : i + 1;
+        const int jm = j == 0 ? A.ny - 1 : j - 1, jp = j == A.ny - 1 ? 0 : j + 1;
+        const int km = k == 0 ? A.nz - 1 : k - 1, kp = k == A.nz - 1 ? 0 : k + 1;
+        const long yz = (long)j * A.pitch_y + (long)k * A.pitch_z;
+        c = yz + i;
+        nb[0] = yz + im; nb[1] = yz + ip;
+        nb[2] = (long)jm * A.pitch_y + (long)k * A.pitch_z + i; nb[3] = (long)jp * A.pitch_y + (long)k * A.pitch_z + i;
+        nb[4] = (long)j * A.pitch_y + (long)km * A.pitch_z + i; nb[5] = (long)j * A.pitch_y + (long)kp * A.pitch_z + i;
+      } else {
+        c = (long)(j + A.ng) * A.pitch_y + (long)(k + A.ng) * A.pitch_z + A.ng + i;
+        nb[0] = c - 1; nb[1] = c + 1;
+        nb[2] = c - A.pitch_y; nb[3] = c + A.pitch_y;
+        nb[4] = c - A.pitch_z; nb[5] = c + A.pitch_z;
+      }
+      double divu = 0.0;
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        const double velg = A.uold[nb[2 * d] + (long)(1 + d) * A.pitch_var] / __builtin_fmax(A.uold[nb[2 * d]], A.smallr);
+        const double veld = A.uold[nb[2 * d + 1] + (long)(1 + d) * A.pitch_var] / __builtin_fmax(A.uold[nb[2 * d + 1]], A.smallr);
+        divu = divu + (veld - velg) / dxs;
+      }
+#pragma unroll
+      for (int n = 0; n < NE; n++) {
+        const long o = c + (long)(5 + n) * A.pitch_var;
+        A.unew[o] = A.unew[o] - A.gm1_rad[n] * A.uold[o] * divu * A.dt;
+      }
+    }
+  }
+}
+
+hipError_t launch_pdv(const PdvArgs &A, int nener, hipStream_t s) {
+  const long nrow = (long)A.ny * A.nz;
+  int grid = (int)((nrow + 3) / 4);
+  if (grid > 2048) grid = 2048;
+  if (grid < 1) grid = 1;
+  if (nener == 1) hipLaunchKernelGGL(pdv_kernel<1>, dim3(grid), dim3(256), 0, s, A);
+  else if (nener == 2) hipLaunchKernelGGL(pdv_kernel<2>, dim3(grid), dim3(256), 0, s, A);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

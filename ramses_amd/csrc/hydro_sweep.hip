@@ -143,7 +143,7 @@ __device__ __forceinline__ int dir_load(const int *base, unsigned plane_ints, un
 // the level is stored in tiles of 32 x 4 x 4 octs, a lane finds the cell of its (plane, column) through the tile directory
 // (one 4-byte load per 8 planes, issued four planes ahead; 256-byte runs of a variable along x inside a tile), the status byte of
 // the cell says whether it is refined (fluxes reset), updated (stored) or a ghost (interpolated: fluxes filed for the coarser level)
-template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, int ROLE, bool MASK>
+template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, int ROLE, bool MASK, int NE = 0>
 __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *smem_raw) {
   const bool DXPOW2 = A.pow2 != 0;   // uniform
   typedef Lds<ST, BY, NV, MASK, GRAV> L;
@@ -365,7 +365,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
   {
     double u[NV], g[3], q[NV];
     load_u(z0 - 2, u); load_g(z0 - 2, g);
-    ctoprim_cell<NV, GRAV>(u, g, dtxhalf, P, q);
+    ctoprim_cell<NV, GRAV, NE>(u, g, dtxhalf, P, q);
 #pragma unroll
     for (int n = 0; n < NV; n++) qring[sa].v[n][ty][tx] = q[n];
     load_u(z0 - 1, u); load_g(z0 - 1, g);
@@ -373,7 +373,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #pragma unroll
       for (int n = 0; n < NV; n++) ukeep[n] = u[n];
     }
-    ctoprim_cell<NV, GRAV>(u, g, dtxhalf, P, q);
+    ctoprim_cell<NV, GRAV, NE>(u, g, dtxhalf, P, q);
 #pragma unroll
     for (int n = 0; n < NV; n++) qring[sb].v[n][ty][tx] = q[n];
     load_u(z0, upre); load_g(z0, gpre);
@@ -419,7 +419,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     Plane<L::MR, NV> &Mprev = mring[(c & 1) ^ 1];
     // ---- phase A: plane c+1 arrives; trace plane c; x and z fluxes ------------------
     double qc[NV];
-    ctoprim_cell<NV, GRAV>(upre, gpre, dtxhalf, P, qc);
+    ctoprim_cell<NV, GRAV, NE>(upre, gpre, dtxhalf, P, qc);
     // plane c+1 goes into the ring: into its own slot (RING 3), or into the slot of plane c-1 as soon as this thread has taken
     // its z slope from it (RING 2; the rows that take no slopes have nothing to wait for)
     if (RING == 3 || !r_trace) {
@@ -494,7 +494,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       }
       double qm[3][NV], qp[3][NV];
       if (SCHEME == 0) {
-        trace3d_cell<NV>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp);
+        trace3d_cell<NV, NE>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp);
       } else {
         const double cc = ctoprim_sound(qb[0], qb[4], P);
         tracexyz_cell<NV>(qb, dq, cc, dtdx, dtdx, dtdx, P, qm, qp);
@@ -507,9 +507,9 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
         double qL[NV], fx[NV], fz[NV];
 #pragma unroll
         for (int n = 0; n < NV; n++) qL[n] = wave_shr1(qm[0][n]);  // +x state of column tx-1
-        scaled_interface_flux<RS, NV, 0, !MASK>(qL, qp[0], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fx);
+        scaled_interface_flux<RS, NV, 0, !MASK, NE>(qL, qp[0], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fx);
         // z flux through the face between planes c-1 and c
-        scaled_interface_flux<RS, NV, 2, !MASK>(qmz, qp[2], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fz);
+        scaled_interface_flux<RS, NV, 2, !MASK, NE>(qmz, qp[2], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fz);
         if (MASK) {
           // hydro/godunov_fine.f90:720-747: the flux through a face is reset when the cell on either side is refined
           const int s_xm = wave_shr1_i(okc);
@@ -527,10 +527,10 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
           // (LATE: the state the update starts from joins in phase B of the next iteration -- a whole trace after its load)
           px[n] = LATE ? (fx[n] - fxh[n]) : ucur[n] + (fx[n] - fxh[n]);
         }
-        if (NV > 5 && !MASK) {
+        if (NV > 5 + NE && !MASK) {
           rnew = ucur[0];
 #pragma unroll
-          for (int n = 5; n < NV; n++) snew[n - 5] = ucur[n];
+          for (int n = 5 + NE; n < NV; n++) snew[n - 5] = ucur[n];
         }
       }
     }
@@ -557,7 +557,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       double qL[NV];
 #pragma unroll
       for (int n = 0; n < NV; n++) qL[n] = M.v[n][tym - M0][tx];
-      scaled_interface_flux<RS, NV, 1, !MASK>(qL, qpy, P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fy);
+      scaled_interface_flux<RS, NV, 1, !MASK, NE>(qL, qpy, P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fy);
       if (MASK) {
         ok_ym = smask[((c + 3) % 3 * BY + tym) * BX + tx];
         const bool zy = ((okc | ok_ym) & CELL_REFINED) != 0;
@@ -582,20 +582,20 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
         const double part = (LATE ? bcar[n] + pxn : pxn) + (fyn - fyh[n]);
         un[n] = part + dz[n];
       }
-      if (NV > 5 && !MASK) {
+      if (NV > 5 + NE && !MASK) {
         // set_uold's passive-scalar fix near the density floor
         // (hydro/godunov_fine.f90:176-190), fused: the kernel's output is the new uold
         // (MASK: the kernel's output is unew; set_uold of the resident level applies the fix, csrc/capi_amr.hip lvl_set_uold)
         if (rold < P.smallr && un[0] > rold) {
 #pragma unroll
-          for (int n = 5; n < NV; n++) un[n] = sold[n - 5] * dmaxd(un[0], P.smallr) / P.smallr;
+          for (int n = 5 + NE; n < NV; n++) un[n] = sold[n - 5] * dmaxd(un[0], P.smallr) / P.smallr;
         } else if (un[0] < P.smallr && rold > un[0]) {
 #pragma unroll
-          for (int n = 5; n < NV; n++) un[n] = sold[n - 5] * P.smallr / dmaxd(rold, P.smallr);
+          for (int n = 5 + NE; n < NV; n++) un[n] = sold[n - 5] * P.smallr / dmaxd(rold, P.smallr);
         }
         rold = rnew;
 #pragma unroll
-        for (int n = 5; n < NV; n++) sold[n - 5] = snew[n - 5];
+        for (int n = 5 + NE; n < NV; n++) sold[n - 5] = snew[n - 5];
       }
 #pragma unroll
       for (int n = 0; n < NV; n++) {
@@ -635,6 +635,22 @@ __global__ __launch_bounds__(BX *BY) void godunov_sweep_kernel(SweepArgs A) {
   else if (ty == 1) sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_LOW, MASK>(A, smem_raw);
   else if (ty == BY - 2) sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_HIGH, MASK>(A, smem_raw);
   else sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_FULL, MASK>(A, smem_raw);
+}
+
+// NENER > 0 (the non-thermal energies in variables 5 .. 5+NE-1, passive scalars after them): the 8-row layout of the
+// passive-scalar kernels of the same NV, muscl, no gravity, the plain brick (no tiles).  A kernel of its own so that the
+// symbols and the code of the NE = 0 kernels stay what they were.
+template <int ST, int RS, int NV, int NE>
+__global__ __launch_bounds__(BX * 8) void godunov_sweep_nener_kernel(SweepArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int BY = 8;
+  const int ty = threadIdx.y;
+  if (ty >= 2 && ty <= BY - 3) __builtin_amdgcn_s_setprio(3);
+  if (ty == 0) sweep_march<ST, RS, BY, false, 0, NV, ROLE_HALO, false, NE>(A, smem_raw);
+  else if (ty == BY - 1) sweep_march<ST, RS, BY, false, 0, NV, ROLE_HALO_HI, false, NE>(A, smem_raw);
+  else if (ty == 1) sweep_march<ST, RS, BY, false, 0, NV, ROLE_LOW, false, NE>(A, smem_raw);
+  else if (ty == BY - 2) sweep_march<ST, RS, BY, false, 0, NV, ROLE_HIGH, false, NE>(A, smem_raw);
+  else sweep_march<ST, RS, BY, false, 0, NV, ROLE_FULL, false, NE>(A, smem_raw);
 }
 
 // ---------------------------------------------------------------------------
@@ -878,14 +894,8 @@ static hipError_t launch2(const SweepArgs &A, bool grav, hipStream_t s) {
   return grav ? launch3<ST, RS, BY, true, SCHEME, NV>(A, s) : launch3<ST, RS, BY, false, SCHEME, NV>(A, s);
 }
 
-template <int ST, int RS>
-static hipError_t launch1(SweepArgs &A, int by, int scheme, int nvar, bool grav, hipStream_t s) {
-  // 8-row tiles (2 waves/SIMD, 256 VGPRs, smaller LDS planes) for the
-  // register/LDS-hungry variants: the Newton solver, the 27-point slope, the
-  // PLMDE tracing and runs with passive scalars
-  const bool heavy = (RS == RIEMANN_EXACT) || (ST == 3) || (ST == 4) || (ST == 5) || (ST == 6) || (scheme != 0) || (nvar != 5);
-  if (by == 0 || heavy) by = heavy ? 8 : 12;
-  // tiles of the whole brick, then the boxes this launch covers (A.region)
+// tiles of the whole brick, then the boxes this launch covers (A.region); 0 = nothing to sweep, -1 = bad region
+static int plan_boxes(SweepArgs &A, int by) {
   const int NTX = (A.nx + (BX - 4) - 1) / (BX - 4);
   const int NTY = (A.ny + (by - 4) - 1) / (by - 4);
   // Boundary shell / interior split used to overlap the halo exchange with the
@@ -920,10 +930,23 @@ static hipError_t launch1(SweepArgs &A, int by, int scheme, int nvar, bool grav,
     add_box(0, NTX, 0, NTY, 0, zb, zs);                                 // z low slab
     add_box(0, NTX, 0, NTY, A.nz - zb, A.nz, zs);                       // z high slab
   } else {
-    return hipErrorInvalidValue;
+    return -1;
   }
-  if (nblocks == 0) return hipSuccess;
+  if (nblocks == 0) return 0;
   A.nblocks = nblocks;
+  return nblocks;
+}
+
+template <int ST, int RS>
+static hipError_t launch1(SweepArgs &A, int by, int scheme, int nvar, bool grav, hipStream_t s) {
+  // 8-row tiles (2 waves/SIMD, 256 VGPRs, smaller LDS planes) for the
+  // register/LDS-hungry variants: the Newton solver, the 27-point slope, the
+  // PLMDE tracing and runs with passive scalars
+  const bool heavy = (RS == RIEMANN_EXACT) || (ST == 3) || (ST == 4) || (ST == 5) || (ST == 6) || (scheme != 0) || (nvar != 5);
+  if (by == 0 || heavy) by = heavy ? 8 : 12;
+  const int planned = plan_boxes(A, by);
+  if (planned < 0) return hipErrorInvalidValue;
+  if (planned == 0) return hipSuccess;
   if (A.stat) {
     // a level of a resident AMR run in tiles: the 12-row muscl kernels on the periodic box of the level, one workgroup per
     // work item (anything else: the caller keeps the tree-walking sweep)
@@ -972,6 +995,43 @@ static hipError_t launch1(SweepArgs &A, int by, int scheme, int nvar, bool grav,
   }
 }
 
+// NENER > 0: (NE, NV) = (1, 6), (1, 7) [one passive scalar], (2, 7); LLF, HLL, HLLC; muscl, no gravity, the plain brick
+template <int ST, int RS, int NV, int NE>
+static hipError_t launch_nener3(SweepArgs &A, hipStream_t s) {
+  const size_t lds = Lds<ST, 8, NV, false, false>::bytes;
+  auto k = godunov_sweep_nener_kernel<ST, RS, NV, NE>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(A.nblocks), dim3(BX, 8), lds, s, A);
+  return hipGetLastError();
+}
+template <int ST, int RS>
+static hipError_t launch_nener1(SweepArgs &A, int nvar, int nener, hipStream_t s) {
+  if (A.stat) return hipErrorInvalidValue;
+  const int planned = plan_boxes(A, 8);
+  if (planned < 0) return hipErrorInvalidValue;
+  if (planned == 0) return hipSuccess;
+  if (nener == 1 && nvar == 6) return launch_nener3<ST, RS, 6, 1>(A, s);
+  if (nener == 1 && nvar == 7) return launch_nener3<ST, RS, 7, 1>(A, s);
+  if (nener == 2 && nvar == 7) return launch_nener3<ST, RS, 7, 2>(A, s);
+  return hipErrorInvalidValue;
+}
+template <int ST>
+hipError_t launch0_nener(SweepArgs &A, int rs, int nvar, int nener, hipStream_t s) {
+  if constexpr (ST == 4 || ST == 5 || ST == 6) {
+    return hipErrorInvalidValue;
+  } else {
+    switch (rs) {
+      case RIEMANN_LLF: return launch_nener1<ST, RIEMANN_LLF>(A, nvar, nener, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+      case RIEMANN_HLLC: return launch_nener1<ST, RIEMANN_HLLC>(A, nvar, nener, s);
+      case RIEMANN_HLL: return launch_nener1<ST, RIEMANN_HLL>(A, nvar, nener, s);
+#endif
+    }
+    return hipErrorInvalidValue;
+  }
+}
+
 template <int ST>
 hipError_t launch0(SweepArgs &A, int rs, int by, int scheme, int nvar, bool grav, hipStream_t s) {
   switch (rs) {
@@ -988,6 +1048,7 @@ hipError_t launch0(SweepArgs &A, int rs, int by, int scheme, int nvar, bool grav
 
 #if defined(SWEEP_ST)
 template hipError_t launch0<SWEEP_ST>(SweepArgs &, int, int, int, int, bool, hipStream_t);
+template hipError_t launch0_nener<SWEEP_ST>(SweepArgs &, int, int, int, hipStream_t);
 #if SWEEP_ST == 3
 template hipError_t launch0<4>(SweepArgs &, int, int, int, int, bool, hipStream_t);
 template hipError_t launch0<5>(SweepArgs &, int, int, int, int, bool, hipStream_t);
@@ -998,6 +1059,9 @@ template hipError_t launch0<6>(SweepArgs &, int, int, int, int, bool, hipStream_
 SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(4) SWEEP_EXTERN_ST(5) SWEEP_EXTERN_ST(6)
 SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
 #undef SWEEP_EXTERN_ST
+#define SWEEP_EXTERN_NENER(K) extern template hipError_t launch0_nener<K>(SweepArgs &, int, int, int, hipStream_t);
+SWEEP_EXTERN_NENER(0) SWEEP_EXTERN_NENER(1) SWEEP_EXTERN_NENER(2) SWEEP_EXTERN_NENER(3) SWEEP_EXTERN_NENER(7) SWEEP_EXTERN_NENER(8)
+#undef SWEEP_EXTERN_NENER
 #endif
 
 #ifndef SWEEP_ST
@@ -1022,6 +1086,22 @@ hipError_t launch_godunov_sweep(SweepArgs &A, int slope_type, int riemann, int b
     case 6: return launch0<6>(A, riemann, by, scheme, nvar, grav, s);
     case 7: return launch0<7>(A, riemann, by, scheme, nvar, grav, s);
     case 8: return launch0<8>(A, riemann, by, scheme, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_godunov_sweep_nener(SweepArgs &A, int slope_type, int riemann, int nvar, int nener, hipStream_t s) {
+  if ((unsigned long)A.pitch_z * 8ul >= (1ul << 31) || (unsigned long)A.pitch_var * 8ul >= (1ul << 32))
+    return hipErrorInvalidValue;
+  switch (slope_type) {
+    case 1: return launch0_nener<1>(A, riemann, nvar, nener, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case 0: return launch0_nener<0>(A, riemann, nvar, nener, s);
+    case 2: return launch0_nener<2>(A, riemann, nvar, nener, s);
+    case 3: return launch0_nener<3>(A, riemann, nvar, nener, s);
+    case 7: return launch0_nener<7>(A, riemann, nvar, nener, s);
+    case 8: return launch0_nener<8>(A, riemann, nvar, nener, s);
 #endif
   }
   return hipErrorInvalidValue;

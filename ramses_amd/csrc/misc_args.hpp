@@ -24,8 +24,19 @@ struct BoxCopyArgs {
   long d_off, d_py, d_pz, d_pv;
 };
 
+// the pdV term of the non-thermal energies on a brick (add_pdv_source_terms): unew(5+n) -= (gamma_rad-1) uold(5+n) div(u) dt
+struct PdvArgs {
+  const double *uold;
+  double *unew;
+  int nx, ny, nz, ng;
+  long pitch_y, pitch_z, pitch_var;
+  double dx, dt, smallr;
+  double gm1_rad[2];    // gamma_rad-1
+};
+
 hipError_t launch_courant_init(double *out, double dt_init, hipStream_t s);
-hipError_t launch_courant(const CourantArgs &A, bool grav, hipStream_t s);
+hipError_t launch_courant(const CourantArgs &A, bool grav, int nener, hipStream_t s);
+hipError_t launch_pdv(const PdvArgs &A, int nener, hipStream_t s);
 hipError_t launch_box_copy(const BoxCopyArgs &A, hipStream_t s);
 
 // all 26 neighbour regions of a ghost-layer brick in ONE launch: region r is the box

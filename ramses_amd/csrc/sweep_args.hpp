@@ -77,12 +77,16 @@ struct SurfArgs {
 };
 
 namespace strictmode {
+// NENER = nener (1, 2) non-thermal energies, the plain brick, muscl, no gravity
+hipError_t launch_godunov_sweep_nener(SweepArgs &A, int slope_type, int riemann, int nvar, int nener, hipStream_t s);
 hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, int nvar, int scheme, bool grav, hipStream_t s);
 hipError_t launch_godunov_sweep(SweepArgs &A, int slope_type, int riemann, int by, int scheme, int nvar,
                                 bool grav, hipStream_t s);
 int tile_sweep_rows(int riemann, int nvar, int slope_type, int scheme);
 }
 namespace fastmode {
+// NENER = nener (1, 2) non-thermal energies, the plain brick, muscl, no gravity
+hipError_t launch_godunov_sweep_nener(SweepArgs &A, int slope_type, int riemann, int nvar, int nener, hipStream_t s);
 hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, int nvar, int scheme, bool grav, hipStream_t s);
 hipError_t launch_godunov_sweep(SweepArgs &A, int slope_type, int riemann, int by, int scheme, int nvar,
                                 bool grav, hipStream_t s);

@@ -64,6 +64,7 @@ class HydroLevel:
             self.f = torch.zeros((3,) + shape[1:], dtype=torch.float64, device=self.device)
         self._red = torch.zeros(4, dtype=torch.float64, device=self.device)
         self.dtnew = 0.0
+        self._dt_swept = None      # dt of the last godunov_fine: set_uold's pdV term of the non-thermal energies
         self.bound_type = dict(bound_type or {})
         self.bound_state = dict(bound_state or {})
         self.no_inflow = bool(no_inflow)
@@ -114,7 +115,8 @@ class HydroLevel:
                                                        int(self.bound_type[face]), buf, int(self.no_inflow), _stream()))
 
     def courant_fine(self):
-        """CFL time step of the level -> (dt, mass, etot, eint); also sets dtnew."""
+        """CFL time step of the level -> (dt, mass, etot, eint); also sets dtnew.
+        With params.nener > 0, eint is less the non-thermal energies (courant_fine.f90:113-118)."""
         check(lib().ramses_amd_courant_init(C.byref(self.params), self.dx, _ptr(self._red), _stream()))
         check(lib().ramses_amd_courant_brick(C.byref(self.params), C.byref(self.brick), _ptr(self.uold),
                                              _ptr(self.f), self.dx, _ptr(self._red), _stream()))
@@ -125,6 +127,7 @@ class HydroLevel:
     def godunov_fine(self, dt=None):
         """set_unew + godunov_fine fused: unew = uold + flux differences."""
         dt = self.dtnew if dt is None else dt
+        self._dt_swept = float(dt)
         check(lib().ramses_amd_godunov_brick(C.byref(self.params), C.byref(self.brick), _ptr(self.uold),
                                              _ptr(self.f), _ptr(self.unew), self.dx, float(dt), _stream()))
 
@@ -132,17 +135,27 @@ class HydroLevel:
         """The part of godunov_fine that produces the cells the neighbour ranks
         receive (tiles/planes touching a brick face); see godunov_fine_interior."""
         dt = self.dtnew if dt is None else dt
+        self._dt_swept = float(dt)
         check(lib().ramses_amd_godunov_brick_shell(C.byref(self.params), C.byref(self.brick), _ptr(self.uold),
                                                    _ptr(self.f), _ptr(self.unew), self.dx, float(dt), _stream()))
 
     def godunov_fine_interior(self, dt=None):
         """The rest of godunov_fine: shell + interior == godunov_fine bit for bit."""
         dt = self.dtnew if dt is None else dt
+        self._dt_swept = float(dt)
         check(lib().ramses_amd_godunov_brick_interior(C.byref(self.params), C.byref(self.brick), _ptr(self.uold),
                                                       _ptr(self.f), _ptr(self.unew), self.dx, float(dt), _stream()))
 
     def set_uold(self):
-        """uold = unew (hydro/godunov_fine.f90:193-197): a buffer swap on the device."""
+        """uold = unew (hydro/godunov_fine.f90:193-197): a buffer swap on the device.  With params.nener > 0
+        the pdV term of the non-thermal energies comes first (add_pdv_source_terms, :166), with the dt of
+        the last godunov_fine."""
+        if self.params.nener > 0:
+            if self._dt_swept is None:
+                raise _capi.RamsesAmdError("set_uold with NENER > 0 needs a godunov_fine first (the pdV term takes its dt)")
+            check(lib().ramses_amd_pdv_brick(C.byref(self.params), C.byref(self.brick), _ptr(self.uold), _ptr(self.unew),
+                                             self.dx, self._dt_swept, _stream()))
+            self._dt_swept = None
         self.uold, self.unew = self.unew, self.uold
 
     def step(self, dt=None):

@@ -242,7 +242,16 @@ class BrickDecomposition:
         The shell launches produce every cell within 2 of a brick face, i.e. all the
         data the face slabs carry; the interior launch writes only cells the exchange
         never touches, and both read the old state, so the result equals
-        godunov_fine -> set_uold -> make_virtual_fine_dp bit for bit."""
+        godunov_fine -> set_uold -> make_virtual_fine_dp bit for bit.
+
+        With non-thermal energies (params.nener > 0) set_uold adds the pdV term to the new
+        state after the sweep, so its ghosts cannot leave before set_uold: that level takes
+        the sequential order."""
+        if getattr(getattr(lev, "params", None), "nener", 0) > 0:     # (the CPU protocol tests drive levels without params)
+            lev.godunov_fine(dt)
+            lev.set_uold()
+            self.make_virtual_fine_dp(lev)
+            return
         if lev.uold.device.type != "cuda":
             # the schedule without streams (the CPU protocol tests, tests/test_halo_gloo.py): the same order of operations
             lev.godunov_fine_shell(dt)

@@ -60,6 +60,7 @@ end subroutine set_unew
 
 subroutine set_uold(ilevel)
   use amr_commons
+  use hydro_parameters, only: nener
   use ramses_amd_iface
   implicit none
   integer::ilevel
@@ -71,6 +72,10 @@ subroutine set_uold(ilevel)
         ! add_gravity_source_terms (:160-162,237-289) on the new state, then the swap
         call ramses_amd_fill_hydro_params(p)
         rc=ramses_amd_resident_set_uold_grav_f90(p,ilevel,dtnew(ilevel))
+     else if(nener>0)then
+        ! add_pdv_source_terms (:166,294-481) of the non-thermal energies on the new state, then the swap
+        call ramses_amd_fill_hydro_params(p)
+        rc=ramses_amd_resident_set_uold_pdv_f90(p,ilevel,0.5d0**ilevel*(boxlen/dble(icoarse_max-icoarse_min+1)),dtnew(ilevel))
      else
         rc=ramses_amd_resident_set_uold_f90(ilevel)
      end if
@@ -78,7 +83,12 @@ subroutine set_uold(ilevel)
      return
   end if
   if(ramses_amd_mpi_resident())then
-     rc=ramses_amd_mpires_set_uold()
+     if(nener>0)then
+        call ramses_amd_fill_hydro_params(p)
+        rc=ramses_amd_mpires_set_uold_pdv(p,0.5d0**ilevel*(boxlen/dble(icoarse_max-icoarse_min+1)),dtnew(ilevel))
+     else
+        rc=ramses_amd_mpires_set_uold()
+     end if
      if(rc/=0)call ramses_amd_fatal('set_uold')
      return
   end if
@@ -184,6 +194,12 @@ subroutine godunov_fine(ilevel)
   if(difmag>0.0d0)amr_level=.true.
   ! so are the divu/enew updates of pressure_fix
   if(pressure_fix)amr_level=.true.
+  ! non-thermal energies run on the uniform brick paths only (ramses_amd_check_build): no silent fallback
+  if(amr_level.and.nener>0)then
+     if(myid==1)write(*,*)'ramses_amd: NENER=',nener,' needs a fully refined periodic level (one rank, or MPI residency), ', &
+          & 'without physical boundaries, difmag or pressure_fix; the tree-walking sweep of AMR levels has no NENER'
+     call ramses_amd_fatal('godunov_fine (NENER>0 on an AMR level / the tree walker)')
+  end if
 
   if(amr_level)then
      ! f, divu, enew exist only with poisson resp. pressure_fix: uold stands in (never read)

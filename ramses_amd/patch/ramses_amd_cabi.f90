@@ -18,7 +18,8 @@ module ramses_amd_cabi
      real(c_double)     :: slope_theta
      integer(c_int32_t) :: scheme, niter_riemann
      real(c_double)     :: difmag, courant_factor
-     integer(c_int32_t) :: fast_math, reserved
+     integer(c_int32_t) :: fast_math, nener
+     real(c_double)     :: gamma_rad(2)     ! RAMSES_AMD_MAX_NENER
   end type ramses_amd_hydro_params
 
   ! struct ramses_amd_brick, only needed for the ABI size check
@@ -550,6 +551,13 @@ module ramses_amd_cabi
        integer(c_int), value :: ilevel
        integer(c_int) :: rc
      end function ramses_amd_resident_set_uold_f90
+     function ramses_amd_resident_set_uold_pdv_f90(p, ilevel, dx, dt) bind(C, name='ramses_amd_resident_set_uold_pdv_f90') result(rc)
+       import :: c_int, c_double, ramses_amd_hydro_params
+       type(ramses_amd_hydro_params) :: p
+       integer(c_int), value :: ilevel
+       real(c_double), value :: dx, dt
+       integer(c_int) :: rc
+     end function ramses_amd_resident_set_uold_pdv_f90
      function ramses_amd_resident_sync_host_f90(uold) bind(C, name='ramses_amd_resident_sync_host_f90') result(rc)
        import :: c_int, c_double
        real(c_double) :: uold(*)
@@ -684,6 +692,12 @@ module ramses_amd_cabi
        import :: c_int
        integer(c_int) :: rc
      end function ramses_amd_mpires_set_uold
+     function ramses_amd_mpires_set_uold_pdv(p, dx, dt) bind(C, name='ramses_amd_mpires_set_uold_pdv') result(rc)
+       import :: c_int, c_double, ramses_amd_hydro_params
+       type(ramses_amd_hydro_params) :: p
+       real(c_double), value :: dx, dt
+       integer(c_int) :: rc
+     end function ramses_amd_mpires_set_uold_pdv
      function ramses_amd_mpires_halo_forward() bind(C, name='ramses_amd_mpires_halo_forward') result(rc)
        import :: c_int
        integer(c_int) :: rc

@@ -121,19 +121,26 @@ contains
   end function ramses_amd_enabled
 
   !---------------------------------------------------------------------------
-  ! What the build must look like for the device hydro path: NENER=0.  With non-thermal
-  ! energies the reference folds them into the pressure in ctoprim, cmpdt, the Riemann
-  ! solvers and set_uold (hydro/godunov_fine.f90:83,166,214; hydro/umuscl.f90;
-  ! hydro/godunov_utils.f90:40-79); the device kernels would treat variables 6.. as
-  ! passive scalars.  Stop instead (RAMSES_AMD=0 runs the reference path).
+  ! What the build must look like for the device hydro path with non-thermal energies: NENER=1 with NVAR=6 or 7 (one
+  ! passive scalar), NENER=2 with NVAR=7, NDIM=3, no self-gravity.  They run on uniform levels (the staged, the resident
+  ! and the MPI-resident brick; scheme='muscl', riemann= llf, hll, hllc -- the library refuses anything else by name);
+  ! AMR levels, tiles and the tree walker stop in godunov_fine, and ramses_amd_amr_config never picks AMR residency.
+  ! Outside this set stop here (RAMSES_AMD=0 runs the reference path).
   !---------------------------------------------------------------------------
   subroutine ramses_amd_check_build()
-    use amr_commons, only: hydro
-    use hydro_parameters, only: nener
+    use amr_commons, only: hydro, poisson
+    use amr_parameters, only: ndim
+    use hydro_parameters, only: nener, nvar
     if (hydro .and. nener > 0) then
-       write(*,*) 'ramses_amd: this binary was built with NENER=', nener, &
-            & ' (non-thermal energies); the device hydro path implements NENER=0 only'
-       call ramses_amd_fatal('build check (NENER>0)')
+       if (nener > 2 .or. ndim /= 3 .or. nvar < ndim + 2 + nener .or. nvar > 7) then
+          write(*,*) 'ramses_amd: this binary was built with NENER=', nener, ' NVAR=', nvar, ' NDIM=', ndim, &
+               & '; the device hydro path implements NENER=1 (NVAR=6,7) and NENER=2 (NVAR=7) with NDIM=3'
+          call ramses_amd_fatal('build check (NENER)')
+       end if
+       if (poisson) then
+          write(*,*) 'ramses_amd: NENER=', nener, ' with self-gravity (poisson=.true.) is not on the device'
+          call ramses_amd_fatal('build check (NENER with poisson)')
+       end if
     end if
   end subroutine ramses_amd_check_build
 
@@ -604,6 +611,8 @@ contains
     if (.not. ramses_amd_amr_checked) then
        ramses_amd_amr_checked = .true.
        ramses_amd_amr_ok = ramses_amd_enabled()
+       ! non-thermal energies run on uniform levels only (ramses_amd_check_build)
+       if (nener > 0) ramses_amd_amr_ok = .false.
        call get_environment_variable('RAMSES_AMD_RESIDENT_AMR', val, status=stat)
        if (stat == 0) then
           if (trim(val) == '0') ramses_amd_amr_ok = .false.
@@ -1360,7 +1369,11 @@ contains
           end if
        end if
     end if
-    p%reserved = 0
+    p%nener = nener
+    p%gamma_rad = 0.0d0
+#if NENER>0
+    p%gamma_rad(1:min(nener,2)) = gamma_rad(1:min(nener,2))
+#endif
   end subroutine ramses_amd_fill_hydro_params
 
 #ifndef WITHOUTMPI
