@@ -47,6 +47,13 @@ enum { RAMSES_AMD_RIEMANN_LLF = 0, RAMSES_AMD_RIEMANN_HLLC = 1,
 enum { RAMSES_AMD_SCHEME_MUSCL = 0, RAMSES_AMD_SCHEME_PLMDE = 1 };
 
 #define RAMSES_AMD_MAX_NENER 2
+/* NVAR of the brick sweep (ramses_amd_godunov_brick and its _shell / _interior
+ * variants, the staged, resident and MPI-resident entry points): 5+nener <=
+ * nvar <= RAMSES_AMD_MAX_NVAR.  Beyond NVAR = 7 the passive scalars are swept
+ * in passes of their own after the hydro variables (muscl; all five solvers
+ * with nener = 0, llf / hll / hllc with nener > 0).  AMR levels, tiles and the
+ * tree walker implement NVAR <= 7 and refuse more by name. */
+#define RAMSES_AMD_MAX_NVAR 16
 
 /* Solver knobs = the &HYDRO_PARAMS namelist group
  * (hydro/read_hydro_params.f90:43-54, defaults hydro/hydro_parameters.f90:75-89).
@@ -54,7 +61,7 @@ enum { RAMSES_AMD_SCHEME_MUSCL = 0, RAMSES_AMD_SCHEME_PLMDE = 1 };
  * unsplit() reads implicitly. */
 typedef struct ramses_amd_hydro_params {
   int32_t ndim;           /* NDIM of the RAMSES build (3 supported on device) */
-  int32_t nvar;           /* NVAR = ndim+2+nener (+ passive scalars)          */
+  int32_t nvar;           /* NVAR = ndim+2+nener (+ passive scalars), <= RAMSES_AMD_MAX_NVAR */
   double gamma;
   double smallr;
   double smallc;
@@ -115,6 +122,8 @@ int ramses_amd_device_info(char *name, size_t name_len, int *n_cu, size_t *hbm_b
  * d_grav: device pointer to the gravitational acceleration f(:,1:ndim) in the
  *         same brick layout with ndim variables, or NULL when poisson=.false.
  * dx = cell size of the level, dt = dtnew(ilevel).
+ * NVAR: 5+nener .. RAMSES_AMD_MAX_NVAR (NVAR > 7: a hydro pass, then the
+ * passive scalars in groups; the result is the same bits as one sweep).
  * stream: hipStream_t (as void*), NULL = default stream.  Asynchronous.
  * ------------------------------------------------------------------------- */
 int ramses_amd_godunov_brick(const ramses_amd_hydro_params *p,
@@ -127,7 +136,9 @@ int ramses_amd_godunov_brick(const ramses_amd_hydro_params *p,
  * amr/amr_step.f90:388-510): _shell updates the tiles and planes that hold the
  * cells within 2 of a brick face (what the neighbour ranks receive as ghost
  * octs), _interior everything else.  shell + interior == ramses_amd_godunov_brick
- * bit for bit; the halo exchange of the new state can start after _shell. */
+ * bit for bit; the halo exchange of the new state can start after _shell.
+ * Each updates its own cells from uold alone and may run without the other;
+ * with NVAR > 7 the scalar passes of each cover exactly its hydro cells. */
 int ramses_amd_godunov_brick_shell(const ramses_amd_hydro_params *p,
                                    const ramses_amd_brick *b, const double *d_uold,
                                    const double *d_grav, double *d_unew, double dx,

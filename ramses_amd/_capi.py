@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("RAMSES_AMD_LIB") or os.path.join(HERE, "lib", "libram
 
 # gamma_rad's default, hydro/hydro_parameters.f90:79 (the reference writes 1.33333333334d0, not 4/3)
 GAMMA_RAD = 1.33333333334
+# RAMSES_AMD_MAX_NVAR: the brick sweep takes 5+nener <= nvar <= MAX_NVAR (NVAR > 7 on the uniform brick paths only)
+MAX_NVAR = 16
 RIEMANN = {"llf": 0, "hllc": 1, "hll": 2, "acoustic": 3, "exact": 4}
 SCHEME = {"muscl": 0, "plmde": 1}
 
@@ -292,7 +294,8 @@ def make_params(ndim=3, nvar=None, gamma=1.4, smallr=1e-10, smallc=1e-10, slope_
                 slope_theta=1.5, riemann="llf", scheme="muscl", niter_riemann=10,
                 difmag=0.0, courant_factor=0.5, fast_math=False, nener=0, gamma_rad=(GAMMA_RAD, GAMMA_RAD)):
     """Defaults are the reference's (hydro/hydro_parameters.f90:75-89).  nener: NENER of the build
-    (non-thermal energies in variables ndim+3 .. ndim+2+nener); nvar defaults to ndim+2+nener."""
+    (non-thermal energies in variables ndim+3 .. ndim+2+nener); nvar defaults to ndim+2+nener, passive scalars
+    beyond it up to MAX_NVAR (the library checks the range and refuses what an entry point does not implement)."""
     gr = (C.c_double * 2)(*(list(gamma_rad) + [GAMMA_RAD, GAMMA_RAD])[:2])
     return HydroParams(ndim, nvar if nvar else ndim + 2 + nener, gamma, smallr, smallc, slope_type,
                        RIEMANN[riemann] if isinstance(riemann, str) else riemann, slope_theta,

@@ -141,8 +141,7 @@ static int godunov_brick_region(const ramses_amd_hydro_params *p, const ramses_a
   if (d_uold == d_unew) return fail(RAMSES_AMD_EINVAL, "uold and unew must be distinct buffers");
   if (int rc = check_ndim(p, b)) return rc;
   if (int rc = check_nener(p, d_grav != nullptr)) return rc;
-  if (p->nvar < 5 || p->nvar > 7) return fail(RAMSES_AMD_EUNSUPPORTED, "device sweep implements NVAR=5..7 (up to two passive scalars; got %d)", p->nvar);
-  if (p->nvar != 5 && p->scheme != RAMSES_AMD_SCHEME_MUSCL) return fail(RAMSES_AMD_EUNSUPPORTED, "passive scalars with scheme='plmde' are not on the device yet");
+  if (int rc = check_nvar(p, "ramses_amd_godunov_brick")) return rc;
   if (p->scheme != RAMSES_AMD_SCHEME_MUSCL && p->scheme != RAMSES_AMD_SCHEME_PLMDE) return fail(RAMSES_AMD_EINVAL, "unknown scheme %d", p->scheme);
   if (p->difmag > 0.0) return fail(RAMSES_AMD_EUNSUPPORTED, "difmag>0 is not implemented on the device yet");
   // slope types: 0,1,2,3,7,8 in every build of the reference; 4,5,6 (superbee, ultrabee, central) exist in its NDIM=1
@@ -171,14 +170,22 @@ static int godunov_brick_region(const ramses_amd_hydro_params *p, const ramses_a
   for (int region = region_first; region <= region_last; region++) {
     A.region = region;
     hipError_t e;
+    // NVAR > 7: the hydro pass sweeps the 5+NENER hydro variables, then the scalar passes the passive scalars (csrc/hydro_sweep.hip
+    // godunov_scalar_kernel); NVAR <= 7: one sweep of everything
+    const int nv_hydro = p->nvar > 7 ? 5 + p->nener : p->nvar;
     if (p->nener > 0)
-      e = p->fast_math ? fastmode::launch_godunov_sweep_nener(A, slope_type, p->riemann, p->nvar, p->nener, s)
-                       : strictmode::launch_godunov_sweep_nener(A, slope_type, p->riemann, p->nvar, p->nener, s);
+      e = p->fast_math ? fastmode::launch_godunov_sweep_nener(A, slope_type, p->riemann, nv_hydro, p->nener, s)
+                       : strictmode::launch_godunov_sweep_nener(A, slope_type, p->riemann, nv_hydro, p->nener, s);
     else
       e = p->fast_math
-              ? fastmode::launch_godunov_sweep(A, slope_type, p->riemann, g_tile_rows, p->scheme, p->nvar, d_grav != nullptr, s)
-              : strictmode::launch_godunov_sweep(A, slope_type, p->riemann, g_tile_rows, p->scheme, p->nvar, d_grav != nullptr, s);
+              ? fastmode::launch_godunov_sweep(A, slope_type, p->riemann, g_tile_rows, p->scheme, nv_hydro, d_grav != nullptr, s)
+              : strictmode::launch_godunov_sweep(A, slope_type, p->riemann, g_tile_rows, p->scheme, nv_hydro, d_grav != nullptr, s);
     if (e != hipSuccess) return hipfail(e, "godunov sweep launch");
+    if (p->nvar > 7) {
+      e = p->fast_math ? fastmode::launch_godunov_sweep_scalars(A, slope_type, p->riemann, g_tile_rows, p->nvar, p->nener, d_grav != nullptr, s)
+                       : strictmode::launch_godunov_sweep_scalars(A, slope_type, p->riemann, g_tile_rows, p->nvar, p->nener, d_grav != nullptr, s);
+      if (e != hipSuccess) return hipfail(e, "godunov scalar pass launch");
+    }
   }
   return 0;
 }

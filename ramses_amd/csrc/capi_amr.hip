@@ -1175,6 +1175,7 @@ int ramses_amd_amrres_set_unew(int ngrid, const int *igrid) {
 
 int ramses_amd_amrres_set_uold(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_set_uold")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_set_uold")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1187,6 +1188,7 @@ int ramses_amd_amrres_set_uold(const ramses_amd_hydro_params *p, int ngrid, cons
 
 int ramses_amd_amrres_upload_fine(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, int interpol_var) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_upload_fine")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_upload_fine")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   if (interpol_var < 0 || interpol_var > 2) return failf(RAMSES_AMD_EINVAL, "interpol_var must be 0, 1 or 2");
   LvlArgs A;
@@ -1206,6 +1208,7 @@ int ramses_amd_amrres_upload_fine(const ramses_amd_hydro_params *p, int ngrid, c
 // out4 = {dt_loc (min with dt_in), mass_loc, sum(E*vol), eint_loc} over the leaf cells of the level
 int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dx, double dt_in, double *out4) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_courant")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_courant")) return rc_;
   if (!p || !out4) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1232,6 +1235,7 @@ int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const
 int ramses_amd_amrres_hydro_flag(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double err_grad_d, double err_grad_p,
                                  double err_grad_u, double floor_d, double floor_p, double floor_u, int *cells, int *ncells) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_hydro_flag")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_hydro_flag")) return rc_;
   if (!p || !cells || !ncells) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   *ncells = 0;
   LvlArgs A;
@@ -1551,6 +1555,7 @@ extern "C" int ramses_amd_amrres_tiled_levels(void) { return g_ar.valid && g_ar.
 int ramses_amd_amrres_godunov(const ramses_amd_hydro_params *p, int ilevel, int ngrid, const int *igrid, double dx, double dt,
                               int nvector, int interpol_var, int interpol_type) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_godunov")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_godunov")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1718,6 +1723,7 @@ int ramses_amd_amrres_xg(const double *xg) {
 int ramses_amd_amrres_rho_fine(const ramses_amd_hydro_params *p, int ilevel, int nlevelmax, int levelmin, int nvector,
                                const int *first, const int *igrid_all, double boxlen_over_nx, double *rho, double *multipole4) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_rho_fine")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_rho_fine")) return rc_;
   AmrRes &R = g_ar;
   if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
   if (!p || !first || !igrid_all || !rho || !multipole4) return failf(RAMSES_AMD_EINVAL, "NULL argument");
@@ -1779,6 +1785,7 @@ int ramses_amd_amrres_rho_fine(const ramses_amd_hydro_params *p, int ilevel, int
 int ramses_amd_amrres_rho_mpi_multipole(const ramses_amd_hydro_params *p, int ilevel, int n_own, int n_all, const int *igrid_all,
                                         double boxlen_over_nx) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_rho_mpi_multipole")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_rho_mpi_multipole")) return rc_;
   AmrRes &R = g_ar;
   if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
   if (!p || (n_all > 0 && !igrid_all)) return failf(RAMSES_AMD_EINVAL, "NULL argument");
@@ -1940,6 +1947,7 @@ int ramses_amd_amrres_sync_density(int ngrid, const int *igrid, double *uold) {
 
 int ramses_amd_amrres_synchro(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dteff) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_synchro")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_synchro")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1954,6 +1962,7 @@ int ramses_amd_amrres_synchro(const ramses_amd_hydro_params *p, int ngrid, const
 // set_uold with poisson: add_gravity_source_terms on unew, then the scalar fix and uold = unew
 int ramses_amd_amrres_set_uold_grav(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_set_uold_grav")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_set_uold_grav")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1980,6 +1989,7 @@ int ramses_amd_amrres_enable_pfix(void) {
 // set_unew with pressure_fix: unew = uold, divu = 0, enew = internal energy
 int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_set_unew_pfix")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_set_unew_pfix")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1996,6 +2006,7 @@ int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid,
 int ramses_amd_amrres_set_uold_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt, double dx_loc, double beta_fix,
                                     double hexp) {
   if (int rc_ = refuse_nener(p, "ramses_amd_amrres_set_uold_pfix")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_set_uold_pfix")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;

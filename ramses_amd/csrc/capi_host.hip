@@ -68,7 +68,8 @@ int ramses_amd_godunov_fine_host(const ramses_amd_hydro_params *p, int ilevel, i
                                  int64_t ncoarse, int nx_loc, const double *uold, double *unew,
                                  const double *f, double dx, double dt) {
   if (!p || !igrid || !xg || !uold || !unew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (p->ndim != 3 || p->nvar < 5 || p->nvar > 7) return fail(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3, NVAR=5..7");
+  if (p->ndim != 3) return fail(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3");
+  if (int rc = check_nvar(p, "ramses_amd_godunov_fine_host")) return rc;
   if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "device path needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
   if (ilevel < 1 || ilevel > 11) return fail(RAMSES_AMD_EINVAL, "level out of range");
   const int n = 1 << ilevel;
@@ -177,6 +178,7 @@ int ramses_amd_godunov_fine_amr_device(const ramses_amd_hydro_params *p, int ile
                                        int nvector, int interpol_var, int interpol_type,
                                        void *d_work, int *d_err, void *stream) {
   if (int rc_ = refuse_nener(p, "ramses_amd_godunov_fine_amr_device")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_godunov_fine_amr_device")) return rc_;
   if ((d_divu == nullptr) != (d_enew == nullptr)) return fail(RAMSES_AMD_EINVAL, "pressure_fix needs both divu and enew");
   if (!p || !d_igrid || !d_son || !d_nbor || !d_father || !d_uold || !d_unew || !d_work || !d_err) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = amr_check(p, ilevel, nvector, interpol_var, interpol_type)) return rc;
@@ -211,6 +213,7 @@ int ramses_amd_godunov_fine_amr_host(const ramses_amd_hydro_params *p, int ileve
                                      double *divu, double *enew, double dx, double dt,
                                      int nvector, int interpol_var, int interpol_type) {
   if (int rc_ = refuse_nener(p, "ramses_amd_godunov_fine_amr_host")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_godunov_fine_amr_host")) return rc_;
   if (!p || !igrid || !son || !nbor || !father || !uold || !unew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if ((divu == nullptr) != (enew == nullptr)) return fail(RAMSES_AMD_EINVAL, "pressure_fix needs both divu and enew");
   if (int rc = amr_check(p, ilevel, nvector, interpol_var, interpol_type)) return rc;
@@ -276,6 +279,7 @@ int ramses_amd_godunov_fine_amr_f90(const ramses_amd_hydro_params *p, int ilevel
                                     double *divu_or_dummy, double *enew_or_dummy, int has_pfix,
                                     double dx, double dt, int nvector, int interpol_var, int interpol_type) {
   if (int rc_ = refuse_nener(p, "ramses_amd_godunov_fine_amr_f90")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_godunov_fine_amr_f90")) return rc_;
   return ramses_amd_godunov_fine_amr_host(p, ilevel, ngrid, igrid, son, nbor, father, ngridmax, ncoarse, uold, unew,
                                           has_f ? f_or_dummy : nullptr, has_pfix ? divu_or_dummy : nullptr,
                                           has_pfix ? enew_or_dummy : nullptr, dx, dt, nvector, interpol_var, interpol_type);
@@ -319,6 +323,7 @@ int ramses_amd_godunov_fine_lowdim_f90(const ramses_amd_hydro_params *p, int ile
                                        const int *igrid_bound, const double *xg, int64_t ngridmax, int64_t ncoarse, const int *skip,
                                        const int *nloc, const double *uold, double *unew, double dx, double dt) {
   if (int rc_ = refuse_nener(p, "ramses_amd_godunov_fine_lowdim_f90")) return rc_;
+  if (int rc_ = refuse_scalars(p, "ramses_amd_godunov_fine_lowdim_f90")) return rc_;
   if (!p || !igrid || !xg || !skip || !nloc || !uold || !unew || (nbound > 0 && !igrid_bound)) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   const int ndim = p->ndim;
   if (ndim != 1 && ndim != 2) return fail(RAMSES_AMD_EINVAL, "ramses_amd_godunov_fine_lowdim_f90 is the entry of NDIM=1 and NDIM=2 builds (got NDIM=%d)", ndim);
@@ -599,7 +604,8 @@ static int resident_ensure(const ramses_amd_hydro_params *p, int ilevel, int ngr
                            const double *xg, int64_t ngridmax, int64_t ncoarse, int nx_loc,
                            const double *uold) {
   if (!p || !igrid || !xg || !uold) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (p->ndim != 3 || p->nvar < 5 || p->nvar > 7) return fail(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3, NVAR=5..7");
+  if (p->ndim != 3) return fail(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3");
+  if (int rc = check_nvar(p, "ramses_amd_resident (godunov / courant)")) return rc;
   if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "device path needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
   if (ilevel < 1 || ilevel > 11) return fail(RAMSES_AMD_EINVAL, "level out of range");
   const int n = 1 << ilevel;

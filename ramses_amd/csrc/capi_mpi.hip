@@ -403,7 +403,9 @@ int ramses_amd_mpires_setup(const ramses_amd_hydro_params *p, int ilevel, int ng
                             int ncpu, int myid, const int *em_ngrid, const int *em_igrid, const int *rc_ngrid,
                             const int *rc_igrid) {
   if (!p || !igrid || !xg || !uold || !unew || !em_ngrid || !rc_ngrid) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (p->ndim != 3 || p->nvar < 5 || p->nvar > 7) return failf(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3, NVAR=5..7");
+  if (p->ndim != 3) return failf(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3");
+  if (p->nvar < 5 || p->nvar > RAMSES_AMD_MAX_NVAR)
+    return failf(RAMSES_AMD_EUNSUPPORTED, "ramses_amd_mpires_setup: NVAR=%d: the device path implements 5+NENER <= NVAR <= %d", p->nvar, RAMSES_AMD_MAX_NVAR);
   if (p->nener < 0 || p->nener > RAMSES_AMD_MAX_NENER || p->nvar < 5 + p->nener)
     return failf(RAMSES_AMD_EUNSUPPORTED, "NENER=%d with NVAR=%d: the device path implements NENER=0, 1, 2 with NVAR >= 5+NENER", p->nener, p->nvar);
   if (nx_loc != 1) return failf(RAMSES_AMD_EUNSUPPORTED, "device path needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);

@@ -88,6 +88,25 @@ static inline int check_nener(const ramses_amd_hydro_params *p, bool grav) {
   return 0;
 }
 
+// NVAR of a brick sweep (every brick entry point): 5+NENER <= NVAR <= RAMSES_AMD_MAX_NVAR; passive scalars with muscl only
+static_assert(RAMSES_AMD_MAX_NVAR == MAX_NVAR, "include/ramses_amd.h and csrc/sweep_args.hpp agree on NVAR");
+static inline int check_nvar(const ramses_amd_hydro_params *p, const char *who) {
+  if (p->nvar < 5 + (p->nener > 0 ? p->nener : 0) || p->nvar > RAMSES_AMD_MAX_NVAR)
+    return fail(RAMSES_AMD_EUNSUPPORTED, "%s: NVAR=%d with NENER=%d: the device sweep implements 5+NENER <= NVAR <= %d", who, p->nvar,
+                p->nener, RAMSES_AMD_MAX_NVAR);
+  if (p->nvar != 5 && p->scheme != RAMSES_AMD_SCHEME_MUSCL)
+    return fail(RAMSES_AMD_EUNSUPPORTED, "%s: passive scalars (NVAR=%d) with scheme='plmde' are not on the device", who, p->nvar);
+  return 0;
+}
+// NVAR > 7 (more than two passive scalars, or NENER with more than 7 variables) runs on the uniform brick paths only: every AMR,
+// tile and tree-walking entry point refuses it by name
+static inline int refuse_scalars(const ramses_amd_hydro_params *p, const char *who) {
+  if (p && p->nvar > 7)
+    return fail(RAMSES_AMD_EUNSUPPORTED, "%s: NVAR=%d: more than 7 variables are implemented on the uniform brick paths only (staged, "
+                "resident and MPI-resident bricks), not on AMR levels, tiles or the tree walker", who, p->nvar);
+  return 0;
+}
+
 // capi_host.hip: the staged entry points reuse the staging buffers of the resident level; refuses while that level holds
 // the only current copy of the hydro state
 int capi_resident_release(const char *who);

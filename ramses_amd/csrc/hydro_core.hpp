@@ -20,6 +20,8 @@ constexpr int RIEMANN_LLF = 0, RIEMANN_HLLC = 1, RIEMANN_HLL = 2,
 // start at 5+NE.  Every NE > 0 term below sits in an `if constexpr` (HLLC: a routine of its own), so the NE = 0
 // instantiations are the code they were.
 constexpr int MAX_NENER = 2;
+// NVAR of the brick sweep: 5+NE hydro variables and passive scalars (include/ramses_amd.h RAMSES_AMD_MAX_NVAR)
+constexpr int MAX_NVAR = 16;
 
 // Constants derived once on the host from &HYDRO_PARAMS.
 struct HydroConst {

@@ -654,6 +654,274 @@ __global__ __launch_bounds__(BX * 8) void godunov_sweep_nener_kernel(SweepArgs A
 }
 
 // ---------------------------------------------------------------------------
+// scalar pass: passive scalars beyond NVAR=7
+// ---------------------------------------------------------------------------
+// A passive scalar never feeds back into the hydro (hydro/umuscl.f90:680-700, the "passive scalars" blocks of
+// hydro/godunov_utils.f90), so with NVAR > 7 the brick is swept in passes: the kernels above at NV = 5+NE sweep the hydro
+// variables, then this kernel sweeps the scalars in groups of G.  It re-derives from uold what a scalar's flux needs -- the
+// primitives, slopes and traced states of the 5+NE hydro variables, and the solver's face quantities (LLF: rho, u_n and
+// cmax; HLL: SL, SR; HLLC, acoustic, exact: the mass flux and its upwind side) -- with the same functions on the same values
+// as the hydro pass, hence the same bits, and updates its group's rows of unew only.  The Riemann routines are called
+// whole: the hydro components of their flux are dead code the compiler removes.  set_uold's near-floor fix of the scalars
+// (hydro/godunov_fine.f90:176-190) is fused as in the kernels above, with the new density read back from unew, which the
+// hydro pass has just written on the same stream.
+// Group g covers the variables s0 .. s0+nlive-1 in slots 5+NE .. 5+NE+nlive-1; the slots past nlive (a group of fewer than
+// G scalars) load the group's last scalar and store nothing.
+// LDS: RING + 2 planes of NV = 5+NE+G doubles per column of a 64 x 8 tile, 16 KB x NV (RING 2) or 20 KB x NV (slope type 3,
+// RING 3), within 160 KB: NV = 10 or 8, the largest group that fits.  One 8-wave workgroup per CU, as the NV = 6, 7 kernels.
+// The exact solver's Newton loop needs ~40 registers more: with it a group is two slots smaller (at NV = 10 / 8 it spills).
+template <int ST, int RS, int NE>
+struct ScalarGroup {
+  static constexpr int RING = (ST == 3) ? 3 : 2;
+  static constexpr int NH = 5 + NE;
+  static constexpr int G = (ST == 3 ? 8 : 10) - (RS == RIEMANN_EXACT ? 2 : 0) - NH;
+  static constexpr int NV = NH + G;
+  static constexpr size_t m_off = RING * sizeof(Plane<8, NV>);
+  static constexpr size_t bytes = m_off + 2 * sizeof(Plane<8, NV>);
+  static_assert(G >= 1 && bytes <= 160 * 1024, "the scalar pass fits one workgroup's LDS");
+};
+
+template <int ST, int RS, bool GRAV, int NE, int ROLE>
+__device__ __forceinline__ void scalar_march(const SweepArgs &A, int s0, int nlive, unsigned char *smem_raw) {
+  typedef ScalarGroup<ST, RS, NE> SG;
+  constexpr int BY = 8, RING = SG::RING, NH = SG::NH, G = SG::G, NV = SG::NV;
+  const bool DXPOW2 = A.pow2 != 0;
+  Plane<BY, NV> *qring = reinterpret_cast<Plane<BY, NV> *>(smem_raw);
+  Plane<BY, NV> *mring = reinterpret_cast<Plane<BY, NV> *>(smem_raw + SG::m_off);
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  const HydroConst &P = A.P;
+
+  // tile decode: the plain brick's of sweep_march
+  const int hb = blockIdx.x;
+  int bi = 0;
+#pragma unroll
+  for (int i = 1; i < 6; i++)
+    if (i < A.nbox && hb >= A.box[i].first) bi = i;
+  const SweepBox &B = A.box[bi];
+  int lb = hb - B.first;
+  {
+    const int nxcd = 8;
+    const int cnt = (bi + 1 < A.nbox ? A.box[bi + 1].first : (int)gridDim.x) - B.first;
+    if (cnt % nxcd == 0) {
+      const int per = cnt / nxcd;
+      lb = (lb % nxcd) * per + lb / nxcd;
+    }
+  }
+  const int tix = B.tx0 + lb % B.ntx;
+  const int tiy = B.ty0 + (lb / B.ntx) % B.nty;
+  const int tiz = lb / (B.ntx * B.nty);
+  const int x0 = tix * (BX - 4), y0 = tiy * (BY - 4);
+  const int z0 = B.zlo + tiz * B.zchunk;
+  const int z1 = min(z0 + B.zchunk, B.zhi);
+  const int xu = x0 - 2 + tx, yu = y0 - 2 + ty;
+  int xi, yi;
+  if (A.ng == 0) {
+    xi = xu < 0 ? xu + A.nx : (xu >= A.nx ? xu - A.nx : xu);
+    xi = xi >= A.nx ? xi % A.nx : xi;
+    yi = yu < 0 ? yu + A.ny : (yu >= A.ny ? yu - A.ny : yu);
+    yi = yi >= A.ny ? yi % A.ny : yi;
+  } else {
+    xi = min(max(xu, -A.ng), A.nx + A.ng - 1) + A.ng;
+    yi = min(max(yu, -A.ng), A.ny + A.ng - 1) + A.ng;
+  }
+  const unsigned colb = (unsigned)(xi + yi * (int)A.pitch_y) * 8u;
+  const double *__restrict__ uold = A.uold;
+  double *__restrict__ unew = A.unew;
+  const double *__restrict__ grav = A.grav;
+
+  constexpr bool r_trace = ROLE == ROLE_LOW || ROLE == ROLE_HIGH || ROLE == ROLE_FULL;
+  constexpr bool r_fxz = ROLE == ROLE_FULL;
+  const bool r_upd = r_fxz && (tx >= 2) && (tx <= BX - 3) && (xu < A.nx) && (yu < A.ny);
+  const unsigned colb_upd = r_upd ? colb : BUF_OOB;
+  const double dtdx = A.dt / A.dx;
+  const double dtxhalf = A.dt * 0.5;
+
+  auto plane_off = [&](int p) -> unsigned {
+    int pz;
+    if (A.ng == 0) { pz = p < 0 ? p + A.nz : (p >= A.nz ? p - A.nz : p); }
+    else { pz = p + A.ng; }
+    return (unsigned)pz * (unsigned)(A.pitch_z * 8);
+  };
+  // slot n of the group -> variable of the brick (wave-uniform)
+  auto var_of = [&](int n) -> long { return n < NH ? n : s0 + min(n - NH, nlive - 1); };
+  auto load_u = [&](int p, double (&u)[NV]) {
+    const unsigned pb = plane_off(p);
+#pragma unroll
+    for (int n = 0; n < NV; n++) u[n] = plane_load(uold + var_of(n) * A.pitch_var, pb, colb);
+  };
+  auto load_g = [&](int p, double (&g)[3]) {
+    if (GRAV) {
+      const unsigned pb = plane_off(p);
+#pragma unroll
+      for (int d = 0; d < 3; d++) g[d] = plane_load(grav + (long)d * A.pitch_var, pb, colb);
+    } else {
+      g[0] = g[1] = g[2] = 0.0;
+    }
+  };
+
+  double qmz[NV];                   // qm along z of plane c-1
+  double fzlo[G];                   // z flux of the scalars through the -z face of plane c-1
+  double upre[NV], gpre[3];         // prefetch: plane c+1
+  double rold = 0.0, sold[G];       // uold density / scalars of plane c-1
+  double rnew = 0.0;                // uold density of plane c
+  double partx[G], fyown[G], dz[G], px[G], fy[G];
+  int sa = 0, sb = 1, sc = 2;
+  {
+    double u[NV], g[3], q[NV];
+    load_u(z0 - 2, u); load_g(z0 - 2, g);
+    ctoprim_cell<NV, GRAV, NE>(u, g, dtxhalf, P, q);
+#pragma unroll
+    for (int n = 0; n < NV; n++) qring[sa].v[n][ty][tx] = q[n];
+    load_u(z0 - 1, u); load_g(z0 - 1, g);
+    ctoprim_cell<NV, GRAV, NE>(u, g, dtxhalf, P, q);
+#pragma unroll
+    for (int n = 0; n < NV; n++) qring[sb].v[n][ty][tx] = q[n];
+    load_u(z0, upre); load_g(z0, gpre);
+#pragma unroll
+    for (int n = 0; n < NV; n++) qmz[n] = 1.0;
+#pragma unroll
+    for (int j = 0; j < G; j++) { fzlo[j] = 0.0; sold[j] = 0.0; partx[j] = 0.0; fyown[j] = 0.0; dz[j] = 0.0; px[j] = 0.0; }
+  }
+  __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
+  __syncthreads();
+  const int txm = tx - 1, txp = tx + 1;
+  const int tym = ty - 1, typ = ty + 1;
+
+  for (int c = z0 - 1; c <= z1; c++) {
+    Plane<BY, NV> &M = mring[c & 1];
+    Plane<BY, NV> &Mprev = mring[(c & 1) ^ 1];
+    // ---- phase A: plane c+1 arrives; trace plane c; x and z fluxes of the scalars ----
+    double qc[NV];
+    ctoprim_cell<NV, GRAV, NE>(upre, gpre, dtxhalf, P, qc);
+    if (RING == 3 || !r_trace) {
+#pragma unroll
+      for (int n = 0; n < NV; n++) qring[RING == 3 ? sc : sa].v[n][ty][tx] = qc[n];
+    }
+    double rnew_m = 0.0;            // the hydro pass's new density of plane c-1
+    double ucur[G];
+    if (r_fxz) {
+      const unsigned pc = plane_off(c);
+      rnew = plane_load(uold, pc, colb);
+#pragma unroll
+      for (int j = 0; j < G; j++) ucur[j] = plane_load(uold + var_of(NH + j) * A.pitch_var, pc, colb);
+      rnew_m = plane_load(unew, plane_off(c - 1), colb);
+    }
+    double qpy[NV];
+    if (ST == 3) __syncthreads();
+    if constexpr (r_trace) {
+      const Plane<BY, NV> &qs = qring[sb];
+      const Plane<BY, NV> &qprev = qring[sa];
+      double qb[NV], dq[3][NV];
+      if (ST == 3) {
+        const Plane<BY, NV> &qnext = qring[sc];
+        const int xs[3] = {txm, tx, txp}, ys[3] = {tym, ty, typ};
+#pragma unroll
+        for (int n = 0; n < NV; n++) {
+          double nb[27], d3[3];
+#pragma unroll
+          for (int dj = 0; dj < 3; dj++)
+#pragma unroll
+            for (int di = 0; di < 3; di++) {
+              nb[di + 3 * dj] = qprev.v[n][ys[dj]][xs[di]];
+              nb[di + 3 * dj + 9] = qs.v[n][ys[dj]][xs[di]];
+              nb[di + 3 * dj + 18] = qnext.v[n][ys[dj]][xs[di]];
+            }
+          qb[n] = nb[13];
+          slope3_var(nb, d3);
+          dq[0][n] = d3[0]; dq[1][n] = d3[1]; dq[2][n] = d3[2];
+        }
+      } else {
+#pragma unroll
+        for (int n = 0; n < NV; n++) {
+          qb[n] = qs.v[n][ty][tx];
+          dq[0][n] = slope1<ST>(qs.v[n][ty][txm], qb[n], qs.v[n][ty][txp], P);
+          dq[1][n] = slope1<ST>(qs.v[n][tym][tx], qb[n], qs.v[n][typ][tx], P);
+          dq[2][n] = slope1<ST>(qprev.v[n][ty][tx], qb[n], qc[n], P);
+        }
+      }
+      if (RING == 2) {
+#pragma unroll
+        for (int n = 0; n < NV; n++) qring[sa].v[n][ty][tx] = qc[n];
+      }
+      double qm[3][NV], qp[3][NV];
+      trace3d_cell<NV, NE>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp);
+#pragma unroll
+      for (int n = 0; n < NV; n++) M.v[n][ty][tx] = qm[1][n];
+#pragma unroll
+      for (int n = 0; n < NV; n++) qpy[n] = qp[1][n];
+      if constexpr (r_fxz) {
+        double qL[NV], fx[NV], fz[NV];
+#pragma unroll
+        for (int n = 0; n < NV; n++) qL[n] = wave_shr1(qm[0][n]);
+        scaled_interface_flux<RS, NV, 0, true, NE>(qL, qp[0], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fx);
+        scaled_interface_flux<RS, NV, 2, true, NE>(qmz, qp[2], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fz);
+#pragma unroll
+        for (int n = 0; n < NV; n++) qmz[n] = qm[2][n];
+#pragma unroll
+        for (int j = 0; j < G; j++) {
+          dz[j] = fzlo[j] - fz[NH + j];
+          fzlo[j] = fz[NH + j];
+          px[j] = ucur[j] + (fx[NH + j] - wave_shl1(fx[NH + j]));
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    {
+      const int pn = min(c + 2, z1 + 1);
+      load_u(pn, upre); load_g(pn, gpre);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+
+    // ---- phase B: y flux of plane c; finish plane c-1 ----
+    if constexpr (ROLE == ROLE_FULL || ROLE == ROLE_HIGH) {
+      double qL[NV], f[NV];
+#pragma unroll
+      for (int n = 0; n < NV; n++) qL[n] = M.v[n][tym][tx];
+      scaled_interface_flux<RS, NV, 1, true, NE>(qL, qpy, P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, f);
+#pragma unroll
+      for (int j = 0; j < G; j++) { fy[j] = f[NH + j]; M.v[NH + j][tym][tx] = fy[j]; }
+    }
+    if constexpr (r_fxz) {
+      double un[G];
+#pragma unroll
+      for (int j = 0; j < G; j++) un[j] = (partx[j] + (fyown[j] - Mprev.v[NH + j][ty][tx])) + dz[j];
+      // set_uold's passive-scalar fix near the density floor (hydro/godunov_fine.f90:176-190), as in sweep_march
+      if (rold < P.smallr && rnew_m > rold) {
+#pragma unroll
+        for (int j = 0; j < G; j++) un[j] = sold[j] * dmaxd(rnew_m, P.smallr) / P.smallr;
+      } else if (rnew_m < P.smallr && rold > rnew_m) {
+#pragma unroll
+        for (int j = 0; j < G; j++) un[j] = sold[j] * P.smallr / dmaxd(rold, P.smallr);
+      }
+      rold = rnew;
+#pragma unroll
+      for (int j = 0; j < G; j++) { sold[j] = ucur[j]; partx[j] = px[j]; fyown[j] = fy[j]; }
+      const unsigned pb = plane_off(c - 1);
+      const unsigned so = (c >= z0 + 1) ? colb_upd : BUF_OOB;
+#pragma unroll
+      for (int j = 0; j < G; j++)
+        if (j < nlive) plane_store(unew + var_of(NH + j) * A.pitch_var, pb, so, un[j]);
+    }
+    if (RING == 3) { const int t = sa; sa = sb; sb = sc; sc = t; }
+    else { const int t = sa; sa = sb; sb = t; }
+  }
+}
+
+template <int ST, int RS, bool GRAV, int NE>
+__global__ __launch_bounds__(BX * 8) void godunov_scalar_kernel(SweepArgs A, int s0, int nlive) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  constexpr int BY = 8;
+  const int ty = threadIdx.y;
+  if (ty >= 2 && ty <= BY - 3) __builtin_amdgcn_s_setprio(3);
+  if (ty == 0) scalar_march<ST, RS, GRAV, NE, ROLE_HALO>(A, s0, nlive, smem_raw);
+  else if (ty == BY - 1) scalar_march<ST, RS, GRAV, NE, ROLE_HALO_HI>(A, s0, nlive, smem_raw);
+  else if (ty == 1) scalar_march<ST, RS, GRAV, NE, ROLE_LOW>(A, s0, nlive, smem_raw);
+  else if (ty == BY - 2) scalar_march<ST, RS, GRAV, NE, ROLE_HIGH>(A, s0, nlive, smem_raw);
+  else scalar_march<ST, RS, GRAV, NE, ROLE_FULL>(A, s0, nlive, smem_raw);
+}
+
+// ---------------------------------------------------------------------------
 // surface pass of a level in tiles (SurfArgs): the fluxes owed to the coarser level
 // ---------------------------------------------------------------------------
 // index (0-based) of cell (x, y, z) of the level in a cell vector; the layout gave every position this pass asks for a tile
@@ -1032,6 +1300,76 @@ hipError_t launch0_nener(SweepArgs &A, int rs, int nvar, int nener, hipStream_t 
   }
 }
 
+// NVAR > 7: the scalar passes that follow the hydro pass (godunov_scalar_kernel), ceil(nscalars / G) launches of the whole
+// region; the last group may hold fewer than G scalars
+template <int ST, int RS, bool GRAV, int NE>
+static hipError_t launch_scalar3(const SweepArgs &A, int nvar, hipStream_t s) {
+  typedef ScalarGroup<ST, RS, NE> SG;
+  auto k = godunov_scalar_kernel<ST, RS, GRAV, NE>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SG::bytes);
+  if (e != hipSuccess) return e;
+  for (int s0 = SG::NH; s0 < nvar; s0 += SG::G) {
+    const int nlive = nvar - s0 < SG::G ? nvar - s0 : SG::G;
+    hipLaunchKernelGGL(k, dim3(A.nblocks), dim3(BX, 8), SG::bytes, s, A, s0, nlive);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+template <int ST, int RS>
+static hipError_t launch_scalar1(SweepArgs &A, int nvar, int nener, bool grav, hipStream_t s) {
+  if (nener == 0) return grav ? launch_scalar3<ST, RS, true, 0>(A, nvar, s) : launch_scalar3<ST, RS, false, 0>(A, nvar, s);
+  if constexpr (RS == RIEMANN_LLF || RS == RIEMANN_HLL || RS == RIEMANN_HLLC) {
+    if (grav) return hipErrorInvalidValue;
+    if (nener == 1) return launch_scalar3<ST, RS, false, 1>(A, nvar, s);
+    if (nener == 2) return launch_scalar3<ST, RS, false, 2>(A, nvar, s);
+  }
+  return hipErrorInvalidValue;
+}
+// The scalar pass updates exactly the cells that the hydro pass of the same region updated -- it reads their new density back
+// from unew -- so its boxes are planned in the hydro pass's tiles (launch1's rows: 12 or 8; the NENER kernels: 8) and re-cut
+// into its own 8-row tiles (4 interior rows; 8 = 2 x 4, so the cut is exact): a shell and an interior call each stand alone.
+static int plan_boxes_scalar(SweepArgs &A, int hydro_by) {
+  const int planned = plan_boxes(A, hydro_by);
+  if (planned <= 0 || hydro_by == 8) return planned;
+  const int f = (hydro_by - 4) / 4, NTY = (A.ny + 3) / 4;
+  int nblocks = 0, k = 0;
+  for (int i = 0; i < A.nbox; i++) {
+    SweepBox B = A.box[i];
+    const int ty0 = B.ty0 * f, ty1 = min((B.ty0 + B.nty) * f, NTY);
+    if (ty1 <= ty0) continue;
+    B.ty0 = ty0; B.nty = ty1 - ty0; B.first = nblocks;
+    nblocks += B.ntx * B.nty * ((B.zhi - B.zlo + B.zchunk - 1) / B.zchunk);
+    A.box[k++] = B;
+  }
+  A.nbox = k;
+  A.nblocks = nblocks;
+  return nblocks;
+}
+template <int ST>
+hipError_t launch0_scalar(SweepArgs &A, int rs, int by, int nvar, int nener, bool grav, hipStream_t s) {
+  if constexpr (ST == 4 || ST == 5 || ST == 6) {
+    return hipErrorInvalidValue;
+  } else {
+    if (A.stat || nener < 0 || nener > MAX_NENER || nvar <= 7 || nvar > MAX_NVAR) return hipErrorInvalidValue;
+    const bool heavy = nener > 0 || rs == RIEMANN_EXACT || ST == 3;       // launch1 at NV = 5, muscl; launch_nener1
+    const int hydro_by = (by == 0 || heavy) ? (heavy ? 8 : 12) : by;
+    if (hydro_by != 8 && hydro_by != 12) return hipErrorInvalidValue;
+    const int planned = plan_boxes_scalar(A, hydro_by);
+    if (planned < 0) return hipErrorInvalidValue;
+    if (planned == 0) return hipSuccess;
+    switch (rs) {
+      case RIEMANN_LLF: return launch_scalar1<ST, RIEMANN_LLF>(A, nvar, nener, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+      case RIEMANN_HLLC: return launch_scalar1<ST, RIEMANN_HLLC>(A, nvar, nener, grav, s);
+      case RIEMANN_HLL: return launch_scalar1<ST, RIEMANN_HLL>(A, nvar, nener, grav, s);
+      case RIEMANN_ACOUSTIC: return launch_scalar1<ST, RIEMANN_ACOUSTIC>(A, nvar, nener, grav, s);
+      case RIEMANN_EXACT: return launch_scalar1<ST, RIEMANN_EXACT>(A, nvar, nener, grav, s);
+#endif
+    }
+    return hipErrorInvalidValue;
+  }
+}
+
 template <int ST>
 hipError_t launch0(SweepArgs &A, int rs, int by, int scheme, int nvar, bool grav, hipStream_t s) {
   switch (rs) {
@@ -1049,6 +1387,7 @@ hipError_t launch0(SweepArgs &A, int rs, int by, int scheme, int nvar, bool grav
 #if defined(SWEEP_ST)
 template hipError_t launch0<SWEEP_ST>(SweepArgs &, int, int, int, int, bool, hipStream_t);
 template hipError_t launch0_nener<SWEEP_ST>(SweepArgs &, int, int, int, hipStream_t);
+template hipError_t launch0_scalar<SWEEP_ST>(SweepArgs &, int, int, int, int, bool, hipStream_t);
 #if SWEEP_ST == 3
 template hipError_t launch0<4>(SweepArgs &, int, int, int, int, bool, hipStream_t);
 template hipError_t launch0<5>(SweepArgs &, int, int, int, int, bool, hipStream_t);
@@ -1062,6 +1401,9 @@ SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
 #define SWEEP_EXTERN_NENER(K) extern template hipError_t launch0_nener<K>(SweepArgs &, int, int, int, hipStream_t);
 SWEEP_EXTERN_NENER(0) SWEEP_EXTERN_NENER(1) SWEEP_EXTERN_NENER(2) SWEEP_EXTERN_NENER(3) SWEEP_EXTERN_NENER(7) SWEEP_EXTERN_NENER(8)
 #undef SWEEP_EXTERN_NENER
+#define SWEEP_EXTERN_SCALAR(K) extern template hipError_t launch0_scalar<K>(SweepArgs &, int, int, int, int, bool, hipStream_t);
+SWEEP_EXTERN_SCALAR(0) SWEEP_EXTERN_SCALAR(1) SWEEP_EXTERN_SCALAR(2) SWEEP_EXTERN_SCALAR(3) SWEEP_EXTERN_SCALAR(7) SWEEP_EXTERN_SCALAR(8)
+#undef SWEEP_EXTERN_SCALAR
 #endif
 
 #ifndef SWEEP_ST
@@ -1102,6 +1444,22 @@ hipError_t launch_godunov_sweep_nener(SweepArgs &A, int slope_type, int riemann,
     case 3: return launch0_nener<3>(A, riemann, nvar, nener, s);
     case 7: return launch0_nener<7>(A, riemann, nvar, nener, s);
     case 8: return launch0_nener<8>(A, riemann, nvar, nener, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_godunov_sweep_scalars(SweepArgs &A, int slope_type, int riemann, int by, int nvar, int nener, bool grav, hipStream_t s) {
+  if ((unsigned long)A.pitch_z * 8ul >= (1ul << 31) || (unsigned long)A.pitch_var * 8ul >= (1ul << 32))
+    return hipErrorInvalidValue;
+  switch (slope_type) {
+    case 1: return launch0_scalar<1>(A, riemann, by, nvar, nener, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case 0: return launch0_scalar<0>(A, riemann, by, nvar, nener, grav, s);
+    case 2: return launch0_scalar<2>(A, riemann, by, nvar, nener, grav, s);
+    case 3: return launch0_scalar<3>(A, riemann, by, nvar, nener, grav, s);
+    case 7: return launch0_scalar<7>(A, riemann, by, nvar, nener, grav, s);
+    case 8: return launch0_scalar<8>(A, riemann, by, nvar, nener, grav, s);
 #endif
   }
   return hipErrorInvalidValue;

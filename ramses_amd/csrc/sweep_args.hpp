@@ -79,6 +79,10 @@ struct SurfArgs {
 namespace strictmode {
 // NENER = nener (1, 2) non-thermal energies, the plain brick, muscl, no gravity
 hipError_t launch_godunov_sweep_nener(SweepArgs &A, int slope_type, int riemann, int nvar, int nener, hipStream_t s);
+// NVAR > 7: the passive scalars 5+nener .. nvar-1 in groups, after the hydro pass of the same region on the same stream (by = the
+// tile rows passed to that pass's launch_godunov_sweep; its cells are the ones updated), the plain brick, muscl; gravity with
+// nener = 0 only
+hipError_t launch_godunov_sweep_scalars(SweepArgs &A, int slope_type, int riemann, int by, int nvar, int nener, bool grav, hipStream_t s);
 hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, int nvar, int scheme, bool grav, hipStream_t s);
 hipError_t launch_godunov_sweep(SweepArgs &A, int slope_type, int riemann, int by, int scheme, int nvar,
                                 bool grav, hipStream_t s);
@@ -87,6 +91,10 @@ int tile_sweep_rows(int riemann, int nvar, int slope_type, int scheme);
 namespace fastmode {
 // NENER = nener (1, 2) non-thermal energies, the plain brick, muscl, no gravity
 hipError_t launch_godunov_sweep_nener(SweepArgs &A, int slope_type, int riemann, int nvar, int nener, hipStream_t s);
+// NVAR > 7: the passive scalars 5+nener .. nvar-1 in groups, after the hydro pass of the same region on the same stream (by = the
+// tile rows passed to that pass's launch_godunov_sweep; its cells are the ones updated), the plain brick, muscl; gravity with
+// nener = 0 only
+hipError_t launch_godunov_sweep_scalars(SweepArgs &A, int slope_type, int riemann, int by, int nvar, int nener, bool grav, hipStream_t s);
 hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, int nvar, int scheme, bool grav, hipStream_t s);
 hipError_t launch_godunov_sweep(SweepArgs &A, int slope_type, int riemann, int by, int scheme, int nvar,
                                 bool grav, hipStream_t s);

@@ -200,6 +200,12 @@ subroutine godunov_fine(ilevel)
           & 'without physical boundaries, difmag or pressure_fix; the tree-walking sweep of AMR levels has no NENER'
      call ramses_amd_fatal('godunov_fine (NENER>0 on an AMR level / the tree walker)')
   end if
+  ! so do more than 7 variables (passive scalars beyond two, or NENER with passive scalars): NVAR up to RAMSES_AMD_MAX_NVAR
+  if(amr_level.and.nvar>7)then
+     if(myid==1)write(*,*)'ramses_amd: NVAR=',nvar,' needs a fully refined periodic level (one rank, or MPI residency), ', &
+          & 'without physical boundaries, difmag or pressure_fix; AMR levels and the tree-walking sweep implement NVAR<=7'
+     call ramses_amd_fatal('godunov_fine (NVAR>7 on an AMR level / the tree walker)')
+  end if
 
   if(amr_level)then
      ! f, divu, enew exist only with poisson resp. pressure_fix: uold stands in (never read)

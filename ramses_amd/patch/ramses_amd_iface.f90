@@ -40,6 +40,7 @@ module ramses_amd_iface
   ! MAXITER of the reference's V-cycle loop (poisson/multigrid_fine_commons.f90:34) = MAXITER of csrc/capi.hip, pois_amr.hip, mg_dist.hip
   integer, parameter :: ramses_amd_mg_maxiter = 10
   integer, parameter :: RAMSES_AMD_EUNSUPPORTED_CODE = -2     ! include/ramses_amd.h: RAMSES_AMD_EUNSUPPORTED
+  integer, parameter :: RAMSES_AMD_MAX_NVAR = 16              ! include/ramses_amd.h: RAMSES_AMD_MAX_NVAR
   integer, save :: ramses_amd_tree_epoch = 0
   ! AMR residency with several MPI ranks: count of build_comm calls per level (the device copy of a level's
   ! communicators is re-sent when its epoch is behind); the transport has been chosen (ramses_amd_halo_init)
@@ -132,9 +133,9 @@ contains
     use amr_parameters, only: ndim
     use hydro_parameters, only: nener, nvar
     if (hydro .and. nener > 0) then
-       if (nener > 2 .or. ndim /= 3 .or. nvar < ndim + 2 + nener .or. nvar > 7) then
+       if (nener > 2 .or. ndim /= 3 .or. nvar < ndim + 2 + nener .or. nvar > RAMSES_AMD_MAX_NVAR) then
           write(*,*) 'ramses_amd: this binary was built with NENER=', nener, ' NVAR=', nvar, ' NDIM=', ndim, &
-               & '; the device hydro path implements NENER=1 (NVAR=6,7) and NENER=2 (NVAR=7) with NDIM=3'
+               & '; the device hydro path implements NENER=1, 2 with 5+NENER <= NVAR <=', RAMSES_AMD_MAX_NVAR, ' and NDIM=3'
           call ramses_amd_fatal('build check (NENER)')
        end if
        if (poisson) then
@@ -613,6 +614,8 @@ contains
        ramses_amd_amr_ok = ramses_amd_enabled()
        ! non-thermal energies run on uniform levels only (ramses_amd_check_build)
        if (nener > 0) ramses_amd_amr_ok = .false.
+       ! so do more than 7 variables (passive scalars beyond NVAR=7: csrc/capi_shared.hpp refuse_scalars)
+       if (nvar > 7) ramses_amd_amr_ok = .false.
        call get_environment_variable('RAMSES_AMD_RESIDENT_AMR', val, status=stat)
        if (stat == 0) then
           if (trim(val) == '0') ramses_amd_amr_ok = .false.
