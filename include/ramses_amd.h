@@ -921,6 +921,10 @@ int ramses_amd_amrres_enable_pfix(void);
 int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid);
 int ramses_amd_amrres_set_uold_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt, double dx_loc,
                                     double beta_fix, double hexp);
+/* divu / enew of the listed octs' cells into the host vectors divu(1:ncell), enew(1:ncell) (indexed like uold(:,1), as
+ * ramses_amd_amrres_sync_level does for uold): the device vectors are scratch of one hydro step, this call is for tests and for a
+ * user debugging a run.  EINVAL without a resident state or before ramses_amd_amrres_enable_pfix. */
+int ramses_amd_amrres_sync_pfix(int ngrid, const int *igrid, double *divu, double *enew);
 /* rho_fine(ilevel,icount) on the resident density of an AMR run (single rank, periodic nx=ny=nz=1 box, no particles):
  *   multipole_fine(l) + cic_from_multipole(l) for l = nlevelmax .. ilevel (pm/rho_fine.f90:45-60,666-1142): multipoles of leaf
  *   and split cells, the CIC deposit at every cell's centre of mass added in the reference's order, the four sequential sums
@@ -952,8 +956,11 @@ int ramses_amd_amrres_godunov(const ramses_amd_hydro_params *p, int ilevel, int 
  * ramses_amd_amrres_godunov: fluxes through the faces of refined cells reset, the update starting from unew
  * (hydro/godunov_fine.f90:661-666,720-790), missing neighbour octs interpolated once per sweep into free tile slots (:563-626),
  * the fluxes owed to the coarser level filed and replayed in the reference's order (:798-908) -- strict arithmetic,
- * bit-identical to the tree-walking sweep and to the reference.  NVAR = 5, muscl, slope types 0/1/2/7/8, every Riemann solver
- * but 'exact', no difmag / pressure_fix, one coarse cell (no physical boundaries); anything else keeps the tree-walking sweep.
+ * bit-identical to the tree-walking sweep and to the reference.  NVAR = 5 .. 7, muscl and plmde (NVAR = 5), slope types
+ * 0/1/2/3/7/8, every Riemann solver, one coarse cell (no physical boundaries), no difmag; anything else keeps the tree-walking
+ * sweep.  pressure_fix (ramses_amd_amrres_enable_pfix) takes the tiles too, muscl only and in strict arithmetic whatever
+ * fast_math says: the face velocity and the internal-energy flux ride through the sweep, the surface pass and the replay as two
+ * more flux components into divu / enew (:752-790, :849-881); plmde with pressure_fix keeps the tree-walking sweep.
  * Switches: RAMSES_AMD_DEVICE_ORDER=0 (the host's numbering on the device, tree-walking sweep everywhere), RAMSES_AMD_TILES=0
  * (Z-order numbering, no tiles), RAMSES_AMD_COVERED_DENSE=0 / RAMSES_AMD_TILE_DENSE=0 (fully refined / partial levels keep the
  * tree-walking sweep), RAMSES_AMD_DEVICE_OCTS=f (the device's index space = f x ngridmax: tiles that are not full cost

@@ -552,7 +552,8 @@ __global__ __launch_bounds__(256) void plan_event_index_kernel(PlanArgs A, const
 }
 __global__ __launch_bounds__(256) void tile_coarse_update_kernel(PlanArgs A, double *__restrict__ unew, const double *__restrict__ corr,
                                                                  const int *__restrict__ corr_tgt, const int *__restrict__ evt_of,
-                                                                 const int *__restrict__ events, int nevent, int nvector, int NV) {
+                                                                 const int *__restrict__ events, int nevent, int nvector, int NV,
+                                                                 double *__restrict__ divu, double *__restrict__ enew) {
   const long e0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e0 >= nevent) return;
   const long ev = events[e0];
@@ -602,6 +603,22 @@ __global__ __launch_bounds__(256) void tile_coarse_update_kernel(PlanArgs A, dou
     }
     unew[(long)v * A.ncell + C - 1] = val;
   }
+  // pressure_fix: the records' last two slots (the face velocity and the internal-energy flux) into divu / enew of the coarse
+  // cell, each vector an accumulation of its own in the same order (hydro/godunov_fine.f90:849-881)
+  if (divu)
+    for (int v = 0; v < 2; v++) {
+      double *vec = v == 0 ? divu : enew;
+      double val = vec[C - 1];
+      for (int i = 0; i < n; i++) {
+        const double *c = corr + (long)evt_of[src[i]] * 4 * CV;
+        const bool left = ((src[i] % 6) & 1) == 0;
+        for (int q = 0; q < 4; q++) {
+          const double t = c[q * CV + NV + v] * oneontwotondim;
+          val = left ? val - t : val + t;
+        }
+      }
+      vec[C - 1] = val;
+    }
 }
 // which (tile column of 60 x 8 cells, chunk of 8 planes) hold listed cells
 __global__ __launch_bounds__(256) void plan_work_kernel(PlanArgs A, int wtx, int rows, int wz, unsigned char *flag) {
@@ -1448,11 +1465,16 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   }
   // (round 6: runs with one or two passive scalars and the Newton solver too -- kernels of 8 rows, work items of 4)
   const int nvar = R.nvar;
-  if (nvar < 5 || nvar > 7 || p->nvar != nvar || p->ndim != 3 || p->difmag > 0.0 || R.pfix) return 0;
+  if (nvar < 5 || nvar > 7 || p->nvar != nvar || p->ndim != 3 || p->difmag > 0.0) return 0;
+  // pressure_fix: divu / enew ride through the dense sweep as two more flux components (muscl; plmde keeps the tree walker, whose
+  // single-oct kernel it takes there too) -- in strict arithmetic whatever fast_math says: the two face quantities exist in the
+  // reference's operation order only, and a bit-identical result meets the fast mode's 1e-12 contract
+  const bool pfix = R.pfix;
+  if (pfix && p->scheme != RAMSES_AMD_SCHEME_MUSCL) return 0;
   if (p->scheme != RAMSES_AMD_SCHEME_MUSCL && !(p->scheme == RAMSES_AMD_SCHEME_PLMDE && nvar == 5)) return 0;
   const int st = p->slope_type;
   if (!(st == 0 || st == 1 || st == 2 || st == 3 || st == 7 || st == 8)) return 0;
-  const int rows = strictmode::tile_sweep_rows(p->riemann, nvar, st, p->scheme);
+  const int rows = pfix ? strictmode::tile_sweep_rows_pfix(nvar, st) : strictmode::tile_sweep_rows(p->riemann, nvar, st, p->scheme);
   if (interpol_var < 0 || interpol_var > 2 || interpol_type < 0 || interpol_type > 4) return 0;
   if ((unsigned long)R.ncell * 8ul >= (1ul << 31)) {      // lane offsets into a cell vector are 31-bit byte offsets
     static bool told = false;
@@ -1481,6 +1503,8 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   SweepArgs A;
   A.uold = R.uold.as<double>(); A.unew = R.unew.as<double>(); A.grav = R.grav ? R.f.as<double>() : nullptr;      // the cell vectors themselves
   A.stat = R.stat.as<unsigned char>(); A.dir = L.dir.as<int>(); A.work = P.work.as<int>(); A.nwork = P.nwork;
+  SweepPfix X;
+  if (pfix) { X.divu = R.divu.as<double>(); X.enew = R.enew.as<double>(); }
   A.ntx = L.ntx; A.nty = L.nty; A.ntz = L.ntz; A.ngd = R.ngridmax; A.ncoarse = R.ncoarse;
   // (the finest level of the tree: nothing has touched unew since set_unew copied uold into it -- the contract of this routine,
   //  hydro/godunov_fine.f90:5-35 after amr_step's set_unew -- so the kernel re-reads uold from L2 instead of streaming unew)
@@ -1499,7 +1523,7 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   // (event, fine face).  Arithmetic: strict (bit-identical) unless the caller's parameters ask for the fast build (fast_math: the
   // patched program's default, certified <= 1e-12 against the reference program on an AMR run with sub-cycling and regrids,
   // tests/test_fast_certificate_gpu.py; RAMSES_AMD_STRICT=1 selects the bit-identical build)
-  const bool fast = p->fast_math != 0;
+  const bool fast = p->fast_math != 0 && !pfix;
   if (P.nevent > 0) {
     SurfArgs S;
     S.uold = A.uold; S.grav = A.grav; S.stat = A.stat; S.dir = A.dir; S.tileid = L.tileid.as<int>();
@@ -1510,12 +1534,14 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
     { const char *e = getenv("RAMSES_AMD_EVENT_LANES"); S.qminor = e ? (e[0] == 'q' ? 1 : 0) : EVENT_QMINOR_DEFAULT; }
     // (the pass on a stream of its own beside the marching kernel was measured in round 6 -- 2.62 -> 2.54 ms strict, 2.09 -> 2.08 fast
     //  on the shell level: a CU the marching kernel fills has no registers left for it, the two take turns; dropped)
-    hipError_t es = fast ? fastmode::launch_surface_flux(S, st, p->riemann, nvar, p->scheme, R.grav, s) : strictmode::launch_surface_flux(S, st, p->riemann, nvar, p->scheme, R.grav, s);
+    hipError_t es = pfix ? strictmode::launch_surface_flux_pfix(S, st, p->riemann, nvar, R.grav, s)
+                    : fast ? fastmode::launch_surface_flux(S, st, p->riemann, nvar, p->scheme, R.grav, s) : strictmode::launch_surface_flux(S, st, p->riemann, nvar, p->scheme, R.grav, s);
     if (es == hipErrorInvalidValue) { (void)hipGetLastError(); return 0; }     // a variant the tile kernels do not cover
     HCHK(es, "surface pass of a level in tiles");
   }
-  hipError_t e = fast ? fastmode::launch_godunov_sweep(A, st, p->riemann, rows + 4, p->scheme, nvar, R.grav, s)
-                      : strictmode::launch_godunov_sweep(A, st, p->riemann, rows + 4, p->scheme, nvar, R.grav, s);
+  hipError_t e = pfix ? strictmode::launch_godunov_sweep_pfix(A, X, st, p->riemann, nvar, R.grav, s)
+                 : fast ? fastmode::launch_godunov_sweep(A, st, p->riemann, rows + 4, p->scheme, nvar, R.grav, s)
+                        : strictmode::launch_godunov_sweep(A, st, p->riemann, rows + 4, p->scheme, nvar, R.grav, s);
   if (e == hipErrorInvalidValue) { (void)hipGetLastError(); return 0; }     // a variant the tile kernels do not cover
   HCHK(e, "dense sweep of a level in tiles");
   // what the level owes to the leaf cells of the coarser one, replayed in the reference's order
@@ -1527,7 +1553,7 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
     Q.dir = L.dir.as<int>(); Q.tileid = L.tileid.as<int>(); Q.base = L.base; Q.no = L.no; Q.ntx = L.ntx; Q.nty = L.nty; Q.ntz = L.ntz;
     if (P.nevent > 0) {
       hipLaunchKernelGGL(tile_coarse_update_kernel, dim3((P.nevent + 255) / 256), dim3(256), 0, s, Q, R.unew.as<double>(), P.corr.as<double>(), P.corr_tgt.as<int>(),
-                         P.evt_of.as<int>(), P.events.as<int>() + 1, P.nevent, nvector, nvar);
+                         P.evt_of.as<int>(), P.events.as<int>() + 1, P.nevent, nvector, nvar, pfix ? R.divu.as<double>() : nullptr, pfix ? R.enew.as<double>() : nullptr);
       HCHK(hipGetLastError(), "coarse corrections");
     }
   }
@@ -2020,6 +2046,32 @@ int ramses_amd_amrres_set_uold_pfix(const ramses_amd_hydro_params *p, int ngrid,
   hipLaunchKernelGGL(lvl_set_uold_kernel, g, b, 0, nullptr, A, p->smallr);
   hipLaunchKernelGGL(lvl_pfix_switch_kernel, g, b, 0, nullptr, A, R.divu.as<double>(), R.enew.as<double>(), dx_loc, dt, beta_fix, hexp, p->smallr);
   HCHK(hipGetLastError(), "set_uold launch");
+  return 0;
+}
+// divu / enew of the listed octs' cells into the host vectors (1:ncell): what a test or a user debugging a pressure_fix run reads
+int ramses_amd_amrres_sync_pfix(int ngrid, const int *igrid, double *divu, double *enew) {
+  AmrRes &R = g_ar;
+  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "sync_pfix: no resident AMR state");
+  if (!R.pfix) return failf(RAMSES_AMD_EINVAL, "sync_pfix: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
+  if (!divu || !enew) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  LvlArgs A;
+  if (int rc = set_level(R, ngrid, igrid, A)) return rc;
+  if (ngrid == 0) return 0;
+  const long tot = (long)ngrid * 8;
+  HCHK(R.pack.ensure(sizeof(double) * (size_t)tot), "hipMalloc");
+  R.hpack.resize((size_t)tot);
+  for (int v = 0; v < 2; v++) {
+    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for(tot)), dim3(256), 0, nullptr, v == 0 ? R.divu.as<double>() : R.enew.as<double>(), R.pack.as<double>(),
+                       R.cur_ig, ngrid, 1, R.ncell, R.ncoarse, R.ngridmax);
+    HCHK(hipGetLastError(), "divu / enew pack launch");
+    HCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost), "D2H divu / enew");
+    double *host = v == 0 ? divu : enew;
+    for (int ind = 0; ind < 8; ind++) {
+      double *dst = host + R.ncoarse + (size_t)ind * R.ngh - 1;
+      const double *src = R.hpack.data() + (size_t)ind * ngrid;
+      for (int i = 0; i < ngrid; i++) dst[igrid[i]] = src[i];
+    }
+  }
   return 0;
 }
 

@@ -54,8 +54,11 @@ struct Plane {
 // in tiles, and the 12-row kernels with gravity: both spill otherwise): the partial update of plane c-1 that the full rows carry
 // across the trace of plane c -- u + x flux difference and the own -y flux -- waits in LDS instead of in 20 VGPRs; the y slots
 // then hold the rows that use them (1 .. BY-2) only.
-template <int ST, int BY, int NV, bool MASK, bool GRAV>
+// (NX: components that ride beside the NV fluxes through the y slots and the parked partial update -- the two face quantities
+// of pressure_fix)
+template <int ST, int BY, int NV, bool MASK, bool GRAV, int NX = 0>
 struct Lds {
+  static constexpr int NF = NV + NX;
   static constexpr int RING = (ST == 3) ? 3 : 2;
 #ifndef SWEEP_PARK_PLAIN
 #ifdef RAMSES_AMD_FAST
@@ -69,8 +72,8 @@ struct Lds {
   static constexpr int M0 = PARK ? 1 : 0;                // first row that owns a slot
   static constexpr size_t q_off = 0;
   static constexpr size_t m_off = q_off + RING * sizeof(Plane<BY, NV>);
-  static constexpr size_t park_off = m_off + 2 * sizeof(Plane<MR, NV>);
-  static constexpr size_t mask_off = park_off + (PARK ? sizeof(double) * 2 * NV * (BY - 4) * BX : 0);   // MASK: [3][BY][BX] status bytes
+  static constexpr size_t park_off = m_off + 2 * sizeof(Plane<MR, NF>);
+  static constexpr size_t mask_off = park_off + (PARK ? sizeof(double) * 2 * NF * (BY - 4) * BX : 0);   // MASK: [3][BY][BX] status bytes
   static constexpr size_t sloc_off = mask_off + (MASK ? 3 * BY * BX : 0);                                // MASK: [BY][BX] lane part of the cell index
   static constexpr size_t bytes = sloc_off + (MASK ? 4 * BY * BX : 0);
 };
@@ -143,16 +146,21 @@ __device__ __forceinline__ int dir_load(const int *base, unsigned plane_ints, un
 // the level is stored in tiles of 32 x 4 x 4 octs, a lane finds the cell of its (plane, column) through the tile directory
 // (one 4-byte load per 8 planes, issued four planes ahead; 256-byte runs of a variable along x inside a tile), the status byte of
 // the cell says whether it is refined (fluxes reset), updated (stored) or a ghost (interpolated: fluxes filed for the coarser level)
-template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, int ROLE, bool MASK, int NE = 0>
-__device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *smem_raw) {
+// PFIX (MASK, strict arithmetic only): pressure_fix -- the face velocity and the internal-energy flux of every interface
+// (hydro/umuscl.f90:843-850) ride beside the NV fluxes as components NV and NV + 1 through the same differencing and the same
+// resets, and land in divu / enew of the cells whose unew is stored (hydro/godunov_fine.f90:720-790)
+template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, int ROLE, bool MASK, int NE = 0, bool PFIX = false>
+__device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *smem_raw, const SweepPfix &X = SweepPfix()) {
+  static_assert(!PFIX || (MASK && NE == 0 && SCHEME == 0), "pressure_fix: the sweep of a level in tiles, muscl");
+  constexpr int NF = NV + (PFIX ? 2 : 0);   // components differenced
   const bool DXPOW2 = A.pow2 != 0;   // uniform
-  typedef Lds<ST, BY, NV, MASK, GRAV> L;
+  typedef Lds<ST, BY, NV, MASK, GRAV, NF - NV> L;
   constexpr int RING = L::RING;
   constexpr bool PARK = L::PARK;
   constexpr int M0 = L::M0;
   Plane<BY, NV> *qring = reinterpret_cast<Plane<BY, NV> *>(smem_raw + L::q_off);  // [RING] primitives of planes c-1, c (, c+1)
-  Plane<L::MR, NV> *mring = reinterpret_cast<Plane<L::MR, NV> *>(smem_raw + L::m_off);   // [2] +y traced state / y flux slots, by plane parity
-  double (*park)[BY - 4][BX] = reinterpret_cast<double (*)[BY - 4][BX]>(smem_raw + L::park_off);   // PARK: [2 NV] of the full rows
+  Plane<L::MR, NF> *mring = reinterpret_cast<Plane<L::MR, NF> *>(smem_raw + L::m_off);   // [2] +y traced state / y flux slots, by plane parity
+  double (*park)[BY - 4][BX] = reinterpret_cast<double (*)[BY - 4][BX]>(smem_raw + L::park_off);   // PARK: [2 NF] of the full rows
 
   const int tx = threadIdx.x, ty = threadIdx.y;
   const HydroConst &P = A.P;
@@ -323,10 +331,12 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
   // level without finer octs (set_unew has just made unew = uold there), uold again: the planes this workgroup read two iterations
   // ago, from L2 instead of a second stream from HBM
   const double *__restrict__ bsrc = A.base_uold ? uold : unew;
-  auto load_base = [&](int p, double (&u)[NV]) {
+  auto load_base = [&](int p, double (&u)[NF]) {
     const unsigned pb = zpart(p) * 8u, off = tbp(p);
 #pragma unroll
     for (int n = 0; n < NV; n++) u[n] = plane_load(bsrc + (long)(n & ~1) * A.pitch_var, pb + (n & 1) * odd_var, off);
+    // (divu / enew are read whatever base_uold says: they hold what set_unew and the finer level left there)
+    if constexpr (PFIX) { u[NV] = plane_load(X.divu, pb, off); u[NV + 1] = plane_load(X.enew, pb, off); }
   };
   int ok_zlo = 0;   // MASK: plane c-1's status byte of this column
   int spre = 0;     // MASK: plane c+1's status byte, on its way
@@ -343,7 +353,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 
   // ---- register state carried along z --------------------------------------
   double qmz[NV];                 // qm along z of plane c-1 (state on its +z face)
-  double fzlo[NV];                // z flux through the -z face of plane c-1
+  double fzlo[NF];                // z flux through the -z face of plane c-1
   double upre[NV], gpre[3];       // prefetch: plane c+1 on entry of iteration c
   double rold = 0.0, sold[NV > 5 ? NV - 5 : 1];   // uold density / scalars of plane c-1 (NV>5 only)
   double ukeep[NV];               // KEEP: the conservative state of plane c
@@ -378,7 +388,9 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     for (int n = 0; n < NV; n++) qring[sb].v[n][ty][tx] = q[n];
     load_u(z0, upre); load_g(z0, gpre);
 #pragma unroll
-    for (int n = 0; n < NV; n++) { qmz[n] = 1.0; fzlo[n] = 0.0; }
+    for (int n = 0; n < NV; n++) qmz[n] = 1.0;
+#pragma unroll
+    for (int n = 0; n < NF; n++) fzlo[n] = 0.0;
   }
   // Enter the loop with no load in flight: otherwise the loop header inherits
   // "prefetch pending" from this path and waits (in issue order) behind the
@@ -402,21 +414,23 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
   // -> c.  Nobody else touches the slot, so the second barrier of the two-barrier loop (and
   // the lock-step of the heavy waves it enforced) is gone.  Same operations in the same
   // order per cell: ((u + (fx- - fx+)) + (fy- - fy+)) + (fz- - fz+).
-  double partx[NV];                      // u + x flux difference of plane c-1
-  double fyown[NV];                      // y flux through the -y face of plane c-1 (computed by this row; its copy
+  double partx[NF];                      // u + x flux difference of plane c-1
+  double fyown[NF];                      // y flux through the -y face of plane c-1 (computed by this row; its copy
                                          // in slot ty-1 belongs to row ty-1, which reuses the slot without a barrier)
   double rnew = 0.0, snew[NV > 5 ? NV - 5 : 1];
   double bcar[NV];                       // LATE: the state the update of plane c-1 starts from
 #pragma unroll
-  for (int n = 0; n < NV; n++) { partx[n] = 0.0; fyown[n] = 0.0; bcar[n] = 0.0; }
+  for (int n = 0; n < NV; n++) bcar[n] = 0.0;
+#pragma unroll
+  for (int n = 0; n < NF; n++) { partx[n] = 0.0; fyown[n] = 0.0; }
   if (PARK && r_fxz) {
 #pragma unroll
-    for (int n = 0; n < 2 * NV; n++) park[n][ty - 2][tx] = 0.0;
+    for (int n = 0; n < 2 * NF; n++) park[n][ty - 2][tx] = 0.0;
   }
 
   for (int c = z0 - 1; c <= z1; c++) {
-    Plane<L::MR, NV> &M = mring[c & 1];
-    Plane<L::MR, NV> &Mprev = mring[(c & 1) ^ 1];
+    Plane<L::MR, NF> &M = mring[c & 1];
+    Plane<L::MR, NF> &Mprev = mring[(c & 1) ^ 1];
     // ---- phase A: plane c+1 arrives; trace plane c; x and z fluxes ------------------
     double qc[NV];
     ctoprim_cell<NV, GRAV, NE>(upre, gpre, dtxhalf, P, qc);
@@ -426,12 +440,12 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #pragma unroll
       for (int n = 0; n < NV; n++) qring[RING == 3 ? sc : sa].v[n][ty][tx] = qc[n];
     }
-    double ucur[NV];
+    double ucur[NF];
     if (r_fxz && !LATE) {
       if (KEEP && (!MASK || A.base_uold)) {
 #pragma unroll
         for (int n = 0; n < NV; n++) ucur[n] = ukeep[n];          // plane c, held since it arrived
-      } else if (MASK) load_base(c, ucur);
+      } else if constexpr (MASK) load_base(c, ucur);
       else load_u(c, ucur);
     }
     if (KEEP && r_fxz) {
@@ -444,7 +458,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       smask[((c + 3) % 3 * BY + ty) * BX + tx] = (unsigned char)okc;   // row ty+1 reads it after the barrier (its -y neighbour), row ty-1 one plane later
     }
 
-    double qpy[NV], dz[NV], px[NV];
+    double qpy[NV], dz[NF], px[NF];
     if (ST == 3) __syncthreads();  // the 27-point slope reads the neighbours' plane c+1 just written
     if constexpr (r_trace) {
       const Plane<BY, NV> &qs = qring[sb];
@@ -504,23 +518,36 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #pragma unroll
       for (int n = 0; n < NV; n++) qpy[n] = qp[1][n];
       if constexpr (r_fxz) {
-        double qL[NV], fx[NV], fz[NV];
+        double qL[NV], fx[NF], fz[NF];
 #pragma unroll
         for (int n = 0; n < NV; n++) qL[n] = wave_shr1(qm[0][n]);  // +x state of column tx-1
+        if constexpr (PFIX) {
+          double f[NV], t[2];
+          scaled_interface_flux_tmp<RS, NV, 0>(qL, qp[0], P, A.dt, A.dx, A.rdx, DXPOW2, f, t);
+#pragma unroll
+          for (int n = 0; n < NV; n++) fx[n] = f[n];
+          fx[NV] = t[0]; fx[NV + 1] = t[1];
+          scaled_interface_flux_tmp<RS, NV, 2>(qmz, qp[2], P, A.dt, A.dx, A.rdx, DXPOW2, f, t);
+#pragma unroll
+          for (int n = 0; n < NV; n++) fz[n] = f[n];
+          fz[NV] = t[0]; fz[NV + 1] = t[1];
+        } else {
         scaled_interface_flux<RS, NV, 0, !MASK, NE>(qL, qp[0], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fx);
         // z flux through the face between planes c-1 and c
         scaled_interface_flux<RS, NV, 2, !MASK, NE>(qmz, qp[2], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fz);
+        }
         if (MASK) {
           // hydro/godunov_fine.f90:720-747: the flux through a face is reset when the cell on either side is refined
           const int s_xm = wave_shr1_i(okc);
           const bool zx = ((okc | s_xm) & CELL_REFINED) != 0, zz = ((okc | ok_zlo) & CELL_REFINED) != 0;
 #pragma unroll
-          for (int n = 0; n < NV; n++) { fx[n] = zx ? 0.0 : fx[n]; fz[n] = zz ? 0.0 : fz[n]; }
+          for (int n = 0; n < NF; n++) { fx[n] = zx ? 0.0 : fx[n]; fz[n] = zz ? 0.0 : fz[n]; }
         }
-        double fxh[NV];
+        double fxh[NF];
 #pragma unroll
-        for (int n = 0; n < NV; n++) {
-          qmz[n] = qm[2][n];
+        for (int n = 0; n < NV; n++) qmz[n] = qm[2][n];
+#pragma unroll
+        for (int n = 0; n < NF; n++) {
           dz[n] = fzlo[n] - fz[n];          // z flux difference of plane c-1
           fzlo[n] = fz[n];
           fxh[n] = wave_shl1(fx[n]);        // -x face flux of column tx+1
@@ -552,34 +579,42 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     __syncthreads();  // the one barrier: +y states of plane c and y fluxes of plane c-1 visible
 
     // ---- phase B: y flux of plane c; finish plane c-1 --------------------------------
-    double fy[NV];
+    double fy[NF];
     if constexpr (ROLE == ROLE_FULL || ROLE == ROLE_HIGH) {
       double qL[NV];
 #pragma unroll
       for (int n = 0; n < NV; n++) qL[n] = M.v[n][tym - M0][tx];
+      if constexpr (PFIX) {
+        double f[NV], t[2];
+        scaled_interface_flux_tmp<RS, NV, 1>(qL, qpy, P, A.dt, A.dx, A.rdx, DXPOW2, f, t);
+#pragma unroll
+        for (int n = 0; n < NV; n++) fy[n] = f[n];
+        fy[NV] = t[0]; fy[NV + 1] = t[1];
+      } else {
       scaled_interface_flux<RS, NV, 1, !MASK, NE>(qL, qpy, P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fy);
+      }
       if (MASK) {
         ok_ym = smask[((c + 3) % 3 * BY + tym) * BX + tx];
         const bool zy = ((okc | ok_ym) & CELL_REFINED) != 0;
 #pragma unroll
-        for (int n = 0; n < NV; n++) fy[n] = zy ? 0.0 : fy[n];
+        for (int n = 0; n < NF; n++) fy[n] = zy ? 0.0 : fy[n];
       }
       // the flux through this row's -y face is the +y face flux of row ty-1: into ITS slot
 #pragma unroll
-      for (int n = 0; n < NV; n++) M.v[n][tym - M0][tx] = fy[n];
+      for (int n = 0; n < NF; n++) M.v[n][tym - M0][tx] = fy[n];
     }
     if constexpr (r_fxz) {
       // plane c-1: its x part and own -y flux were kept in registers, the +y face flux was left
       // in this row's slot of the other buffer by row ty+1 before this iteration's barrier.
       // (The first two iterations of a chunk produce values from the not yet primed pipeline;
       // they are computed and dropped by the store's range check.)
-      double un[NV], fyh[NV];
+      double un[NF], fyh[NF];
 #pragma unroll
-      for (int n = 0; n < NV; n++) {
+      for (int n = 0; n < NF; n++) {
         fyh[n] = Mprev.v[n][ty - M0][tx];
         const double pxn = PARK ? park[n][ty - 2][tx] : partx[n];
-        const double fyn = PARK ? park[NV + n][ty - 2][tx] : fyown[n];
-        const double part = (LATE ? bcar[n] + pxn : pxn) + (fyn - fyh[n]);
+        const double fyn = PARK ? park[NF + n][ty - 2][tx] : fyown[n];
+        const double part = (LATE ? bcar[n < NV ? n : 0] + pxn : pxn) + (fyn - fyh[n]);
         un[n] = part + dz[n];
       }
       if (NV > 5 + NE && !MASK) {
@@ -598,8 +633,8 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
         for (int n = 5 + NE; n < NV; n++) sold[n - 5] = snew[n - 5];
       }
 #pragma unroll
-      for (int n = 0; n < NV; n++) {
-        if (PARK) { park[n][ty - 2][tx] = px[n]; park[NV + n][ty - 2][tx] = fy[n]; }
+      for (int n = 0; n < NF; n++) {
+        if (PARK) { park[n][ty - 2][tx] = px[n]; park[NF + n][ty - 2][tx] = fy[n]; }
         else { partx[n] = px[n]; fyown[n] = fy[n]; }
       }
       {
@@ -610,11 +645,12 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
           if (MASK) plane_store(unew + (long)(n & ~1) * A.pitch_var, pb + (n & 1) * odd_var, so, un[n]);
           else plane_store(unew + (long)n * A.pitch_var, pb, so, un[n]);
         }
+        if constexpr (PFIX) { plane_store(X.divu, pb, so, un[NV]); plane_store(X.enew, pb, so, un[NV + 1]); }
       }
       // LATE: the state the update of plane c starts from (MASK: unew, in place -- another array, an HBM miss; else the plane of
       // uold this workgroup read two iterations ago), requested now and used in phase B of the next iteration: at the top of
       // phase A it was due at the x flux, and every wave of the workgroup sat at that wait together
-      if (LATE) { if (MASK) load_base(c, bcar); else load_u(c, bcar); }
+      if constexpr (LATE) { if (MASK) load_base(c, bcar); else load_u(c, bcar); }
     }
     // rotate the ring
     if (RING == 3) { const int t = sa; sa = sb; sb = sc; sc = t; }
@@ -636,6 +672,29 @@ __global__ __launch_bounds__(BX *BY) void godunov_sweep_kernel(SweepArgs A) {
   else if (ty == BY - 2) sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_HIGH, MASK>(A, smem_raw);
   else sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_FULL, MASK>(A, smem_raw);
 }
+
+#ifndef RAMSES_AMD_FAST
+// pressure_fix on a level in tiles (strict arithmetic only: scaled_interface_flux_tmp): muscl, the 8-row layout of the
+// NV = 6, 7 kernels -- the two face quantities cost what two passive scalars cost -- or 6 rows where the LDS of 8 does not
+// hold them (NV = 7 with the 27-point slope's third ring plane).  A kernel of its own so that the symbols and the code of the
+// kernels without pressure_fix stay what they were.
+template <int ST, int NV>
+struct PfixRows {
+  static constexpr int BY = (ST == 3 && NV == 7) ? 6 : 8;
+};
+template <int ST, int RS, int BY, bool GRAV, int NV>
+__global__ __launch_bounds__(BX *BY) void godunov_sweep_pfix_kernel(SweepArgs A, SweepPfix X) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  static_assert(Lds<ST, BY, NV, true, GRAV, 2>::bytes <= 160 * 1024, "the pressure_fix sweep fits one workgroup's LDS");
+  const int ty = threadIdx.y;   // wave-uniform
+  if (ty >= 2 && ty <= BY - 3) __builtin_amdgcn_s_setprio(3);
+  if (ty == 0) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_HALO, true, 0, true>(A, smem_raw, X);
+  else if (ty == BY - 1) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_HALO_HI, true, 0, true>(A, smem_raw, X);
+  else if (ty == 1) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_LOW, true, 0, true>(A, smem_raw, X);
+  else if (ty == BY - 2) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_HIGH, true, 0, true>(A, smem_raw, X);
+  else sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_FULL, true, 0, true>(A, smem_raw, X);
+}
+#endif
 
 // NENER > 0 (the non-thermal energies in variables 5 .. 5+NE-1, passive scalars after them): the 8-row layout of the
 // passive-scalar kernels of the same NV, muscl, no gravity, the plain brick (no tiles).  A kernel of its own so that the
@@ -940,8 +999,9 @@ __device__ __forceinline__ long surf_cell(const SurfArgs &A, int x, int y, int z
 // converted (ctoprim), then the slopes and the two traces -- what a lane of the marching kernel does for its cell in phase A --
 // and the Riemann flux, scaled like the marching kernel's.
 // (slope type 3: the 3 x 3 x 3 neighbourhoods of the two cells -- 36 cells, four slabs of nine along DIR)
-template <int RS, int NV, bool GRAV, int SCHEME, int DIR>
-__device__ __forceinline__ void surf_interface27(const SurfArgs &A, const int (&lo)[3], double (&fl)[NV]) {
+// (NF = NV + 2: pressure_fix -- fl[NV], fl[NV + 1] = the face velocity and the internal-energy flux, scaled like the fluxes)
+template <int RS, int NV, bool GRAV, int SCHEME, int DIR, int NF = NV>
+__device__ __forceinline__ void surf_interface27(const SurfArgs &A, const int (&lo)[3], double (&fl)[NF]) {
   constexpr int T0 = DIR == 0 ? 1 : 0, T1 = DIR == 2 ? 1 : 2;
   long c[36];
 #pragma unroll
@@ -990,11 +1050,21 @@ __device__ __forceinline__ void surf_interface27(const SurfArgs &A, const int (&
 #pragma unroll
     for (int n = 0; n < NV; n++) { if (w == 0) qL[n] = qm[DIR][n]; else qR[n] = qp[DIR][n]; }
   }
+  if constexpr (NF == NV) {
   scaled_interface_flux<RS, NV, DIR, false>(qL, qR, A.P, A.dt, A.dx, A.rdx, dtdx, A.pow2 != 0, fl);   // (as the marching kernel of a level in tiles does)
+  } else {
+#ifndef RAMSES_AMD_FAST
+    double f[NV], t[2];
+    scaled_interface_flux_tmp<RS, NV, DIR>(qL, qR, A.P, A.dt, A.dx, A.rdx, A.pow2 != 0, f, t);
+#pragma unroll
+    for (int n = 0; n < NV; n++) fl[n] = f[n];
+    fl[NV] = t[0]; fl[NV + 1] = t[1];
+#endif
+  }
 }
-template <int ST, int RS, int NV, bool GRAV, int SCHEME, int DIR>
-__device__ __forceinline__ void surf_interface(const SurfArgs &A, const int (&lo)[3], double (&fl)[NV]) {
-  if constexpr (ST == 3) { surf_interface27<RS, NV, GRAV, SCHEME, DIR>(A, lo, fl); return; }
+template <int ST, int RS, int NV, bool GRAV, int SCHEME, int DIR, int NF = NV>
+__device__ __forceinline__ void surf_interface(const SurfArgs &A, const int (&lo)[3], double (&fl)[NF]) {
+  if constexpr (ST == 3) { surf_interface27<RS, NV, GRAV, SCHEME, DIR, NF>(A, lo, fl); return; }
   constexpr int T0 = DIR == 0 ? 1 : 0, T1 = DIR == 2 ? 1 : 2;
   long c[12];
   // 0..3: along DIR at lo-1, lo, hi, hi+1;  4..7: lo -T0, +T0, -T1, +T1;  8..11: the same of hi
@@ -1042,40 +1112,58 @@ __device__ __forceinline__ void surf_interface(const SurfArgs &A, const int (&lo
 #pragma unroll
     for (int n = 0; n < NV; n++) { if (w == 0) qL[n] = qm[DIR][n]; else qR[n] = qp[DIR][n]; }
   }
+  if constexpr (NF == NV) {
   scaled_interface_flux<RS, NV, DIR, false>(qL, qR, A.P, A.dt, A.dx, A.rdx, dtdx, A.pow2 != 0, fl);   // (as the marching kernel of a level in tiles does)
+  } else {
+#ifndef RAMSES_AMD_FAST
+    double f[NV], t[2];
+    scaled_interface_flux_tmp<RS, NV, DIR>(qL, qR, A.P, A.dt, A.dx, A.rdx, A.pow2 != 0, f, t);
+#pragma unroll
+    for (int n = 0; n < NV; n++) fl[n] = f[n];
+    fl[NV] = t[0]; fl[NV + 1] = t[1];
+#endif
+  }
 }
+// (NF = NV + 2: the records' last two slots are written too -- pressure_fix; NF = NV: they are neither written nor read)
+// (the body as a macro, not a function of its own: through a function the compiler commutes the operands of 27 additions of
+//  surface_flux_kernel -- harmless, but the kernels without pressure_fix are to stay the code they were, instruction for
+//  instruction.  Events arrive sorted by device oct and face -- round 6, session T: 2.59 -> 2.38 ms strict on the shell level
+//  against the (face, oct) order -- and the four fine faces of an event sit in neighbouring lanes.  The updated cell behind fine
+//  face q of face f (q: the two transverse coordinates, lower axis first), the ghost cell beyond the face, lo = the left cell of
+//  the interface; hydro/godunov_fine.f90:720-747: reset when the cell on either side is refined (a ghost cell never is))
+#define SURFACE_FLUX_BODY(SCHEME, NF) \
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x; \
+  if (t >= (long)A.nevent * 4) return; \
+  const int e = A.qminor ? (int)(t >> 2) : (int)(t % A.nevent), q = A.qminor ? (int)(t & 3) : (int)(t / A.nevent); \
+  const int ev = A.events[e]; \
+  const int io = ev / 6, f = ev % 6; \
+  const int dirn = f >> 1, side = f & 1; \
+  const long r = (long)A.ig[io] - A.base; \
+  const int tl = A.tileid[r / TILE_OCTS], l = (int)(r % TILE_OCTS); \
+  int p[3] = {2 * ((tl % A.ntx) * TILE_OX + l % TILE_OX), 2 * (((tl / A.ntx) % A.nty) * TILE_OY + (l / TILE_OX) % TILE_OY), \
+              2 * ((tl / (A.ntx * A.nty)) * TILE_OZ + l / (TILE_OX * TILE_OY))}; \
+  const int t0 = dirn == 0 ? 1 : 0, t1 = dirn == 2 ? 1 : 2; \
+  p[dirn] += side; p[t0] += q & 1; p[t1] += q >> 1; \
+  const bool zero = (A.stat[surf_cell(A, p[0], p[1], p[2])] & CELL_REFINED) != 0; \
+  int lo[3] = {p[0], p[1], p[2]}; \
+  if (!side) lo[dirn] -= 1; \
+  double fl[NF]; \
+  if (dirn == 0) surf_interface<ST, RS, NV, GRAV, SCHEME, 0, NF>(A, lo, fl); \
+  else if (dirn == 1) surf_interface<ST, RS, NV, GRAV, SCHEME, 1, NF>(A, lo, fl); \
+  else surf_interface<ST, RS, NV, GRAV, SCHEME, 2, NF>(A, lo, fl); \
+  double *dst = A.rec + ((long)e * 4 + q) * (NV + 2); \
+  _Pragma("unroll") for (int n = 0; n < NF; n++) dst[n] = zero ? 0.0 : fl[n];
 template <int ST, int RS, int NV, bool GRAV, int SCHEME = 0>
 __global__ __launch_bounds__(128) void surface_flux_kernel(SurfArgs A) {
-  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long)A.nevent * 4) return;
-  // (events arrive sorted by device oct and face -- round 6, session T: 2.59 -> 2.38 ms strict on the shell level against the
-  //  (face, oct) order with 64 events of one fine face per wave -- and the four fine faces of an event sit in neighbouring
-  //  lanes: an oct's records and the cells its faces read are touched by one wave)
-  const int e = A.qminor ? (int)(t >> 2) : (int)(t % A.nevent), q = A.qminor ? (int)(t & 3) : (int)(t / A.nevent);
-  const int ev = A.events[e];
-  const int io = ev / 6, f = ev % 6;
-  const int dirn = f >> 1, side = f & 1;
-  // the oct's position from its device index (its slab of 512 indices is one tile)
-  const long r = (long)A.ig[io] - A.base;
-  const int tl = A.tileid[r / TILE_OCTS], l = (int)(r % TILE_OCTS);
-  int p[3] = {2 * ((tl % A.ntx) * TILE_OX + l % TILE_OX), 2 * (((tl / A.ntx) % A.nty) * TILE_OY + (l / TILE_OX) % TILE_OY),
-              2 * ((tl / (A.ntx * A.nty)) * TILE_OZ + l / (TILE_OX * TILE_OY))};
-  // the updated cell behind fine face q of face f (q: the two transverse coordinates, lower axis first); the ghost cell is the
-  // one beyond the face; lo = the left cell of the interface
-  const int t0 = dirn == 0 ? 1 : 0, t1 = dirn == 2 ? 1 : 2;
-  p[dirn] += side; p[t0] += q & 1; p[t1] += q >> 1;
-  // hydro/godunov_fine.f90:720-747: reset when the cell on either side is refined (a ghost cell never is)
-  const bool zero = (A.stat[surf_cell(A, p[0], p[1], p[2])] & CELL_REFINED) != 0;
-  int lo[3] = {p[0], p[1], p[2]};
-  if (!side) lo[dirn] -= 1;
-  double fl[NV];
-  if (dirn == 0) surf_interface<ST, RS, NV, GRAV, SCHEME, 0>(A, lo, fl);
-  else if (dirn == 1) surf_interface<ST, RS, NV, GRAV, SCHEME, 1>(A, lo, fl);
-  else surf_interface<ST, RS, NV, GRAV, SCHEME, 2>(A, lo, fl);
-  double *dst = A.rec + ((long)e * 4 + q) * (NV + 2);
-#pragma unroll
-  for (int n = 0; n < NV; n++) dst[n] = zero ? 0.0 : fl[n];
+  SURFACE_FLUX_BODY(SCHEME, NV)
 }
+#ifndef RAMSES_AMD_FAST
+template <int ST, int RS, int NV, bool GRAV>
+__global__ __launch_bounds__(128) void surface_flux_pfix_kernel(SurfArgs A) {
+  SURFACE_FLUX_BODY(0, NV + 2)
+}
+#endif
+#undef SURFACE_FLUX_BODY
 
 template <int ST, int RS, int NV, int SCHEME = 0>
 static hipError_t surface2(const SurfArgs &A, bool grav, hipStream_t s) {
@@ -1114,16 +1202,60 @@ hipError_t surface0(const SurfArgs &A, int rs, int nvar, int scheme, bool grav, 
   }
   return hipErrorInvalidValue;
 }
+#ifndef RAMSES_AMD_FAST
+// pressure_fix: muscl, NVAR 5 .. 7, every solver
+template <int ST, int RS, int NV>
+static hipError_t surface_pfix2(const SurfArgs &A, bool grav, hipStream_t s) {
+  const dim3 grid((unsigned)(((long)A.nevent * 4 + 127) / 128)), block(128);
+  if (grav) hipLaunchKernelGGL((surface_flux_pfix_kernel<ST, RS, NV, true>), grid, block, 0, s, A);
+  else hipLaunchKernelGGL((surface_flux_pfix_kernel<ST, RS, NV, false>), grid, block, 0, s, A);
+  return hipGetLastError();
+}
+template <int ST, int RS>
+static hipError_t surface_pfix1(const SurfArgs &A, int nvar, bool grav, hipStream_t s) {
+  if constexpr (ST == 4 || ST == 5 || ST == 6) {
+    return hipErrorInvalidValue;
+  } else {
+    if (nvar == 5) return surface_pfix2<ST, RS, 5>(A, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    if (nvar == 6) return surface_pfix2<ST, RS, 6>(A, grav, s);
+    if (nvar == 7) return surface_pfix2<ST, RS, 7>(A, grav, s);
+#endif
+    return hipErrorInvalidValue;
+  }
+}
+template <int ST>
+hipError_t surface0_pfix(const SurfArgs &A, int rs, int nvar, bool grav, hipStream_t s) {
+  switch (rs) {
+    case RIEMANN_LLF: return surface_pfix1<ST, RIEMANN_LLF>(A, nvar, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case RIEMANN_HLLC: return surface_pfix1<ST, RIEMANN_HLLC>(A, nvar, grav, s);
+    case RIEMANN_HLL: return surface_pfix1<ST, RIEMANN_HLL>(A, nvar, grav, s);
+    case RIEMANN_ACOUSTIC: return surface_pfix1<ST, RIEMANN_ACOUSTIC>(A, nvar, grav, s);
+    case RIEMANN_EXACT: return surface_pfix1<ST, RIEMANN_EXACT>(A, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+#endif
 // One translation unit per slope type (ramses_amd/build.py compiles this file once without SWEEP_ST -- the dispatchers -- and once
 // per slope type with -DSWEEP_ST=<type>, 3 standing for 3, 4, 5 and 6, for each arithmetic: the instantiations of the option
 // matrix build side by side instead of in two nine-minute compiles; the variant builds of scripts/build_variant.sh --
 // SWEEP_FLAGSHIP_ONLY -- keep one unit)
 #if defined(SWEEP_ST)
 template hipError_t surface0<SWEEP_ST>(const SurfArgs &, int, int, int, bool, hipStream_t);
+#ifndef RAMSES_AMD_FAST
+template hipError_t surface0_pfix<SWEEP_ST>(const SurfArgs &, int, int, bool, hipStream_t);
+#endif
 #elif !defined(SWEEP_FLAGSHIP_ONLY)
 #define SWEEP_EXTERN_ST(K) extern template hipError_t surface0<K>(const SurfArgs &, int, int, int, bool, hipStream_t);
 SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
 #undef SWEEP_EXTERN_ST
+#ifndef RAMSES_AMD_FAST
+#define SWEEP_EXTERN_ST(K) extern template hipError_t surface0_pfix<K>(const SurfArgs &, int, int, bool, hipStream_t);
+SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
+#undef SWEEP_EXTERN_ST
+#endif
 #endif
 #ifndef SWEEP_ST
 hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, int nvar, int scheme, bool grav, hipStream_t s) {
@@ -1140,6 +1272,22 @@ hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, i
   }
   return hipErrorInvalidValue;
 }
+#ifndef RAMSES_AMD_FAST
+hipError_t launch_surface_flux_pfix(const SurfArgs &A, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
+  if (A.nevent <= 0) return hipSuccess;
+  switch (slope_type) {
+    case 1: return surface0_pfix<1>(A, riemann, nvar, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case 0: return surface0_pfix<0>(A, riemann, nvar, grav, s);
+    case 2: return surface0_pfix<2>(A, riemann, nvar, grav, s);
+    case 3: return surface0_pfix<3>(A, riemann, nvar, grav, s);
+    case 7: return surface0_pfix<7>(A, riemann, nvar, grav, s);
+    case 8: return surface0_pfix<8>(A, riemann, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+#endif
 #endif   // SWEEP_ST
 
 // ---------------------------------------------------------------------------
@@ -1262,6 +1410,50 @@ static hipError_t launch1(SweepArgs &A, int by, int scheme, int nvar, bool grav,
     return hipErrorInvalidValue;
   }
 }
+
+#ifndef RAMSES_AMD_FAST
+// pressure_fix on a level in tiles: one workgroup per work item of the plan (cut for tile_sweep_rows_pfix interior rows)
+template <int ST, int RS, bool GRAV, int NV>
+static hipError_t launch_pfix3(const SweepArgs &A, const SweepPfix &X, hipStream_t s) {
+  constexpr int BY = PfixRows<ST, NV>::BY;
+  const size_t lds = Lds<ST, BY, NV, true, GRAV, 2>::bytes;
+  auto k = godunov_sweep_pfix_kernel<ST, RS, BY, GRAV, NV>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(A.nblocks), dim3(BX, BY), lds, s, A, X);
+  return hipGetLastError();
+}
+template <int ST, int RS>
+static hipError_t launch_pfix1(SweepArgs &A, const SweepPfix &X, int nvar, bool grav, hipStream_t s) {
+  if constexpr (ST == 4 || ST == 5 || ST == 6) {
+    return hipErrorInvalidValue;
+  } else {
+    if (!A.stat || !A.dir || !A.work || !X.divu || !X.enew || A.ng != 0 || A.nwork <= 0) return hipErrorInvalidValue;
+    A.nblocks = A.nwork;
+    A.nbox = 1;          // (the box decode runs, its result is replaced by the work item)
+    A.box[0] = SweepBox{0, 1, 0, 1, 0, A.nz, A.nz, 0};
+    if (nvar == 5) return grav ? launch_pfix3<ST, RS, true, 5>(A, X, s) : launch_pfix3<ST, RS, false, 5>(A, X, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    if (nvar == 6) return grav ? launch_pfix3<ST, RS, true, 6>(A, X, s) : launch_pfix3<ST, RS, false, 6>(A, X, s);
+    if (nvar == 7) return grav ? launch_pfix3<ST, RS, true, 7>(A, X, s) : launch_pfix3<ST, RS, false, 7>(A, X, s);
+#endif
+    return hipErrorInvalidValue;
+  }
+}
+template <int ST>
+hipError_t launch0_pfix(SweepArgs &A, const SweepPfix &X, int rs, int nvar, bool grav, hipStream_t s) {
+  switch (rs) {
+    case RIEMANN_LLF: return launch_pfix1<ST, RIEMANN_LLF>(A, X, nvar, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case RIEMANN_HLLC: return launch_pfix1<ST, RIEMANN_HLLC>(A, X, nvar, grav, s);
+    case RIEMANN_HLL: return launch_pfix1<ST, RIEMANN_HLL>(A, X, nvar, grav, s);
+    case RIEMANN_ACOUSTIC: return launch_pfix1<ST, RIEMANN_ACOUSTIC>(A, X, nvar, grav, s);
+    case RIEMANN_EXACT: return launch_pfix1<ST, RIEMANN_EXACT>(A, X, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+#endif
 
 // NENER > 0: (NE, NV) = (1, 6), (1, 7) [one passive scalar], (2, 7); LLF, HLL, HLLC; muscl, no gravity, the plain brick
 template <int ST, int RS, int NV, int NE>
@@ -1388,6 +1580,9 @@ hipError_t launch0(SweepArgs &A, int rs, int by, int scheme, int nvar, bool grav
 template hipError_t launch0<SWEEP_ST>(SweepArgs &, int, int, int, int, bool, hipStream_t);
 template hipError_t launch0_nener<SWEEP_ST>(SweepArgs &, int, int, int, hipStream_t);
 template hipError_t launch0_scalar<SWEEP_ST>(SweepArgs &, int, int, int, int, bool, hipStream_t);
+#ifndef RAMSES_AMD_FAST
+template hipError_t launch0_pfix<SWEEP_ST>(SweepArgs &, const SweepPfix &, int, int, bool, hipStream_t);
+#endif
 #if SWEEP_ST == 3
 template hipError_t launch0<4>(SweepArgs &, int, int, int, int, bool, hipStream_t);
 template hipError_t launch0<5>(SweepArgs &, int, int, int, int, bool, hipStream_t);
@@ -1404,6 +1599,11 @@ SWEEP_EXTERN_NENER(0) SWEEP_EXTERN_NENER(1) SWEEP_EXTERN_NENER(2) SWEEP_EXTERN_N
 #define SWEEP_EXTERN_SCALAR(K) extern template hipError_t launch0_scalar<K>(SweepArgs &, int, int, int, int, bool, hipStream_t);
 SWEEP_EXTERN_SCALAR(0) SWEEP_EXTERN_SCALAR(1) SWEEP_EXTERN_SCALAR(2) SWEEP_EXTERN_SCALAR(3) SWEEP_EXTERN_SCALAR(7) SWEEP_EXTERN_SCALAR(8)
 #undef SWEEP_EXTERN_SCALAR
+#ifndef RAMSES_AMD_FAST
+#define SWEEP_EXTERN_PFIX(K) extern template hipError_t launch0_pfix<K>(SweepArgs &, const SweepPfix &, int, int, bool, hipStream_t);
+SWEEP_EXTERN_PFIX(0) SWEEP_EXTERN_PFIX(1) SWEEP_EXTERN_PFIX(2) SWEEP_EXTERN_PFIX(3) SWEEP_EXTERN_PFIX(7) SWEEP_EXTERN_PFIX(8)
+#undef SWEEP_EXTERN_PFIX
+#endif
 #endif
 
 #ifndef SWEEP_ST
@@ -1432,6 +1632,26 @@ hipError_t launch_godunov_sweep(SweepArgs &A, int slope_type, int riemann, int b
   }
   return hipErrorInvalidValue;
 }
+
+#ifndef RAMSES_AMD_FAST
+// interior rows of a work item of the pressure_fix sweep of a level in tiles
+int tile_sweep_rows_pfix(int nvar, int slope_type) { return ((slope_type == 3 && nvar == 7) ? 6 : 8) - 4; }
+
+hipError_t launch_godunov_sweep_pfix(SweepArgs &A, const SweepPfix &X, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
+  if ((unsigned long)A.pitch_var * 8ul >= (1ul << 31)) return hipErrorInvalidValue;      // lane offsets into a cell vector
+  switch (slope_type) {
+    case 1: return launch0_pfix<1>(A, X, riemann, nvar, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case 0: return launch0_pfix<0>(A, X, riemann, nvar, grav, s);
+    case 2: return launch0_pfix<2>(A, X, riemann, nvar, grav, s);
+    case 3: return launch0_pfix<3>(A, X, riemann, nvar, grav, s);
+    case 7: return launch0_pfix<7>(A, X, riemann, nvar, grav, s);
+    case 8: return launch0_pfix<8>(A, X, riemann, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+#endif
 
 hipError_t launch_godunov_sweep_nener(SweepArgs &A, int slope_type, int riemann, int nvar, int nener, hipStream_t s) {
   if ((unsigned long)A.pitch_z * 8ul >= (1ul << 31) || (unsigned long)A.pitch_var * 8ul >= (1ul << 32))

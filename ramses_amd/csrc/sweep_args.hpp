@@ -54,6 +54,13 @@ struct SweepArgs {
   HydroConst P;
 };
 
+// pressure_fix on a level in tiles (launch_godunov_sweep_pfix): the device's divu / enew cell vectors, read-modify-written for
+// exactly the cells whose unew is stored (hydro/godunov_fine.f90:752-790).  Beside SweepArgs, not inside: the kernels without
+// pressure_fix keep their argument block (and the place of the hidden arguments behind it) byte for byte.
+struct SweepPfix {
+  double *divu = nullptr, *enew = nullptr;
+};
+
 // The surface pass of the sweep of a level in tiles (hydro/godunov_fine.f90:798-908): the fluxes an updated cell exchanges with
 // a GHOST cell (an oct the level does not have, interpolated by the pre-pass) are owed to the leaf cell of the coarser level
 // behind that oct face.  One thread per (event = (oct of the list, face) with such a neighbour, fine face q): it rebuilds the
@@ -87,6 +94,11 @@ hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, i
 hipError_t launch_godunov_sweep(SweepArgs &A, int slope_type, int riemann, int by, int scheme, int nvar,
                                 bool grav, hipStream_t s);
 int tile_sweep_rows(int riemann, int nvar, int slope_type, int scheme);
+// pressure_fix on a level in tiles: strict arithmetic only (scaled_interface_flux_tmp), muscl, NVAR 5 .. 7, slope types 0 - 3, 7, 8.
+// The surface pass writes all nvar + 2 slots of a record; the marching kernel updates X.divu / X.enew beside A.unew.
+hipError_t launch_surface_flux_pfix(const SurfArgs &A, int slope_type, int riemann, int nvar, bool grav, hipStream_t s);
+hipError_t launch_godunov_sweep_pfix(SweepArgs &A, const SweepPfix &X, int slope_type, int riemann, int nvar, bool grav, hipStream_t s);
+int tile_sweep_rows_pfix(int nvar, int slope_type);
 }
 namespace fastmode {
 // NENER = nener (1, 2) non-thermal energies, the plain brick, muscl, no gravity

@@ -864,6 +864,13 @@ module ramses_amd_cabi
        real(c_double), value :: dt, dx_loc, beta_fix, hexp
        integer(c_int) :: rc
      end function ramses_amd_amrres_set_uold_pfix
+     function ramses_amd_amrres_sync_pfix(ngrid, igrid, divu, enew) bind(C, name='ramses_amd_amrres_sync_pfix') result(rc)
+       import :: c_int, c_double
+       integer(c_int), value :: ngrid
+       integer(c_int) :: igrid(*)
+       real(c_double) :: divu(*), enew(*)
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_sync_pfix
      function ramses_amd_amrres_courant(p, ngrid, igrid, dx, dt_in, out4) bind(C, name='ramses_amd_amrres_courant') result(rc)
        import :: ramses_amd_hydro_params, c_int, c_double
        type(ramses_amd_hydro_params), intent(in) :: p

@@ -1367,6 +1367,8 @@ contains
        if (myid == 1) then
           if (p%fast_math == 1) then
              write(*,*) 'ramses_amd: dense sweep arithmetic = fast (<= 1e-12 of the reference; RAMSES_AMD_STRICT=1: bit-identical)'
+             ! (divu / enew ride through the dense sweep in the reference's operation order only: csrc/capi_amr.hip tile_level_sweep)
+             if (pressure_fix) write(*,*) 'ramses_amd: pressure_fix: AMR levels in tiles are swept in strict arithmetic (bit-identical)'
           else
              write(*,*) 'ramses_amd: dense sweep arithmetic = strict (bit-identical to the reference)'
           end if

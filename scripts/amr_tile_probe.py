@@ -1,4 +1,8 @@
-"""ramses_amd_amrres_godunov of a level in tiles, for rocprofv3 --kernel-trace --stats:  python scripts/amr_tile_probe.py [level] [kind] [steps]"""
+"""ramses_amd_amrres_godunov of a level in tiles, for rocprofv3 --kernel-trace --stats:  python scripts/amr_tile_probe.py [level] [kind] [steps]
+--pfix (anywhere on the line): the same level with pressure_fix, through a loop of its own over the public calls (bench.py knows
+nothing of pressure_fix); kinds "covered" and "shell" (= bench.py's "partial"); RAMSES_AMD_TILE_SWEEP=0 selects the tree-walking
+sweep for the comparison, RAMSES_AMD_PROBE_PFIX=0 times the same loop without pressure_fix."""
+import ctypes as C
 import json
 import os
 import sys
@@ -6,12 +10,82 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
+
+def pfix_probe(level, kind, steps, riemann="llf"):
+    """level `level` complete with level + 1 in a spherical shell ("covered"), or level `level` in a spherical shell over a
+    complete level - 1 ("shell"): trees as bench.amr_resident_bench builds them; HIP events around ramses_amd_amrres_godunov"""
+    import numpy as np
+    import torch
+    import ramses_amd
+    from ramses_amd import ic
+    from ramses_amd._capi import check, lib
+    Lfull = level - 1 if kind == "shell" else level
+    n = 2 ** Lfull
+    z, y, x = np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing="ij")
+    r = np.sqrt((x - n / 2 + 0.5) ** 2 + (y - n / 2 + 0.5) ** 2 + (z - n / 2 + 0.5) ** 2)
+    mask = (r >= 0.23 * n) & (r <= 0.36 * n)
+    del x, y, z, r
+    T = ic.uniform_tree(Lfull, order="morton", refine_mask=mask, slack=int(1.6 * mask.sum()) + 4096)
+    igrid = np.ascontiguousarray(T["igrid_fine"] if kind == "shell" else T["igrid"])
+    lists = [np.ascontiguousarray(T["igrid"]), np.ascontiguousarray(T["igrid_fine"])]
+    ncells = 8 * len(igrid)
+    dx = 0.5 / 2 ** level
+    u = np.zeros((5, T["ncell"]))
+    u[0] = 1.0
+    u[4] = 1e-5 / 0.4
+    u[4, T["ncoarse"] + int(igrid[0]) - 1] = (1e-5 + 0.4 * 0.125 / dx ** 3) / 0.4
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    L = lib()
+    pfix = os.environ.get("RAMSES_AMD_PROBE_PFIX", "1") != "0"
+    os.environ.setdefault("RAMSES_AMD_TILE_MIN_OCTS", "0")
+    p = ramses_amd.make_params(courant_factor=0.8, riemann=riemann)
+    check(L.ramses_amd_amrres_invalidate())
+    check(L.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], vp(u), vp(T["son"]), vp(T["nbor"]), vp(T["father"])))
+    if pfix:
+        check(L.ramses_amd_amrres_enable_pfix())
+    t0, w0 = L.ramses_amd_amrres_tile_sweeps(), L.ramses_amd_amrres_tree_sweeps()
+
+    def set_unew():
+        for ig in lists:
+            if pfix:
+                check(L.ramses_amd_amrres_set_unew_pfix(C.byref(p), len(ig), vp(ig)))
+            else:
+                check(L.ramses_amd_amrres_set_unew(len(ig), vp(ig)))
+
+    def sweep():
+        check(L.ramses_amd_amrres_godunov(C.byref(p), level, len(igrid), vp(igrid), dx, 1e-6, 32, 0, 1))
+    for _ in range(2):
+        set_unew()
+        sweep()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(steps):
+        set_unew()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        sweep()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b))
+    out = {"pressure_fix": pfix, "level": level, "kind": kind, "riemann": riemann, "cells": ncells,
+           "ms_per_sweep": sorted(times)[len(times) // 2], "ms_all": [round(t, 4) for t in times],
+           "tile_sweeps": int(L.ramses_amd_amrres_tile_sweeps() - t0), "tree_sweeps": int(L.ramses_amd_amrres_tree_sweeps() - w0),
+           "levels_in_tiles": int(L.ramses_amd_amrres_tiled_levels())}
+    check(L.ramses_amd_amrres_invalidate())
+    return out
+
+
 if __name__ == "__main__":
-    level = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-    kind = sys.argv[2] if len(sys.argv) > 2 else "covered"
-    steps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
+    args = [a for a in sys.argv[1:] if a != "--pfix"]
+    level = int(args[0]) if len(args) > 0 else 8
+    kind = args[1] if len(args) > 1 else "covered"
+    steps = int(args[2]) if len(args) > 2 else 5
     import torch
     torch.cuda.init()
-    out = bench.amr_resident_bench(level, steps=steps, kind=kind)
-    print(json.dumps({k: out[k] for k in ("ms_per_sweep", "tree_walking_ms_per_sweep", "cells", "workload")}))
-    print("frac", out["roofline"]["frac"])
+    if "--pfix" in sys.argv[1:]:
+        print(json.dumps(pfix_probe(level, {"partial": "shell"}.get(kind, kind), steps, os.environ.get("RAMSES_AMD_BENCH_AMR_RIEMANN", "llf"))))
+    else:
+        out = bench.amr_resident_bench(level, steps=steps, kind=kind)
+        print(json.dumps({k: out[k] for k in ("ms_per_sweep", "tree_walking_ms_per_sweep", "cells", "workload")}))
+        print("frac", out["roofline"]["frac"])
