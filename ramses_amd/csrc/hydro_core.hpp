@@ -94,11 +94,13 @@ RA_DEV double dsqrt(double x) { return __builtin_sqrt(x); }
 // q = (rho,u,v,w,P [, non-thermal pressures (gamma_rad-1)*e] [,s])
 // The sound speed is not produced: only scheme='plmde' reads it (NE = 0 only).
 // ---------------------------------------------------------------------------
+// (rinv_out: the cell's 1 / rho as computed here, for a caller that traces the same cell later -- trace3d_cell's rinv_in)
 template <int NV, bool GRAV, int NE = 0>
 RA_DEV void ctoprim_cell(const double (&u)[NV], const double (&g)[3],
-                         double dtxhalf, const HydroConst &P, double (&q)[NV]) {
+                         double dtxhalf, const HydroConst &P, double (&q)[NV], double *rinv_out = nullptr) {
   const double rho = dmaxd(u[0], P.smallr);
   const double oneoverrho = ddiv(1.0, rho);
+  if (rinv_out) *rinv_out = oneoverrho;
   const double vx = u[1] * oneoverrho;
   const double vy = u[2] * oneoverrho;
   const double vz = u[3] * oneoverrho;
@@ -267,11 +269,13 @@ RA_DEV void slope3_var(const double (&nb)[27], double (&d)[3]) {
 // NE > 0: the non-thermal pressures e (q[5..5+NE)) -- their gradients push the
 // velocities, e is advected and compressed with gamma_rad (umuscl.f90:583-593).
 // ---------------------------------------------------------------------------
+// (fast build, rinv_in: ctoprim_cell's 1 / rho of this same cell -- ddiv(1, rho) = 1 * rcp_fast(rho), the bits of the rcp_fast(r)
+// it replaces -- where the caller has kept it)
 template <int NV, int NE = 0>
 RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
                          double dtdx, double dtdy, double dtdz,
                          const HydroConst &P, double (&qm)[3][NV],
-                         double (&qp)[3][NV]) {
+                         double (&qp)[3][NV], const double *rinv_in = nullptr) {
   const double r = q[0], u = q[1], v = q[2], w = q[3], p = q[4];
   const double drx = dq[0][0], dux = dq[0][1], dvx = dq[0][2], dwx = dq[0][3], dpx = dq[0][4];
   const double dry = dq[1][0], duy = dq[1][1], dvy = dq[1][2], dwy = dq[1][3], dpy = dq[1][4];
@@ -279,7 +283,7 @@ RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
   const double div = dux + dvy + dwz;
 #ifdef RAMSES_AMD_FAST
   // s = -(u dq/dx + v dq/dy + w dq/dz + source) as explicit FMA chains
-  const double rinv = rcp_fast(r);
+  const double rinv = rinv_in ? *rinv_in : rcp_fast(r);
   auto adv = [&](double ax, double ay, double az, double c0, double c1) {
     double t = u * ax;
     t = __builtin_fma(v, ay, t);
@@ -861,14 +865,17 @@ RA_DEV double rsqrt_fast(double x) {
   const double e = __builtin_fma(-(x * y), y, 1.0);
   return __builtin_fma(0.5 * y, e, y);
 }
-template <int DIR>
+// FLOORED: both states come out of trace3d_cell, which has just replaced a face density below smallr by the cell's own -- at
+// least smallr out of ctoprim_cell -- so max(rho, smallr) is rho itself and is not taken again (a density that is not a
+// number would pass where the max replaced it by smallr; ctoprim_cell's own max keeps the cell's finite)
+template <int DIR, bool FLOORED = false>
 RA_DEV void llf_flux_fast(const double (&qL)[5], const double (&qR)[5],
                           const HydroConst &P, double dtdx, double (&flux)[5]) {
   constexpr int ln = DIR == 0 ? 1 : (DIR == 1 ? 2 : 3);
   constexpr int lt1 = DIR == 0 ? 2 : 1;
   constexpr int lt2 = DIR == 2 ? 2 : 3;
-  const double rl = dmaxd(qL[0], P.smallr), pl = dmaxd(qL[4], rl * P.smallp);
-  const double rr = dmaxd(qR[0], P.smallr), pr = dmaxd(qR[4], rr * P.smallp);
+  const double rl = FLOORED ? qL[0] : dmaxd(qL[0], P.smallr), pl = dmaxd(qL[4], rl * P.smallp);
+  const double rr = FLOORED ? qR[0] : dmaxd(qR[0], P.smallr), pr = dmaxd(qR[4], rr * P.smallp);
   const double gl = P.gamma * pl, gr = P.gamma * pr;
   const double cl = gl * rsqrt_fast(gl * rl);   // sqrt(gamma p / rho)
   const double cr = gr * rsqrt_fast(gr * rr);
@@ -949,13 +956,14 @@ RA_DEV void hllc_flux_fast(const double (&qL)[5], const double (&qR)[5],
 // FUSE_HLLC = false: the sweep of a level in tiles and its surface pass (which must agree with each other flux by flux) take
 // the generic HLLC routine -- their kernels carry the tile bookkeeping on top and the fused flux's live values spill there:
 // 256^3 level in tiles 1.005 ms fused, 0.830 ms generic; shell level 2.40 / 1.98 ms (profiles/r06_hllc_fast.txt)
-template <int RS, int NV, int DIR, bool FUSE_HLLC = true, int NE = 0>
+// (FLOORED: llf_flux_fast's -- the densities of both states are known to be at least smallr)
+template <int RS, int NV, int DIR, bool FUSE_HLLC = true, int NE = 0, bool FLOORED = false>
 RA_DEV void scaled_interface_flux(const double (&qL)[NV], const double (&qR)[NV],
                                   const HydroConst &P, double dt, double dx, double rdx,
                                   double dtdx, bool DXPOW2, double (&flux)[NV]) {
 #ifdef RAMSES_AMD_FAST
   if constexpr (RS == RIEMANN_LLF && NV == 5) {
-    llf_flux_fast<DIR>(qL, qR, P, dtdx, flux);
+    llf_flux_fast<DIR, FLOORED>(qL, qR, P, dtdx, flux);
     return;
   }
 #ifndef RAMSES_AMD_HLLC_FUSED

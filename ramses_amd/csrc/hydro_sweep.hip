@@ -56,7 +56,8 @@ struct Plane {
 // then hold the rows that use them (1 .. BY-2) only.
 // (NX: components that ride beside the NV fluxes through the y slots and the parked partial update -- the two face quantities
 // of pressure_fix)
-template <int ST, int BY, int NV, bool MASK, bool GRAV, int NX = 0>
+// (DUTY: the two slot planes of one row -- y_duty below -- through which row 2 hands its -y face to the wave of row 0)
+template <int ST, int BY, int NV, bool MASK, bool GRAV, int NX = 0, bool DUTY = false>
 struct Lds {
   static constexpr int NF = NV + NX;
   static constexpr int RING = (ST == 3) ? 3 : 2;
@@ -73,7 +74,8 @@ struct Lds {
   static constexpr size_t q_off = 0;
   static constexpr size_t m_off = q_off + RING * sizeof(Plane<BY, NV>);
   static constexpr size_t park_off = m_off + 2 * sizeof(Plane<MR, NF>);
-  static constexpr size_t mask_off = park_off + (PARK ? sizeof(double) * 2 * NF * (BY - 4) * BX : 0);   // MASK: [3][BY][BX] status bytes
+  static constexpr size_t duty_off = park_off + (PARK ? sizeof(double) * 2 * NF * (BY - 4) * BX : 0);   // DUTY: [2][NF][BX], by plane parity
+  static constexpr size_t mask_off = duty_off + (DUTY ? sizeof(double) * 2 * NF * BX : 0);   // MASK: [3][BY][BX] status bytes
   static constexpr size_t sloc_off = mask_off + (MASK ? 3 * BY * BX : 0);                                // MASK: [BY][BX] lane part of the cell index
   static constexpr size_t bytes = sloc_off + (MASK ? 4 * BY * BX : 0);
 };
@@ -102,9 +104,60 @@ __device__ __forceinline__ double wave_shl1(double v) {
 //   ROLE_FULL    : rows 2..BY-3 everything, and the update
 //   ROLE_HIGH    : row BY-2     + slopes, the y flux through its -y face (the +y face flux of row BY-3)
 //   ROLE_HALO_HI : row BY-1     primitives only
-enum { ROLE_HALO = 0, ROLE_LOW = 1, ROLE_HIGH = 2, ROLE_FULL = 3, ROLE_HALO_HI = 4 };
-// (Handing row BY-2's y flux to the otherwise idle wave of row BY-1 paid with two barriers per plane only; with one
-// barrier it costs in both builds -- measured, profiles/r02_ab_sweep.txt -- and is gone.)
+//   ROLE_FULL_LO : row 2 where the y fluxes are shared out (SWEEP_YDUTY): a full row whose -y face flux another wave computes
+enum { ROLE_HALO = 0, ROLE_LOW = 1, ROLE_HIGH = 2, ROLE_FULL = 3, ROLE_HALO_HI = 4, ROLE_FULL_LO = 5 };
+
+// Who computes which y flux: an A/B knob, OFF (measured, and slower: below).  The hardware deals the 12 waves of a workgroup
+// round the four SIMDs, rows r, r+4 and r+8 together (profiles/r07_sweep_balance.txt), so every SIMD holds two full rows, one
+// of them row BY-2 -- slopes, trace and a y flux, half a full row -- on top, and two of them a halo row, which converts a plane
+// and waits at the barrier for 70 - 95 % of it.  The flux through a y face needs nothing its row keeps in registers but the
+// row's -y traced state, and both its inputs and its result already cross waves through the slots, so WHICH wave computes it
+// is a table:
+//   face f (between rows f-1 and f), f = 2 .. BY-2  ->  wave yflux_wave(f)
+// With SWEEP_YDUTY=1 face 2 goes to the wave of row 0 and face BY-2 to the wave of row BY-1.  A row that hands its -y face
+// away writes its -y state to a slot before the barrier -- row BY-2 into its own +y slot, which nobody reads; row 2 into a
+// slot pair of its own, Lds::duty_off -- the computing wave reads both states after the barrier, calls the same flux routine
+// on the same values and leaves the result where the rows beside the face read it after the NEXT barrier: face BY-2 in row
+// BY-3's slot as before, face 2 over row 2's -y state (row 1 takes no flux).  Every slot is rewritten only by the wave that
+// last read it, or a barrier later: still ONE barrier per plane, the same bits (tests/test_sweep_rebalance_gpu.py).
+// Measured at 512^3, five alternating runs each: 2.975 -> 3.136 ms with the duties shared out (2.939 -> 3.088 with the trims
+// below) although the busiest SIMD issues 7 % fewer VALU instructions per plane: rows 6 and 8, which close the barrier
+// with or without it, take 17 - 23 % longer from the barrier to the loop end once a flux is computed beside them.
+// (Round 2 found the same with face BY-2 alone on a much earlier kernel, profiles/r02_ab_sweep.txt.)
+#ifndef SWEEP_YDUTY
+#define SWEEP_YDUTY 0
+#endif
+template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, bool MASK, int NE = 0, bool PFIX = false>
+constexpr bool y_duty() {
+  return SWEEP_YDUTY && SWEEP_PARK_PLAIN && RS == RIEMANN_LLF && BY == 12 && ST != 3 && !GRAV && SCHEME == 0 && NV == 5 && !MASK && NE == 0 && !PFIX;
+}
+template <int BY, bool DUTY>
+constexpr int yflux_wave(int f) { return !DUTY ? f : (f == 2 ? 0 : (f == BY - 2 ? BY - 1 : f)); }
+
+// The trims of the full rows' instruction stream (fast build, muscl): the interface fluxes skip the density floor of states
+// that trace3d_cell has floored already (hydro_core.hpp llf_flux_fast FLOORED), and the trace takes 1 / rho from the
+// ctoprim_cell of the same cell one iteration earlier instead of a second v_rcp_f64 + Newton step: 503 -> 489 VALU
+// instructions per plane of a full row (12 v_max_f64, one v_rcp_f64, two FMAs less, one copy more), 154 VGPRs as before, same
+// bits; 512^3 LLF + minmod 2.975 -> 2.939 ms (medians of five alternating runs, profiles/r07_sweep_balance.txt).
+#ifndef SWEEP_TRIM
+#ifdef RAMSES_AMD_FAST
+#define SWEEP_TRIM 1
+#else
+#define SWEEP_TRIM 0
+#endif
+#endif
+
+// SWEEP_CYCLE_PROBE=1 (a build of its own, never the shipped one: with 0 nothing of it is compiled): every wave sums, per
+// plane, the shader clocks from the loop top to the barrier, inside the barrier and from the barrier to the loop end, and
+// lane 0 leaves the sums with the wave's row and its HW_ID register (SIMD: bits 5:4) per (block, row) after the march;
+// scripts/sweep_probe.py --balance reads them back through ramses_amd_sweep_cycle_probe.
+#ifndef SWEEP_CYCLE_PROBE
+#define SWEEP_CYCLE_PROBE 0
+#endif
+#if SWEEP_CYCLE_PROBE
+constexpr int PROBE_BLOCKS = 8192, PROBE_ROWS = 12, PROBE_WORDS = 6;
+static __device__ unsigned long long sweep_cycle_probe[PROBE_BLOCKS][PROBE_ROWS][PROBE_WORDS];
+#endif
 
 // Raw buffer access: one scalar resource descriptor per variable (base of the
 // variable's brick), a wave-uniform byte offset of the plane (soffset) and one
@@ -154,13 +207,16 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
   static_assert(!PFIX || (MASK && NE == 0 && SCHEME == 0), "pressure_fix: the sweep of a level in tiles, muscl");
   constexpr int NF = NV + (PFIX ? 2 : 0);   // components differenced
   const bool DXPOW2 = A.pow2 != 0;   // uniform
-  typedef Lds<ST, BY, NV, MASK, GRAV, NF - NV> L;
+  constexpr bool DUTY = y_duty<ST, RS, BY, GRAV, SCHEME, NV, MASK, NE, PFIX>();
+  static_assert(DUTY || ROLE != ROLE_FULL_LO, "row 2 is a full row like the others unless the y fluxes are shared out");
+  typedef Lds<ST, BY, NV, MASK, GRAV, NF - NV, DUTY> L;
   constexpr int RING = L::RING;
   constexpr bool PARK = L::PARK;
   constexpr int M0 = L::M0;
   Plane<BY, NV> *qring = reinterpret_cast<Plane<BY, NV> *>(smem_raw + L::q_off);  // [RING] primitives of planes c-1, c (, c+1)
   Plane<L::MR, NF> *mring = reinterpret_cast<Plane<L::MR, NF> *>(smem_raw + L::m_off);   // [2] +y traced state / y flux slots, by plane parity
   double (*park)[BY - 4][BX] = reinterpret_cast<double (*)[BY - 4][BX]>(smem_raw + L::park_off);   // PARK: [2 NF] of the full rows
+  double (*yduty)[NF][BX] = reinterpret_cast<double (*)[NF][BX]>(smem_raw + L::duty_off);           // DUTY: [2] row 2's -y state / -y flux, by plane parity
 
   const int tx = threadIdx.x, ty = threadIdx.y;
   const HydroConst &P = A.P;
@@ -279,8 +335,17 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #else
   constexpr bool KEEP = false;
 #endif
-  constexpr bool r_trace = ROLE == ROLE_LOW || ROLE == ROLE_HIGH || ROLE == ROLE_FULL;
-  constexpr bool r_fxz = ROLE == ROLE_FULL;
+  constexpr bool r_fxz = ROLE == ROLE_FULL || ROLE == ROLE_FULL_LO;
+  constexpr bool r_trace = ROLE == ROLE_LOW || ROLE == ROLE_HIGH || r_fxz;
+  // the y flux duties (yflux_wave): the flux through this row's -y face is another wave's / this wave computes the flux of face DUTY_F
+  constexpr bool y_give = DUTY && (ROLE == ROLE_FULL_LO || ROLE == ROLE_HIGH);
+  constexpr bool y_take = DUTY && (ROLE == ROLE_HALO || ROLE == ROLE_HALO_HI);
+  constexpr int DUTY_F = ROLE == ROLE_HALO ? 2 : BY - 2;
+  static_assert(!DUTY || (yflux_wave<BY, DUTY>(2) == 0 && yflux_wave<BY, DUTY>(BY - 2) == BY - 1 && yflux_wave<BY, DUTY>(3) == 3),
+                "the roles below implement this table");
+  // (the traced states of trace3d_cell are floored: llf_flux_fast FLOORED; 1 / rho rides from ctoprim_cell to the trace)
+  // (the LLF kernels: the others sit at their register limit and keep the instructions they had)
+  constexpr bool TRIM = SWEEP_TRIM != 0 && RS == RIEMANN_LLF && SCHEME == 0 && NE == 0 && !PFIX;
   const bool r_upd = r_fxz && (tx >= 2) && (tx <= BX - 3) && (xu < A.nx) && (yu < A.ny);
   const unsigned colb_upd = r_upd ? colb : BUF_OOB;   // lanes that own no cell store nowhere
 
@@ -360,6 +425,11 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #pragma unroll
   for (int n = 0; n < NV; n++) ukeep[n] = 0.0;
 
+  double rinv_c = 0.0;            // TRIM: 1 / rho of this column's cell of plane c (ctoprim_cell's)
+#if SWEEP_CYCLE_PROBE
+  unsigned long long pr_a = 0, pr_w = 0, pr_b = 0, pr_n = 0;
+#endif
+
   // ring slots of planes c-1, c, c+1
   int sa = 0, sb = 1, sc = 2;
 
@@ -383,7 +453,8 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #pragma unroll
       for (int n = 0; n < NV; n++) ukeep[n] = u[n];
     }
-    ctoprim_cell<NV, GRAV, NE>(u, g, dtxhalf, P, q);
+    if constexpr (TRIM && r_trace) ctoprim_cell<NV, GRAV, NE>(u, g, dtxhalf, P, q, &rinv_c);
+    else ctoprim_cell<NV, GRAV, NE>(u, g, dtxhalf, P, q);
 #pragma unroll
     for (int n = 0; n < NV; n++) qring[sb].v[n][ty][tx] = q[n];
     load_u(z0, upre); load_g(z0, gpre);
@@ -427,13 +498,22 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #pragma unroll
     for (int n = 0; n < 2 * NF; n++) park[n][ty - 2][tx] = 0.0;
   }
+  if constexpr (DUTY && ROLE == ROLE_FULL_LO) {
+#pragma unroll
+    for (int n = 0; n < NF; n++) yduty[0][n][tx] = yduty[1][n][tx] = 0.0;
+  }
 
   for (int c = z0 - 1; c <= z1; c++) {
     Plane<L::MR, NF> &M = mring[c & 1];
     Plane<L::MR, NF> &Mprev = mring[(c & 1) ^ 1];
+#if SWEEP_CYCLE_PROBE
+    const unsigned long long pr_t0 = __builtin_readcyclecounter();
+#endif
     // ---- phase A: plane c+1 arrives; trace plane c; x and z fluxes ------------------
     double qc[NV];
-    ctoprim_cell<NV, GRAV, NE>(upre, gpre, dtxhalf, P, qc);
+    double rinv_n = 0.0;
+    if constexpr (TRIM && r_trace) ctoprim_cell<NV, GRAV, NE>(upre, gpre, dtxhalf, P, qc, &rinv_n);
+    else ctoprim_cell<NV, GRAV, NE>(upre, gpre, dtxhalf, P, qc);
     // plane c+1 goes into the ring: into its own slot (RING 3), or into the slot of plane c-1 as soon as this thread has taken
     // its z slope from it (RING 2; the rows that take no slopes have nothing to wait for)
     if (RING == 3 || !r_trace) {
@@ -508,15 +588,21 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       }
       double qm[3][NV], qp[3][NV];
       if (SCHEME == 0) {
-        trace3d_cell<NV, NE>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp);
+        if constexpr (TRIM) trace3d_cell<NV, NE>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp, &rinv_c);
+        else trace3d_cell<NV, NE>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp);
       } else {
         const double cc = ctoprim_sound(qb[0], qb[4], P);
         tracexyz_cell<NV>(qb, dq, cc, dtdx, dtdx, dtdx, P, qm, qp);
       }
+      // (DUTY: nobody reads row BY-2's +y state -- its slot takes the -y state, for the wave of row BY-1)
 #pragma unroll
-      for (int n = 0; n < NV; n++) M.v[n][ty - M0][tx] = qm[1][n];
+      for (int n = 0; n < NV; n++) M.v[n][ty - M0][tx] = (DUTY && ROLE == ROLE_HIGH) ? qp[1][n] : qm[1][n];
 #pragma unroll
       for (int n = 0; n < NV; n++) qpy[n] = qp[1][n];
+      if constexpr (DUTY && ROLE == ROLE_FULL_LO) {
+#pragma unroll
+        for (int n = 0; n < NV; n++) yduty[c & 1][n][tx] = qp[1][n];      // for the wave of row 0
+      }
       if constexpr (r_fxz) {
         double qL[NV], fx[NF], fz[NF];
 #pragma unroll
@@ -532,9 +618,9 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
           for (int n = 0; n < NV; n++) fz[n] = f[n];
           fz[NV] = t[0]; fz[NV + 1] = t[1];
         } else {
-        scaled_interface_flux<RS, NV, 0, !MASK, NE>(qL, qp[0], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fx);
+        scaled_interface_flux<RS, NV, 0, !MASK, NE, TRIM>(qL, qp[0], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fx);
         // z flux through the face between planes c-1 and c
-        scaled_interface_flux<RS, NV, 2, !MASK, NE>(qmz, qp[2], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fz);
+        scaled_interface_flux<RS, NV, 2, !MASK, NE, TRIM>(qmz, qp[2], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fz);
         }
         if (MASK) {
           // hydro/godunov_fine.f90:720-747: the flux through a face is reset when the cell on either side is refined
@@ -576,11 +662,32 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       if (MASK && r_trace) { const int ps = min(c + 1, z1 + 1); spre = stat_load(A.stat, (unsigned)A.pitch_var, tbp(ps) >> 3, zpart(ps)); }
     }
     __builtin_amdgcn_sched_barrier(0);
+#if SWEEP_CYCLE_PROBE
+    const unsigned long long pr_t1 = __builtin_readcyclecounter();
+#endif
     __syncthreads();  // the one barrier: +y states of plane c and y fluxes of plane c-1 visible
+#if SWEEP_CYCLE_PROBE
+    const unsigned long long pr_t2 = __builtin_readcyclecounter();
+#endif
 
     // ---- phase B: y flux of plane c; finish plane c-1 --------------------------------
     double fy[NF];
-    if constexpr (ROLE == ROLE_FULL || ROLE == ROLE_HIGH) {
+    if constexpr (y_take) {
+      // the flux through face DUTY_F, between rows DUTY_F-1 and DUTY_F, for the rows beside it
+      double qL[NV], qR[NV];
+#pragma unroll
+      for (int n = 0; n < NV; n++) {
+        qL[n] = M.v[n][DUTY_F - 1 - M0][tx];
+        qR[n] = ROLE == ROLE_HALO ? yduty[c & 1][n][tx] : M.v[n][DUTY_F - M0][tx];
+      }
+      scaled_interface_flux<RS, NV, 1, !MASK, NE, TRIM>(qL, qR, P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fy);
+#pragma unroll
+      for (int n = 0; n < NF; n++) {
+        if (ROLE == ROLE_HALO) yduty[c & 1][n][tx] = fy[n];       // row 2 picks it up after the next barrier
+        else M.v[n][DUTY_F - 1 - M0][tx] = fy[n];                 // row BY-3's slot, where row BY-2 used to leave it
+      }
+    }
+    if constexpr ((r_fxz || ROLE == ROLE_HIGH) && !y_give) {
       double qL[NV];
 #pragma unroll
       for (int n = 0; n < NV; n++) qL[n] = M.v[n][tym - M0][tx];
@@ -591,7 +698,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
         for (int n = 0; n < NV; n++) fy[n] = f[n];
         fy[NV] = t[0]; fy[NV + 1] = t[1];
       } else {
-      scaled_interface_flux<RS, NV, 1, !MASK, NE>(qL, qpy, P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fy);
+      scaled_interface_flux<RS, NV, 1, !MASK, NE, TRIM>(qL, qpy, P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fy);
       }
       if (MASK) {
         ok_ym = smask[((c + 3) % 3 * BY + tym) * BX + tx];
@@ -613,7 +720,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       for (int n = 0; n < NF; n++) {
         fyh[n] = Mprev.v[n][ty - M0][tx];
         const double pxn = PARK ? park[n][ty - 2][tx] : partx[n];
-        const double fyn = PARK ? park[NF + n][ty - 2][tx] : fyown[n];
+        const double fyn = y_give ? yduty[(c & 1) ^ 1][n][tx] : (PARK ? park[NF + n][ty - 2][tx] : fyown[n]);
         const double part = (LATE ? bcar[n < NV ? n : 0] + pxn : pxn) + (fyn - fyh[n]);
         un[n] = part + dz[n];
       }
@@ -634,7 +741,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       }
 #pragma unroll
       for (int n = 0; n < NF; n++) {
-        if (PARK) { park[n][ty - 2][tx] = px[n]; park[NF + n][ty - 2][tx] = fy[n]; }
+        if (PARK) { park[n][ty - 2][tx] = px[n]; if (!y_give) park[NF + n][ty - 2][tx] = fy[n]; }
         else { partx[n] = px[n]; fyown[n] = fy[n]; }
       }
       {
@@ -656,7 +763,18 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     if (RING == 3) { const int t = sa; sa = sb; sb = sc; sc = t; }
     else { const int t = sa; sa = sb; sb = t; }
     if (MASK) ok_zlo = okc;
+    if (TRIM) rinv_c = rinv_n;
+#if SWEEP_CYCLE_PROBE
+    pr_a += pr_t1 - pr_t0; pr_w += pr_t2 - pr_t1; pr_b += __builtin_readcyclecounter() - pr_t2; pr_n += 1;
+#endif
   }
+#if SWEEP_CYCLE_PROBE
+  if (tx == 0 && blockIdx.x < PROBE_BLOCKS && ty < PROBE_ROWS) {
+    unsigned long long *o = sweep_cycle_probe[blockIdx.x][ty];
+    o[0] = pr_a; o[1] = pr_w; o[2] = pr_b; o[3] = pr_n; o[4] = (unsigned long long)ty;
+    o[5] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_ID
+  }
+#endif
 }
 
 template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, bool MASK = false>
@@ -670,7 +788,12 @@ __global__ __launch_bounds__(BX *BY) void godunov_sweep_kernel(SweepArgs A) {
   else if (ty == BY - 1) sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_HALO_HI, MASK>(A, smem_raw);
   else if (ty == 1) sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_LOW, MASK>(A, smem_raw);
   else if (ty == BY - 2) sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_HIGH, MASK>(A, smem_raw);
-  else sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_FULL, MASK>(A, smem_raw);
+  else {
+    if constexpr (y_duty<ST, RS, BY, GRAV, SCHEME, NV, MASK>()) {
+      if (ty == 2) { sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_FULL_LO, MASK>(A, smem_raw); return; }
+    }
+    sweep_march<ST, RS, BY, GRAV, SCHEME, NV, ROLE_FULL, MASK>(A, smem_raw);
+  }
 }
 
 #ifndef RAMSES_AMD_FAST
@@ -1295,7 +1418,9 @@ hipError_t launch_surface_flux_pfix(const SurfArgs &A, int slope_type, int riema
 // ---------------------------------------------------------------------------
 template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, bool MASK = false>
 static hipError_t launch3(const SweepArgs &A, hipStream_t s) {
-  const size_t lds = Lds<ST, BY, NV, MASK, GRAV>::bytes;
+  typedef Lds<ST, BY, NV, MASK, GRAV, 0, y_duty<ST, RS, BY, GRAV, SCHEME, NV, MASK>()> L;
+  static_assert(L::bytes <= 160 * 1024, "one workgroup's LDS");
+  const size_t lds = L::bytes;
   dim3 block(BX, BY);
   dim3 grid(A.nblocks);
   auto k = godunov_sweep_kernel<ST, RS, BY, GRAV, SCHEME, NV, MASK>;
@@ -1689,6 +1814,17 @@ hipError_t launch_godunov_sweep_scalars(SweepArgs &A, int slope_type, int rieman
 
 }  // namespace SWEEP_NS
 }  // namespace ramses_amd
+
+#if SWEEP_CYCLE_PROBE && defined(RAMSES_AMD_FAST) && defined(SWEEP_ST) && SWEEP_ST == 1
+// the probe's sums of the last launches of this unit's kernels: PROBE_BLOCKS x PROBE_ROWS x PROBE_WORDS 64-bit words
+extern "C" int ramses_amd_sweep_cycle_probe(unsigned long long *out, long nwords) {
+  using namespace ramses_amd::fastmode;
+  const long have = (long)PROBE_BLOCKS * PROBE_ROWS * PROBE_WORDS;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(sweep_cycle_probe), sizeof(unsigned long long) * (nwords < have ? nwords : have)) != hipSuccess) return -1;
+  return 0;
+}
+#endif
 
 // (the units of one slope type are not warmed up: a run uses one of the twelve, which loads with its first sweep)
 #include "warm.hpp"
