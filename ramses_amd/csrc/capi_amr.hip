@@ -1465,16 +1465,27 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   }
   // (round 6: runs with one or two passive scalars and the Newton solver too -- kernels of 8 rows, work items of 4)
   const int nvar = R.nvar;
-  if (nvar < 5 || nvar > 7 || p->nvar != nvar || p->ndim != 3 || p->difmag > 0.0) return 0;
+  if (nvar < 5 || nvar > 7 || p->nvar != nvar || p->ndim != 3) return 0;
   // pressure_fix: divu / enew ride through the dense sweep as two more flux components (muscl; plmde keeps the tree walker, whose
   // single-oct kernel it takes there too) -- in strict arithmetic whatever fast_math says: the two face quantities exist in the
   // reference's operation order only, and a bit-identical result meets the fast mode's 1e-12 contract
   const bool pfix = R.pfix;
   if (pfix && p->scheme != RAMSES_AMD_SCHEME_MUSCL) return 0;
+  // difmag > 0: cmpdivu / consup ride through the dense sweep too (csrc/difmag_core.hpp; muscl, without pressure_fix: the other
+  // combinations keep the tree walker) -- in strict arithmetic whatever fast_math says, for the same reason
+  // OPT-IN (RAMSES_AMD_DIFMAG_TILES=1) until the tiles are measured against the tree walker with difmag on the two probe levels
+  // (scripts/amr_tile_probe.py --difmag; DESIGN.md "difmag on tiles"): unmeasured, a difmag run keeps the path it had
+  const bool difmag = p->difmag > 0.0;
+  if (difmag && (pfix || p->scheme != RAMSES_AMD_SCHEME_MUSCL)) return 0;
+  if (difmag) {
+    const char *e = getenv("RAMSES_AMD_DIFMAG_TILES");
+    if (!(e && e[0] == '1')) return 0;
+  }
   if (p->scheme != RAMSES_AMD_SCHEME_MUSCL && !(p->scheme == RAMSES_AMD_SCHEME_PLMDE && nvar == 5)) return 0;
   const int st = p->slope_type;
   if (!(st == 0 || st == 1 || st == 2 || st == 3 || st == 7 || st == 8)) return 0;
-  const int rows = pfix ? strictmode::tile_sweep_rows_pfix(nvar, st) : strictmode::tile_sweep_rows(p->riemann, nvar, st, p->scheme);
+  const int rows = pfix ? strictmode::tile_sweep_rows_pfix(nvar, st) : difmag ? strictmode::tile_sweep_rows_difmag(nvar, st)
+                                                                              : strictmode::tile_sweep_rows(p->riemann, nvar, st, p->scheme);
   if (interpol_var < 0 || interpol_var > 2 || interpol_type < 0 || interpol_type > 4) return 0;
   if ((unsigned long)R.ncell * 8ul >= (1ul << 31)) {      // lane offsets into a cell vector are 31-bit byte offsets
     static bool told = false;
@@ -1505,6 +1516,8 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   A.stat = R.stat.as<unsigned char>(); A.dir = L.dir.as<int>(); A.work = P.work.as<int>(); A.nwork = P.nwork;
   SweepPfix X;
   if (pfix) { X.divu = R.divu.as<double>(); X.enew = R.enew.as<double>(); }
+  SweepDifmag D;
+  D.difmag = p->difmag;
   A.ntx = L.ntx; A.nty = L.nty; A.ntz = L.ntz; A.ngd = R.ngridmax; A.ncoarse = R.ncoarse;
   // (the finest level of the tree: nothing has touched unew since set_unew copied uold into it -- the contract of this routine,
   //  hydro/godunov_fine.f90:5-35 after amr_step's set_unew -- so the kernel re-reads uold from L2 instead of streaming unew)
@@ -1523,7 +1536,7 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   // (event, fine face).  Arithmetic: strict (bit-identical) unless the caller's parameters ask for the fast build (fast_math: the
   // patched program's default, certified <= 1e-12 against the reference program on an AMR run with sub-cycling and regrids,
   // tests/test_fast_certificate_gpu.py; RAMSES_AMD_STRICT=1 selects the bit-identical build)
-  const bool fast = p->fast_math != 0 && !pfix;
+  const bool fast = p->fast_math != 0 && !pfix && !difmag;
   if (P.nevent > 0) {
     SurfArgs S;
     S.uold = A.uold; S.grav = A.grav; S.stat = A.stat; S.dir = A.dir; S.tileid = L.tileid.as<int>();
@@ -1535,11 +1548,13 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
     // (the pass on a stream of its own beside the marching kernel was measured in round 6 -- 2.62 -> 2.54 ms strict, 2.09 -> 2.08 fast
     //  on the shell level: a CU the marching kernel fills has no registers left for it, the two take turns; dropped)
     hipError_t es = pfix ? strictmode::launch_surface_flux_pfix(S, st, p->riemann, nvar, R.grav, s)
+                    : difmag ? strictmode::launch_surface_flux_difmag(S, D, st, p->riemann, nvar, R.grav, s)
                     : fast ? fastmode::launch_surface_flux(S, st, p->riemann, nvar, p->scheme, R.grav, s) : strictmode::launch_surface_flux(S, st, p->riemann, nvar, p->scheme, R.grav, s);
     if (es == hipErrorInvalidValue) { (void)hipGetLastError(); return 0; }     // a variant the tile kernels do not cover
     HCHK(es, "surface pass of a level in tiles");
   }
   hipError_t e = pfix ? strictmode::launch_godunov_sweep_pfix(A, X, st, p->riemann, nvar, R.grav, s)
+                 : difmag ? strictmode::launch_godunov_sweep_difmag(A, D, st, p->riemann, nvar, R.grav, s)
                  : fast ? fastmode::launch_godunov_sweep(A, st, p->riemann, rows + 4, p->scheme, nvar, R.grav, s)
                         : strictmode::launch_godunov_sweep(A, st, p->riemann, rows + 4, p->scheme, nvar, R.grav, s);
   if (e == hipErrorInvalidValue) { (void)hipGetLastError(); return 0; }     // a variant the tile kernels do not cover

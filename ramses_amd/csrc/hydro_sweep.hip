@@ -24,6 +24,7 @@
 // contraction, rcp/rsq-based division and square root, fused LLF).
 #include <hip/hip_runtime.h>
 
+#include "difmag_core.hpp"
 #include "hydro_core.hpp"
 #include "sweep_args.hpp"
 
@@ -57,10 +58,13 @@ struct Plane {
 // (NX: components that ride beside the NV fluxes through the y slots and the parked partial update -- the two face quantities
 // of pressure_fix)
 // (DUTY: the two slot planes of one row -- y_duty below -- through which row 2 hands its -y face to the wave of row 0)
-template <int ST, int BY, int NV, bool MASK, bool GRAV, int NX = 0, bool DUTY = false>
+// (R3: three ring planes whatever the slope type -- difmag, whose corner divergences read the neighbours' planes c and c+1 AFTER
+//  the barrier, while the quickest waves already write plane c+2)
+// (DPN: doubles per column of a full row that the difmag kernels park beside it -- dif_parked() below)
+template <int ST, int BY, int NV, bool MASK, bool GRAV, int NX = 0, bool DUTY = false, bool R3 = false, int DPN = 0>
 struct Lds {
   static constexpr int NF = NV + NX;
-  static constexpr int RING = (ST == 3) ? 3 : 2;
+  static constexpr int RING = (ST == 3 || R3) ? 3 : 2;
 #ifndef SWEEP_PARK_PLAIN
 #ifdef RAMSES_AMD_FAST
 #define SWEEP_PARK_PLAIN 1     // the fast 12-row kernels park too: with the plane held in registers (KEEP) 3.23 -> 3.08 ms at 512^3
@@ -77,8 +81,14 @@ struct Lds {
   static constexpr size_t duty_off = park_off + (PARK ? sizeof(double) * 2 * NF * (BY - 4) * BX : 0);   // DUTY: [2][NF][BX], by plane parity
   static constexpr size_t mask_off = duty_off + (DUTY ? sizeof(double) * 2 * NF * BX : 0);   // MASK: [3][BY][BX] status bytes
   static constexpr size_t sloc_off = mask_off + (MASK ? 3 * BY * BX : 0);                                // MASK: [BY][BX] lane part of the cell index
-  static constexpr size_t bytes = sloc_off + (MASK ? 4 * BY * BX : 0);
+  static constexpr size_t dpark_off = sloc_off + (MASK ? 4 * BY * BX : 0);                               // DPN: [DPN][BY - 4][BX]
+  static constexpr size_t bytes = dpark_off + sizeof(double) * DPN * (BY - 4) * BX;
 };
+// difmag: what a full row carries from plane to plane waits in LDS where the registers run out and the LDS has room -- the
+// Newton solver (it spills otherwise, NV = 5 too) and NV = 6: the z flux of plane c-1's face and the two corner divergences
+// (NV + 2 doubles), at NV = 5 the +z traced state as well (2 NV + 2).  NV = 7 fills the LDS with its three ring planes.
+template <int RS, int NV>
+constexpr int dif_parked() { return (NV == 5 && RS == RIEMANN_EXACT) ? 2 * NV + 2 : ((NV == 6) ? NV + 2 : 0); }
 
 // wavefront shift by one lane: lane i receives the value of lane i-1 (shr) or
 // i+1 (shl); the edge lane keeps its own value (a halo lane, never stored).
@@ -202,14 +212,39 @@ __device__ __forceinline__ int dir_load(const int *base, unsigned plane_ints, un
 // PFIX (MASK, strict arithmetic only): pressure_fix -- the face velocity and the internal-energy flux of every interface
 // (hydro/umuscl.f90:843-850) ride beside the NV fluxes as components NV and NV + 1 through the same differencing and the same
 // resets, and land in divu / enew of the cells whose unew is stored (hydro/godunov_fine.f90:720-790)
-template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, int ROLE, bool MASK, int NE = 0, bool PFIX = false>
-__device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *smem_raw, const SweepPfix &X = SweepPfix()) {
+// DIFMAG: the conserved variables of one cell of a level in tiles again (pb: the plane's part of the cell index in bytes, off: the
+// lane's): an L2 hit.  (Free functions, not lambdas of sweep_march: what difmag needs stays out of the scope that every
+// instantiation of sweep_march compiles, so that the kernels without difmag stay the code they were.)
+template <int NV>
+__device__ __forceinline__ void load_uold_cell(const double *uold, long pitch_var, unsigned odd_var, unsigned pb, unsigned off, double (&u)[NV]) {
+#pragma unroll
+  for (int n = 0; n < NV; n++) u[n] = plane_load(uold + (long)(n & ~1) * pitch_var, pb + (n & 1) * odd_var, off);
+}
+// the tile base of row ty-1's cell: by z-tile parity and x-tile A / B, as sweep_march's tbp picks the row's own
+__device__ __forceinline__ unsigned tile_base_ym(int par, bool inB, unsigned a0, unsigned a1, unsigned b0, unsigned b1) {
+  const unsigned a = par ? a1 : a0, b = par ? b1 : b0;
+  return inB ? b : a;
+}
+// DIFMAG (MASK, strict arithmetic only): difmag > 0 -- cmpdivu / consup of csrc/difmag_core.hpp.  The diffusive term of a face
+// needs the velocity divergence at the face's four corners, and the corners of plane c+1 need the neighbours' primitives of
+// plane c+1, which the ring shows after the barrier only.  So the x and z fluxes of phase A cross the barrier as they are, and
+// phase B finishes all three: every thread takes the corners (tx, ty) and (tx, ty+1) of plane c+1 from the velocities of planes
+// c and c+1 in the ring -- its own column from LDS, column tx-1 by DPP -- keeps them for the next plane (where they are the
+// corners of plane c), gets the corners at tx+1 by DPP, adds the term to each flux BEFORE the reset at refined cells and the
+// differencing, and goes on as without difmag.  No corner array in LDS and no second barrier; the price is a third ring plane
+// (Lds R3), 18 LDS reads and the conserved variables of plane c (own, row ty-1) and c-1 (own) read again from L2.
+template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, int ROLE, bool MASK, int NE = 0, bool PFIX = false, bool DIFMAG = false>
+__device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *smem_raw, const SweepPfix &X = SweepPfix(),
+                                            const SweepDifmag &D = SweepDifmag()) {
   static_assert(!PFIX || (MASK && NE == 0 && SCHEME == 0), "pressure_fix: the sweep of a level in tiles, muscl");
+  static_assert(!DIFMAG || (MASK && NE == 0 && SCHEME == 0 && !PFIX), "difmag: the sweep of a level in tiles, muscl, no pressure_fix");
   constexpr int NF = NV + (PFIX ? 2 : 0);   // components differenced
   const bool DXPOW2 = A.pow2 != 0;   // uniform
   constexpr bool DUTY = y_duty<ST, RS, BY, GRAV, SCHEME, NV, MASK, NE, PFIX>();
   static_assert(DUTY || ROLE != ROLE_FULL_LO, "row 2 is a full row like the others unless the y fluxes are shared out");
-  typedef Lds<ST, BY, NV, MASK, GRAV, NF - NV, DUTY> L;
+  constexpr int DPN = DIFMAG ? dif_parked<RS, NV>() : 0;
+  typedef Lds<ST, BY, NV, MASK, GRAV, NF - NV, DUTY, DIFMAG, DPN> L;
+  double (*dpark)[BY - 4][BX] = reinterpret_cast<double (*)[BY - 4][BX]>(smem_raw + L::dpark_off);   // DPN: fzlo, the two corners (, qmz) of the full rows
   constexpr int RING = L::RING;
   constexpr bool PARK = L::PARK;
   constexpr int M0 = L::M0;
@@ -364,6 +399,12 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
   // no tile: with the lane's part still beyond every buffer range, so such a lane loads zeros and stores nothing.
   constexpr unsigned TILE_VOID = 0x80000000u;
   unsigned sA0 = TILE_VOID, sA1 = TILE_VOID, sB0 = TILE_VOID, sB1 = TILE_VOID;    // (four scalars: an indexed local array would live in scratch)
+  unsigned mA0 = TILE_VOID, mA1 = TILE_VOID, mB0 = TILE_VOID, mB1 = TILE_VOID;    // DIFMAG: the same of row ty-1 (another tile row where yis % 8 == 0)
+  int drow_m = 0;
+  if constexpr (DIFMAG) {
+    const int ym = yis > 0 ? yis - 1 : A.ny - 1;
+    drow_m = A.ntx * (ym >> 3);
+  }
   auto tile_of_plane = [&](int p) -> int { return wrap_z(p) >> 3; };
   auto tile_set = [&](int tz) {
     // (through the constant address space: the directory is not written during the launch, and only such a load is scalar)
@@ -372,6 +413,12 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     const int ra = row[tA], rb = row[tB];
     const unsigned a = ra < 0 ? TILE_VOID : (unsigned)ra * 8u, b = rb < 0 ? TILE_VOID : (unsigned)rb * 8u;
     if (tz & 1) { sA1 = a; sB1 = b; } else { sA0 = a; sB0 = b; }
+    if constexpr (DIFMAG) {
+      const cdir_p rowm = (cdir_p)(A.dir + (long)tz * (A.ntx * A.nty) + drow_m);
+      const int qa = rowm[tA], qb = rowm[tB];
+      const unsigned am = qa < 0 ? TILE_VOID : (unsigned)qa * 8u, bm = qb < 0 ? TILE_VOID : (unsigned)qb * 8u;
+      if (tz & 1) { mA1 = am; mB1 = bm; } else { mA0 = am; mB0 = bm; }
+    }
   };
   auto zpart = [&](int p) -> unsigned {          // cells
     const int pz = wrap_z(p);
@@ -403,6 +450,8 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     // (divu / enew are read whatever base_uold says: they hold what set_unew and the finer level left there)
     if constexpr (PFIX) { u[NV] = plane_load(X.divu, pb, off); u[NV + 1] = plane_load(X.enew, pb, off); }
   };
+  double dif_cy = 0.0;                 // DIFMAG: difmag * min(0, div1) of this row's -y face of plane c (set and used in phase B)
+  double dif_c0 = 0.0, dif_c1 = 0.0;   // DIFMAG: the corner divergences of plane c at (tx, ty) and (tx, ty+1)
   int ok_zlo = 0;   // MASK: plane c-1's status byte of this column
   int spre = 0;     // MASK: plane c+1's status byte, on its way
   unsigned char *smask = smem_raw + L::mask_off;   // MASK: [3][BY][BX] status bytes of planes c-1, c, c+1, by plane mod 3
@@ -502,6 +551,10 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #pragma unroll
     for (int n = 0; n < NF; n++) yduty[0][n][tx] = yduty[1][n][tx] = 0.0;
   }
+  if constexpr (DPN > 0 && (ROLE == ROLE_FULL || ROLE == ROLE_FULL_LO)) {
+#pragma unroll
+    for (int n = 0; n < DPN; n++) dpark[n][ty - 2][tx] = n < NV + 2 ? 0.0 : 1.0;      // (as fzlo, the corners and qmz start)
+  }
 
   for (int c = z0 - 1; c <= z1; c++) {
     Plane<L::MR, NF> &M = mring[c & 1];
@@ -521,7 +574,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       for (int n = 0; n < NV; n++) qring[RING == 3 ? sc : sa].v[n][ty][tx] = qc[n];
     }
     double ucur[NF];
-    if (r_fxz && !LATE) {
+    if (r_fxz && !LATE && !DIFMAG) {
       if (KEEP && (!MASK || A.base_uold)) {
 #pragma unroll
         for (int n = 0; n < NV; n++) ucur[n] = ukeep[n];          // plane c, held since it arrived
@@ -620,9 +673,13 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
         } else {
         scaled_interface_flux<RS, NV, 0, !MASK, NE, TRIM>(qL, qp[0], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fx);
         // z flux through the face between planes c-1 and c
+        if constexpr (DPN > NV + 2) {
+#pragma unroll
+          for (int n = 0; n < NV; n++) qmz[n] = dpark[NV + 2 + n][ty - 2][tx];
+        }
         scaled_interface_flux<RS, NV, 2, !MASK, NE, TRIM>(qmz, qp[2], P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fz);
         }
-        if (MASK) {
+        if (MASK && !DIFMAG) {
           // hydro/godunov_fine.f90:720-747: the flux through a face is reset when the cell on either side is refined
           const int s_xm = wave_shr1_i(okc);
           const bool zx = ((okc | s_xm) & CELL_REFINED) != 0, zz = ((okc | ok_zlo) & CELL_REFINED) != 0;
@@ -632,6 +689,15 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
         double fxh[NF];
 #pragma unroll
         for (int n = 0; n < NV; n++) qmz[n] = qm[2][n];
+        if constexpr (DPN > NV + 2) {
+#pragma unroll
+          for (int n = 0; n < NV; n++) dpark[NV + 2 + n][ty - 2][tx] = qm[2][n];
+        }
+        if constexpr (DIFMAG) {
+          // the x and z fluxes cross the barrier as they are: their diffusive term, the resets and the differencing in phase B
+#pragma unroll
+          for (int n = 0; n < NF; n++) { px[n] = fx[n]; dz[n] = fz[n]; }
+        } else {
 #pragma unroll
         for (int n = 0; n < NF; n++) {
           dz[n] = fzlo[n] - fz[n];          // z flux difference of plane c-1
@@ -639,6 +705,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
           fxh[n] = wave_shl1(fx[n]);        // -x face flux of column tx+1
           // (LATE: the state the update starts from joins in phase B of the next iteration -- a whole trace after its load)
           px[n] = LATE ? (fx[n] - fxh[n]) : ucur[n] + (fx[n] - fxh[n]);
+        }
         }
         if (NV > 5 + NE && !MASK) {
           rnew = ucur[0];
@@ -649,6 +716,24 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     }
     // prefetch plane c+2 after the register peak of the trace and flux phase (still ~1 us ahead of its use)
     __builtin_amdgcn_sched_barrier(0);
+    // DIFMAG: uold of plane c -- this cell's and row ty-1's -- and of plane c-1, for the conserved differences of phase B; requested
+    // before the prefetch, so that waiting for them does not wait for plane c+2.  They wait in three arrays that a difmag kernel
+    // leaves idle (ukeep: KEEP, bcar: LATE, partx: without PARK), under other names: a local declared in this loop's body, used
+    // or not, leaves its lifetime markers in EVERY instantiation and moved scalar code of the exact-solver tile kernels
+    // (profiles/difmag_asm_diff.txt) -- what difmag adds to the loop's scope lives inside if constexpr (DIFMAG) or before the loop.
+    if constexpr (DIFMAG && (r_fxz || ROLE == ROLE_HIGH)) {
+      static_assert(!KEEP && !LATE && PARK, "difmag borrows ukeep, bcar and partx");
+      double (&dif_u)[NV] = ukeep, (&dif_uym)[NV] = bcar, (&dif_uzm)[NV] = partx;
+      // (row ty-1 parked its lane part of the cell index in sloc before the first barrier)
+      load_uold_cell<NV>(uold, A.pitch_var, odd_var, zpart(c) * 8u, tbp(c), dif_u);
+      if constexpr (!r_fxz)
+        load_uold_cell<NV>(uold, A.pitch_var, odd_var, zpart(c) * 8u,
+                           tile_base_ym(tile_of_plane(c) & 1, inB, mA0, mA1, mB0, mB1) + sloc[(ty - 1) * BX + tx], dif_uym);
+      if constexpr (r_fxz) {
+        load_uold_cell<NV>(uold, A.pitch_var, odd_var, zpart(c - 1) * 8u, tbp(c - 1), dif_uzm);
+        load_base(c, ucur);      // (the state the update starts from: not needed before phase B either)
+      }
+    }
     {
       const int pn = min(c + 2, z1 + 1);
       if (MASK) {
@@ -671,6 +756,70 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #endif
 
     // ---- phase B: y flux of plane c; finish plane c-1 --------------------------------
+    if constexpr (DIFMAG && (r_fxz || ROLE == ROLE_HIGH)) {
+      double (&dif_u)[NV] = ukeep, (&dif_uym)[NV] = bcar, (&dif_uzm)[NV] = partx;
+      const Plane<BY, NV> &q0 = qring[sb], &q1 = qring[sc];     // planes c and c+1, every row's and lane's
+      constexpr int NR = r_fxz ? 3 : 2;                         // rows ty-1, ty (, ty+1)
+      const double fdiv = 0.25 / A.dx;
+      double dsum[3][2];                                        // the three sums of cmpdivu at the corners (tx, ty) and (tx, ty+1) of plane c+1
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        // one component at a time (the registers of 12 velocities, not of 36): column tx from LDS, column tx-1 by DPP
+        double vo[2][NR], vl[2][NR];                            // [plane][row]
+#pragma unroll
+        for (int r = 0; r < NR; r++) {
+          vo[0][r] = q0.v[1 + d][tym + r][tx];
+          vo[1][r] = q1.v[1 + d][tym + r][tx];
+          vl[0][r] = wave_shr1(vo[0][r]);
+          vl[1][r] = wave_shr1(vo[1][r]);
+        }
+#pragma unroll
+        for (int r0 = 0; r0 < NR - 1; r0++) {
+          double v[2][2][2];
+#pragma unroll
+          for (int dk = 0; dk < 2; dk++)
+#pragma unroll
+            for (int dj = 0; dj < 2; dj++) { v[dk][dj][0] = vl[dk][r0 + dj]; v[dk][dj][1] = vo[dk][r0 + dj]; }
+          dsum[d][r0] = d == 0 ? difmag::cmpdivu_ux(v, fdiv) : (d == 1 ? difmag::cmpdivu_vy(v, fdiv) : difmag::cmpdivu_wz(v, fdiv));
+        }
+        if (NR == 2) dsum[d][1] = 0.0;
+      }
+      const double dn[2] = {dsum[0][0] + dsum[1][0] + dsum[2][0], dsum[0][1] + dsum[1][1] + dsum[2][1]};
+      if constexpr (DPN > 0 && r_fxz) {
+        dif_c0 = dpark[NV][ty - 2][tx]; dif_c1 = dpark[NV + 1][ty - 2][tx];
+#pragma unroll
+        for (int n = 0; n < NV; n++) fzlo[n] = dpark[n][ty - 2][tx];
+      }
+      const double c0x = wave_shl1(dif_c0), n0x = wave_shl1(dn[0]);     // the corners at tx+1
+      dif_cy = difmag::consup_coef(D.difmag, difmag::consup_div1_y(dif_c0, c0x, dn[0], n0x));
+      if constexpr (r_fxz) {
+        const double c1x = wave_shl1(dif_c1);
+        const double cx = difmag::consup_coef(D.difmag, difmag::consup_div1_x(dif_c0, dif_c1, dn[0], dn[1]));
+        const double cz = difmag::consup_coef(D.difmag, difmag::consup_div1_z(dif_c0, c0x, dif_c1, c1x));
+        // hydro/godunov_fine.f90:720-747 after consup: the flux through a face is reset when the cell on either side is refined
+        const int s_xm = wave_shr1_i(okc);
+        const bool zx = ((okc | s_xm) & CELL_REFINED) != 0, zz = ((okc | ok_zlo) & CELL_REFINED) != 0;
+#pragma unroll
+        for (int n = 0; n < NV; n++) {
+          const double fxd = difmag::consup_term(px[n], A.dt, cx, dif_u[n], wave_shr1(dif_u[n]));
+          const double fzd = difmag::consup_term(dz[n], A.dt, cz, dif_u[n], dif_uzm[n]);
+          const double fxn = zx ? 0.0 : fxd, fzn = zz ? 0.0 : fzd;
+          dz[n] = fzlo[n] - fzn;              // z flux difference of plane c-1
+          fzlo[n] = fzn;
+          px[n] = ucur[n] + (fxn - wave_shl1(fxn));
+        }
+      }
+      dif_c0 = dn[0]; dif_c1 = dn[1];
+      if constexpr (DPN > 0 && r_fxz) {
+        dpark[NV][ty - 2][tx] = dn[0]; dpark[NV + 1][ty - 2][tx] = dn[1];
+#pragma unroll
+        for (int n = 0; n < NV; n++) dpark[n][ty - 2][tx] = fzlo[n];
+      }
+      // (a full row asks for row ty-1's conserved variables only now: they arrive while the Riemann solver of the y face runs)
+      if constexpr (r_fxz)
+        load_uold_cell<NV>(uold, A.pitch_var, odd_var, zpart(c) * 8u,
+                           tile_base_ym(tile_of_plane(c) & 1, inB, mA0, mA1, mB0, mB1) + sloc[(ty - 1) * BX + tx], dif_uym);
+    }
     double fy[NF];
     if constexpr (y_take) {
       // the flux through face DUTY_F, between rows DUTY_F-1 and DUTY_F, for the rows beside it
@@ -699,6 +848,11 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
         fy[NV] = t[0]; fy[NV + 1] = t[1];
       } else {
       scaled_interface_flux<RS, NV, 1, !MASK, NE, TRIM>(qL, qpy, P, A.dt, A.dx, A.rdx, dtdx, DXPOW2, fy);
+      }
+      if constexpr (DIFMAG) {
+        double (&dif_u)[NV] = ukeep, (&dif_uym)[NV] = bcar;
+#pragma unroll
+        for (int n = 0; n < NV; n++) fy[n] = difmag::consup_term(fy[n], A.dt, dif_cy, dif_u[n], dif_uym[n]);
       }
       if (MASK) {
         ok_ym = smask[((c + 3) % 3 * BY + tym) * BX + tx];
@@ -816,6 +970,24 @@ __global__ __launch_bounds__(BX *BY) void godunov_sweep_pfix_kernel(SweepArgs A,
   else if (ty == 1) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_LOW, true, 0, true>(A, smem_raw, X);
   else if (ty == BY - 2) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_HIGH, true, 0, true>(A, smem_raw, X);
   else sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_FULL, true, 0, true>(A, smem_raw, X);
+}
+#endif
+
+#ifndef RAMSES_AMD_FAST
+// difmag > 0 on a level in tiles (strict arithmetic only: the term exists in the reference's operation order only): muscl, no
+// pressure_fix, the 8-row layout with three ring planes for every slope type (sweep_march DIFMAG).  A kernel of its own so that
+// the symbols and the code of the kernels without difmag stay what they were.
+template <int ST, int RS, int BY, bool GRAV, int NV>
+__global__ __launch_bounds__(BX *BY) void godunov_sweep_difmag_kernel(SweepArgs A, SweepDifmag D) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  static_assert(Lds<ST, BY, NV, true, GRAV, 0, false, true, dif_parked<RS, NV>()>::bytes <= 160 * 1024, "the difmag sweep fits one workgroup's LDS");
+  const int ty = threadIdx.y;   // wave-uniform
+  if (ty >= 2 && ty <= BY - 3) __builtin_amdgcn_s_setprio(3);
+  if (ty == 0) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_HALO, true, 0, false, true>(A, smem_raw, SweepPfix(), D);
+  else if (ty == BY - 1) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_HALO_HI, true, 0, false, true>(A, smem_raw, SweepPfix(), D);
+  else if (ty == 1) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_LOW, true, 0, false, true>(A, smem_raw, SweepPfix(), D);
+  else if (ty == BY - 2) sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_HIGH, true, 0, false, true>(A, smem_raw, SweepPfix(), D);
+  else sweep_march<ST, RS, BY, GRAV, 0, NV, ROLE_FULL, true, 0, false, true>(A, smem_raw, SweepPfix(), D);
 }
 #endif
 
@@ -1247,6 +1419,76 @@ __device__ __forceinline__ void surf_interface(const SurfArgs &A, const int (&lo
 #endif
   }
 }
+#ifndef RAMSES_AMD_FAST
+// difmag > 0: the diffusive term of the interface between lo and hi = lo + e_DIR (consup), added to the scaled flux fl.  The
+// four corners of the face take the velocities of the 2 x 3 x 3 cells round it -- ctoprim_cell's, with the half kick of the
+// gravity, exactly what the marching kernel's ring holds -- and the term the conserved pair lo, hi.  A gather of its own after
+// the interface routine's (the cells of that one are cache hits here): the routines of the kernels without difmag stay as they are.
+template <int NV, bool GRAV, int DIR>
+__device__ __forceinline__ void surf_difmag_term(const SurfArgs &A, double coef_difmag, const int (&lo)[3], double (&fl)[NV]) {
+  constexpr int T0 = DIR == 0 ? 1 : 0, T1 = DIR == 2 ? 1 : 2;
+  long c[2][3][3];
+#pragma unroll
+  for (int s = 0; s < 2; s++)
+#pragma unroll
+    for (int u = 0; u < 3; u++)
+#pragma unroll
+      for (int v = 0; v < 3; v++) {
+        int p[3] = {lo[0], lo[1], lo[2]};
+        p[DIR] += s; p[T0] += u - 1; p[T1] += v - 1;
+        c[s][u][v] = surf_cell(A, p[0], p[1], p[2]);
+      }
+  double vel[2][3][3][3], ulo[NV], uhi[NV];
+#pragma unroll
+  for (int s = 0; s < 2; s++)
+#pragma unroll
+    for (int u = 0; u < 3; u++)
+#pragma unroll
+      for (int v = 0; v < 3; v++) {
+        double uc[NV], g[3], q[NV];
+#pragma unroll
+        for (int n = 0; n < NV; n++) uc[n] = A.uold[(long)n * A.ncell + c[s][u][v]];
+#pragma unroll
+        for (int d = 0; d < 3; d++) g[d] = GRAV ? A.grav[(long)d * A.ncell + c[s][u][v]] : 0.0;
+        ctoprim_cell<NV, GRAV>(uc, g, A.dt * 0.5, A.P, q);
+#pragma unroll
+        for (int d = 0; d < 3; d++) vel[s][u][v][d] = q[1 + d];
+        if (u == 1 && v == 1) {
+#pragma unroll
+          for (int n = 0; n < NV; n++) { if (s == 0) ulo[n] = uc[n]; else uhi[n] = uc[n]; }
+        }
+      }
+  const double fdiv = 0.25 / A.dx;
+  double cn[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; a++)
+#pragma unroll
+    for (int b = 0; b < 2; b++) {
+      double w[3][2][2][2];
+#pragma unroll
+      for (int d = 0; d < 3; d++)
+#pragma unroll
+        for (int dk = 0; dk < 2; dk++)
+#pragma unroll
+          for (int dj = 0; dj < 2; dj++)
+#pragma unroll
+            for (int di = 0; di < 2; di++) {
+              const int o[3] = {di, dj, dk};
+              w[d][dk][dj][di] = vel[o[DIR]][a + o[T0]][b + o[T1]][d];
+            }
+      cn[a][b] = difmag::cmpdivu_corner(w, fdiv, fdiv, fdiv);
+    }
+  const double coef = difmag::consup_coef(coef_difmag, difmag::consup_div1<DIR>(cn));
+#pragma unroll
+  for (int n = 0; n < NV; n++) fl[n] = difmag::consup_term(fl[n], A.dt, coef, uhi[n], ulo[n]);
+}
+template <int NV, bool GRAV>
+__device__ __forceinline__ void surf_difmag_add(const SurfArgs &A, double coef_difmag, int dirn, const int (&lo)[3], double (&fl)[NV]) {
+  if (dirn == 0) surf_difmag_term<NV, GRAV, 0>(A, coef_difmag, lo, fl);
+  else if (dirn == 1) surf_difmag_term<NV, GRAV, 1>(A, coef_difmag, lo, fl);
+  else surf_difmag_term<NV, GRAV, 2>(A, coef_difmag, lo, fl);
+}
+#endif
 // (NF = NV + 2: the records' last two slots are written too -- pressure_fix; NF = NV: they are neither written nor read)
 // (the body as a macro, not a function of its own: through a function the compiler commutes the operands of 27 additions of
 //  surface_flux_kernel -- harmless, but the kernels without pressure_fix are to stay the code they were, instruction for
@@ -1254,7 +1496,8 @@ __device__ __forceinline__ void surf_interface(const SurfArgs &A, const int (&lo
 //  against the (face, oct) order -- and the four fine faces of an event sit in neighbouring lanes.  The updated cell behind fine
 //  face q of face f (q: the two transverse coordinates, lower axis first), the ghost cell beyond the face, lo = the left cell of
 //  the interface; hydro/godunov_fine.f90:720-747: reset when the cell on either side is refined (a ghost cell never is))
-#define SURFACE_FLUX_BODY(SCHEME, NF) \
+// (POST: what a kernel does to the flux between the interface routine and the reset -- nothing, or the diffusive term of difmag)
+#define SURFACE_FLUX_BODY(SCHEME, NF, POST) \
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x; \
   if (t >= (long)A.nevent * 4) return; \
   const int e = A.qminor ? (int)(t >> 2) : (int)(t % A.nevent), q = A.qminor ? (int)(t & 3) : (int)(t / A.nevent); \
@@ -1274,16 +1517,24 @@ __device__ __forceinline__ void surf_interface(const SurfArgs &A, const int (&lo
   if (dirn == 0) surf_interface<ST, RS, NV, GRAV, SCHEME, 0, NF>(A, lo, fl); \
   else if (dirn == 1) surf_interface<ST, RS, NV, GRAV, SCHEME, 1, NF>(A, lo, fl); \
   else surf_interface<ST, RS, NV, GRAV, SCHEME, 2, NF>(A, lo, fl); \
+  POST \
   double *dst = A.rec + ((long)e * 4 + q) * (NV + 2); \
   _Pragma("unroll") for (int n = 0; n < NF; n++) dst[n] = zero ? 0.0 : fl[n];
 template <int ST, int RS, int NV, bool GRAV, int SCHEME = 0>
 __global__ __launch_bounds__(128) void surface_flux_kernel(SurfArgs A) {
-  SURFACE_FLUX_BODY(SCHEME, NV)
+  SURFACE_FLUX_BODY(SCHEME, NV, )
 }
 #ifndef RAMSES_AMD_FAST
 template <int ST, int RS, int NV, bool GRAV>
 __global__ __launch_bounds__(128) void surface_flux_pfix_kernel(SurfArgs A) {
-  SURFACE_FLUX_BODY(0, NV + 2)
+  SURFACE_FLUX_BODY(0, NV + 2, )
+}
+// difmag > 0: the flux of the interface WITH the diffusive term (the coarser level is owed what the fine cell exchanged)
+template <int ST, int RS, int NV, bool GRAV>
+__global__ __launch_bounds__(128) void surface_flux_difmag_kernel(SurfArgs A, SweepDifmag D) {
+#define SURFACE_DIFMAG_POST surf_difmag_add<NV, GRAV>(A, D.difmag, dirn, lo, fl);
+  SURFACE_FLUX_BODY(0, NV, SURFACE_DIFMAG_POST)
+#undef SURFACE_DIFMAG_POST
 }
 #endif
 #undef SURFACE_FLUX_BODY
@@ -1360,6 +1611,40 @@ hipError_t surface0_pfix(const SurfArgs &A, int rs, int nvar, bool grav, hipStre
   }
   return hipErrorInvalidValue;
 }
+// difmag > 0: muscl, NVAR 5 .. 7, every solver
+template <int ST, int RS, int NV>
+static hipError_t surface_difmag2(const SurfArgs &A, const SweepDifmag &D, bool grav, hipStream_t s) {
+  const dim3 grid((unsigned)(((long)A.nevent * 4 + 127) / 128)), block(128);
+  if (grav) hipLaunchKernelGGL((surface_flux_difmag_kernel<ST, RS, NV, true>), grid, block, 0, s, A, D);
+  else hipLaunchKernelGGL((surface_flux_difmag_kernel<ST, RS, NV, false>), grid, block, 0, s, A, D);
+  return hipGetLastError();
+}
+template <int ST, int RS>
+static hipError_t surface_difmag1(const SurfArgs &A, const SweepDifmag &D, int nvar, bool grav, hipStream_t s) {
+  if constexpr (ST == 4 || ST == 5 || ST == 6) {
+    return hipErrorInvalidValue;
+  } else {
+    if (nvar == 5) return surface_difmag2<ST, RS, 5>(A, D, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    if (nvar == 6) return surface_difmag2<ST, RS, 6>(A, D, grav, s);
+    if (nvar == 7) return surface_difmag2<ST, RS, 7>(A, D, grav, s);
+#endif
+    return hipErrorInvalidValue;
+  }
+}
+template <int ST>
+hipError_t surface0_difmag(const SurfArgs &A, const SweepDifmag &D, int rs, int nvar, bool grav, hipStream_t s) {
+  switch (rs) {
+    case RIEMANN_LLF: return surface_difmag1<ST, RIEMANN_LLF>(A, D, nvar, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case RIEMANN_HLLC: return surface_difmag1<ST, RIEMANN_HLLC>(A, D, nvar, grav, s);
+    case RIEMANN_HLL: return surface_difmag1<ST, RIEMANN_HLL>(A, D, nvar, grav, s);
+    case RIEMANN_ACOUSTIC: return surface_difmag1<ST, RIEMANN_ACOUSTIC>(A, D, nvar, grav, s);
+    case RIEMANN_EXACT: return surface_difmag1<ST, RIEMANN_EXACT>(A, D, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
 #endif
 // One translation unit per slope type (ramses_amd/build.py compiles this file once without SWEEP_ST -- the dispatchers -- and once
 // per slope type with -DSWEEP_ST=<type>, 3 standing for 3, 4, 5 and 6, for each arithmetic: the instantiations of the option
@@ -1369,6 +1654,7 @@ hipError_t surface0_pfix(const SurfArgs &A, int rs, int nvar, bool grav, hipStre
 template hipError_t surface0<SWEEP_ST>(const SurfArgs &, int, int, int, bool, hipStream_t);
 #ifndef RAMSES_AMD_FAST
 template hipError_t surface0_pfix<SWEEP_ST>(const SurfArgs &, int, int, bool, hipStream_t);
+template hipError_t surface0_difmag<SWEEP_ST>(const SurfArgs &, const SweepDifmag &, int, int, bool, hipStream_t);
 #endif
 #elif !defined(SWEEP_FLAGSHIP_ONLY)
 #define SWEEP_EXTERN_ST(K) extern template hipError_t surface0<K>(const SurfArgs &, int, int, int, bool, hipStream_t);
@@ -1376,6 +1662,9 @@ SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEE
 #undef SWEEP_EXTERN_ST
 #ifndef RAMSES_AMD_FAST
 #define SWEEP_EXTERN_ST(K) extern template hipError_t surface0_pfix<K>(const SurfArgs &, int, int, bool, hipStream_t);
+SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
+#undef SWEEP_EXTERN_ST
+#define SWEEP_EXTERN_ST(K) extern template hipError_t surface0_difmag<K>(const SurfArgs &, const SweepDifmag &, int, int, bool, hipStream_t);
 SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
 #undef SWEEP_EXTERN_ST
 #endif
@@ -1406,6 +1695,20 @@ hipError_t launch_surface_flux_pfix(const SurfArgs &A, int slope_type, int riema
     case 3: return surface0_pfix<3>(A, riemann, nvar, grav, s);
     case 7: return surface0_pfix<7>(A, riemann, nvar, grav, s);
     case 8: return surface0_pfix<8>(A, riemann, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+hipError_t launch_surface_flux_difmag(const SurfArgs &A, const SweepDifmag &D, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
+  if (A.nevent <= 0) return hipSuccess;
+  switch (slope_type) {
+    case 1: return surface0_difmag<1>(A, D, riemann, nvar, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case 0: return surface0_difmag<0>(A, D, riemann, nvar, grav, s);
+    case 2: return surface0_difmag<2>(A, D, riemann, nvar, grav, s);
+    case 3: return surface0_difmag<3>(A, D, riemann, nvar, grav, s);
+    case 7: return surface0_difmag<7>(A, D, riemann, nvar, grav, s);
+    case 8: return surface0_difmag<8>(A, D, riemann, nvar, grav, s);
 #endif
   }
   return hipErrorInvalidValue;
@@ -1580,6 +1883,50 @@ hipError_t launch0_pfix(SweepArgs &A, const SweepPfix &X, int rs, int nvar, bool
 }
 #endif
 
+#ifndef RAMSES_AMD_FAST
+// difmag > 0 on a level in tiles: one workgroup per work item of the plan (cut for tile_sweep_rows_difmag interior rows)
+template <int ST, int RS, bool GRAV, int NV>
+static hipError_t launch_difmag3(const SweepArgs &A, const SweepDifmag &D, hipStream_t s) {
+  constexpr int BY = 8;
+  const size_t lds = Lds<ST, BY, NV, true, GRAV, 0, false, true, dif_parked<RS, NV>()>::bytes;
+  auto k = godunov_sweep_difmag_kernel<ST, RS, BY, GRAV, NV>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(A.nblocks), dim3(BX, BY), lds, s, A, D);
+  return hipGetLastError();
+}
+template <int ST, int RS>
+static hipError_t launch_difmag1(SweepArgs &A, const SweepDifmag &D, int nvar, bool grav, hipStream_t s) {
+  if constexpr (ST == 4 || ST == 5 || ST == 6) {
+    return hipErrorInvalidValue;
+  } else {
+    if (!A.stat || !A.dir || !A.work || !(D.difmag > 0.0) || A.ng != 0 || A.nwork <= 0) return hipErrorInvalidValue;
+    A.nblocks = A.nwork;
+    A.nbox = 1;          // (the box decode runs, its result is replaced by the work item)
+    A.box[0] = SweepBox{0, 1, 0, 1, 0, A.nz, A.nz, 0};
+    if (nvar == 5) return grav ? launch_difmag3<ST, RS, true, 5>(A, D, s) : launch_difmag3<ST, RS, false, 5>(A, D, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    if (nvar == 6) return grav ? launch_difmag3<ST, RS, true, 6>(A, D, s) : launch_difmag3<ST, RS, false, 6>(A, D, s);
+    if (nvar == 7) return grav ? launch_difmag3<ST, RS, true, 7>(A, D, s) : launch_difmag3<ST, RS, false, 7>(A, D, s);
+#endif
+    return hipErrorInvalidValue;
+  }
+}
+template <int ST>
+hipError_t launch0_difmag(SweepArgs &A, const SweepDifmag &D, int rs, int nvar, bool grav, hipStream_t s) {
+  switch (rs) {
+    case RIEMANN_LLF: return launch_difmag1<ST, RIEMANN_LLF>(A, D, nvar, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case RIEMANN_HLLC: return launch_difmag1<ST, RIEMANN_HLLC>(A, D, nvar, grav, s);
+    case RIEMANN_HLL: return launch_difmag1<ST, RIEMANN_HLL>(A, D, nvar, grav, s);
+    case RIEMANN_ACOUSTIC: return launch_difmag1<ST, RIEMANN_ACOUSTIC>(A, D, nvar, grav, s);
+    case RIEMANN_EXACT: return launch_difmag1<ST, RIEMANN_EXACT>(A, D, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+#endif
+
 // NENER > 0: (NE, NV) = (1, 6), (1, 7) [one passive scalar], (2, 7); LLF, HLL, HLLC; muscl, no gravity, the plain brick
 template <int ST, int RS, int NV, int NE>
 static hipError_t launch_nener3(SweepArgs &A, hipStream_t s) {
@@ -1707,6 +2054,7 @@ template hipError_t launch0_nener<SWEEP_ST>(SweepArgs &, int, int, int, hipStrea
 template hipError_t launch0_scalar<SWEEP_ST>(SweepArgs &, int, int, int, int, bool, hipStream_t);
 #ifndef RAMSES_AMD_FAST
 template hipError_t launch0_pfix<SWEEP_ST>(SweepArgs &, const SweepPfix &, int, int, bool, hipStream_t);
+template hipError_t launch0_difmag<SWEEP_ST>(SweepArgs &, const SweepDifmag &, int, int, bool, hipStream_t);
 #endif
 #if SWEEP_ST == 3
 template hipError_t launch0<4>(SweepArgs &, int, int, int, int, bool, hipStream_t);
@@ -1728,6 +2076,9 @@ SWEEP_EXTERN_SCALAR(0) SWEEP_EXTERN_SCALAR(1) SWEEP_EXTERN_SCALAR(2) SWEEP_EXTER
 #define SWEEP_EXTERN_PFIX(K) extern template hipError_t launch0_pfix<K>(SweepArgs &, const SweepPfix &, int, int, bool, hipStream_t);
 SWEEP_EXTERN_PFIX(0) SWEEP_EXTERN_PFIX(1) SWEEP_EXTERN_PFIX(2) SWEEP_EXTERN_PFIX(3) SWEEP_EXTERN_PFIX(7) SWEEP_EXTERN_PFIX(8)
 #undef SWEEP_EXTERN_PFIX
+#define SWEEP_EXTERN_DIFMAG(K) extern template hipError_t launch0_difmag<K>(SweepArgs &, const SweepDifmag &, int, int, bool, hipStream_t);
+SWEEP_EXTERN_DIFMAG(0) SWEEP_EXTERN_DIFMAG(1) SWEEP_EXTERN_DIFMAG(2) SWEEP_EXTERN_DIFMAG(3) SWEEP_EXTERN_DIFMAG(7) SWEEP_EXTERN_DIFMAG(8)
+#undef SWEEP_EXTERN_DIFMAG
 #endif
 #endif
 
@@ -1772,6 +2123,26 @@ hipError_t launch_godunov_sweep_pfix(SweepArgs &A, const SweepPfix &X, int slope
     case 3: return launch0_pfix<3>(A, X, riemann, nvar, grav, s);
     case 7: return launch0_pfix<7>(A, X, riemann, nvar, grav, s);
     case 8: return launch0_pfix<8>(A, X, riemann, nvar, grav, s);
+#endif
+  }
+  return hipErrorInvalidValue;
+}
+#endif
+
+#ifndef RAMSES_AMD_FAST
+// interior rows of a work item of the difmag sweep of a level in tiles: the 8-row kernels for every NVAR and slope type
+int tile_sweep_rows_difmag(int nvar, int slope_type) { (void)nvar; (void)slope_type; return 8 - 4; }
+
+hipError_t launch_godunov_sweep_difmag(SweepArgs &A, const SweepDifmag &D, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
+  if ((unsigned long)A.pitch_var * 8ul >= (1ul << 31)) return hipErrorInvalidValue;      // lane offsets into a cell vector
+  switch (slope_type) {
+    case 1: return launch0_difmag<1>(A, D, riemann, nvar, grav, s);
+#ifndef SWEEP_FLAGSHIP_ONLY
+    case 0: return launch0_difmag<0>(A, D, riemann, nvar, grav, s);
+    case 2: return launch0_difmag<2>(A, D, riemann, nvar, grav, s);
+    case 3: return launch0_difmag<3>(A, D, riemann, nvar, grav, s);
+    case 7: return launch0_difmag<7>(A, D, riemann, nvar, grav, s);
+    case 8: return launch0_difmag<8>(A, D, riemann, nvar, grav, s);
 #endif
   }
   return hipErrorInvalidValue;

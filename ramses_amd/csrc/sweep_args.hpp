@@ -61,6 +61,12 @@ struct SweepPfix {
   double *divu = nullptr, *enew = nullptr;
 };
 
+// difmag > 0 on a level in tiles (launch_godunov_sweep_difmag, launch_surface_flux_difmag): the coefficient of the artificial
+// diffusion (csrc/difmag_core.hpp).  Beside SweepArgs / SurfArgs, not inside, for the same reason.
+struct SweepDifmag {
+  double difmag = 0.0;
+};
+
 // The surface pass of the sweep of a level in tiles (hydro/godunov_fine.f90:798-908): the fluxes an updated cell exchanges with
 // a GHOST cell (an oct the level does not have, interpolated by the pre-pass) are owed to the leaf cell of the coarser level
 // behind that oct face.  One thread per (event = (oct of the list, face) with such a neighbour, fine face q): it rebuilds the
@@ -99,6 +105,11 @@ int tile_sweep_rows(int riemann, int nvar, int slope_type, int scheme);
 hipError_t launch_surface_flux_pfix(const SurfArgs &A, int slope_type, int riemann, int nvar, bool grav, hipStream_t s);
 hipError_t launch_godunov_sweep_pfix(SweepArgs &A, const SweepPfix &X, int slope_type, int riemann, int nvar, bool grav, hipStream_t s);
 int tile_sweep_rows_pfix(int nvar, int slope_type);
+// difmag > 0 on a level in tiles: strict arithmetic only (the term exists in the reference's operation order only), muscl, no
+// pressure_fix, NVAR 5 .. 7, slope types 0 - 3, 7, 8.  The surface pass files the fluxes with the diffusive term.
+hipError_t launch_surface_flux_difmag(const SurfArgs &A, const SweepDifmag &D, int slope_type, int riemann, int nvar, bool grav, hipStream_t s);
+hipError_t launch_godunov_sweep_difmag(SweepArgs &A, const SweepDifmag &D, int slope_type, int riemann, int nvar, bool grav, hipStream_t s);
+int tile_sweep_rows_difmag(int nvar, int slope_type);
 }
 namespace fastmode {
 // NENER = nener (1, 2) non-thermal energies, the plain brick, muscl, no gravity

@@ -190,7 +190,7 @@ subroutine godunov_fine(ilevel)
   if(ncpu>1.or.nboundary>0)amr_level=.true.
   ! the dense brick entry points cover a box with nx=ny=nz=1; other coarse grids walk the tree
   if(nx_loc/=1.or.jcoarse_max/=jcoarse_min.or.kcoarse_max/=kcoarse_min)amr_level=.true.
-  ! artificial diffusion (cmpdivu + consup) is implemented in the tree-walking sweep only
+  ! artificial diffusion (cmpdivu + consup) is implemented on the AMR path only: the dense sweep of a level in tiles, or the tree walker
   if(difmag>0.0d0)amr_level=.true.
   ! so are the divu/enew updates of pressure_fix
   if(pressure_fix)amr_level=.true.

@@ -1369,6 +1369,13 @@ contains
              write(*,*) 'ramses_amd: dense sweep arithmetic = fast (<= 1e-12 of the reference; RAMSES_AMD_STRICT=1: bit-identical)'
              ! (divu / enew ride through the dense sweep in the reference's operation order only: csrc/capi_amr.hip tile_level_sweep)
              if (pressure_fix) write(*,*) 'ramses_amd: pressure_fix: AMR levels in tiles are swept in strict arithmetic (bit-identical)'
+             ! (so does the artificial diffusion: cmpdivu / consup, csrc/difmag_core.hpp)
+             ! (opt-in: RAMSES_AMD_DIFMAG_TILES=1, csrc/capi_amr.hip tile_level_sweep; without it a difmag run walks the tree)
+             if (difmag > 0.0d0) then
+                call get_environment_variable('RAMSES_AMD_DIFMAG_TILES', val, status=stat)
+                if (stat == 0 .and. trim(val) == '1') &
+                     & write(*,*) 'ramses_amd: difmag: AMR levels in tiles are swept in strict arithmetic (bit-identical)'
+             end if
           else
              write(*,*) 'ramses_amd: dense sweep arithmetic = strict (bit-identical to the reference)'
           end if

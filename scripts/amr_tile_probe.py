@@ -1,7 +1,9 @@
 """ramses_amd_amrres_godunov of a level in tiles, for rocprofv3 --kernel-trace --stats:  python scripts/amr_tile_probe.py [level] [kind] [steps]
 --pfix (anywhere on the line): the same level with pressure_fix, through a loop of its own over the public calls (bench.py knows
 nothing of pressure_fix); kinds "covered" and "shell" (= bench.py's "partial"); RAMSES_AMD_TILE_SWEEP=0 selects the tree-walking
-sweep for the comparison, RAMSES_AMD_PROBE_PFIX=0 times the same loop without pressure_fix."""
+sweep for the comparison, RAMSES_AMD_PROBE_PFIX=0 times the same loop without pressure_fix.
+--difmag X: the same loop with difmag = X and no pressure_fix (X = 0: the loop without either, the level's plain sweep in tiles);
+--nvar N (5 .. 7) with --pfix / --difmag: N - 5 passive scalars."""
 import ctypes as C
 import json
 import os
@@ -11,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
 
-def pfix_probe(level, kind, steps, riemann="llf"):
+def pfix_probe(level, kind, steps, riemann="llf", difmag=None, nvar=5):
     """level `level` complete with level + 1 in a spherical shell ("covered"), or level `level` in a spherical shell over a
     complete level - 1 ("shell"): trees as bench.amr_resident_bench builds them; HIP events around ramses_amd_amrres_godunov"""
     import numpy as np
@@ -30,17 +32,18 @@ def pfix_probe(level, kind, steps, riemann="llf"):
     lists = [np.ascontiguousarray(T["igrid"]), np.ascontiguousarray(T["igrid_fine"])]
     ncells = 8 * len(igrid)
     dx = 0.5 / 2 ** level
-    u = np.zeros((5, T["ncell"]))
+    u = np.zeros((nvar, T["ncell"]))       # (passive scalars beyond 5: zero)
     u[0] = 1.0
     u[4] = 1e-5 / 0.4
     u[4, T["ncoarse"] + int(igrid[0]) - 1] = (1e-5 + 0.4 * 0.125 / dx ** 3) / 0.4
     vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
     L = lib()
-    pfix = os.environ.get("RAMSES_AMD_PROBE_PFIX", "1") != "0"
+    pfix = os.environ.get("RAMSES_AMD_PROBE_PFIX", "1") != "0" and difmag is None
     os.environ.setdefault("RAMSES_AMD_TILE_MIN_OCTS", "0")
-    p = ramses_amd.make_params(courant_factor=0.8, riemann=riemann)
+    os.environ.setdefault("RAMSES_AMD_DIFMAG_TILES", "1")       # (opt-in in production; RAMSES_AMD_TILE_SWEEP=0 still selects the tree walker)
+    p = ramses_amd.make_params(courant_factor=0.8, riemann=riemann, difmag=difmag or 0.0, nvar=nvar)
     check(L.ramses_amd_amrres_invalidate())
-    check(L.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], vp(u), vp(T["son"]), vp(T["nbor"]), vp(T["father"])))
+    check(L.ramses_amd_amrres_load(nvar, T["ngridmax"], T["ncoarse"], vp(u), vp(T["son"]), vp(T["nbor"]), vp(T["father"])))
     if pfix:
         check(L.ramses_amd_amrres_enable_pfix())
     t0, w0 = L.ramses_amd_amrres_tile_sweeps(), L.ramses_amd_amrres_tree_sweeps()
@@ -68,7 +71,7 @@ def pfix_probe(level, kind, steps, riemann="llf"):
         b.record()
         torch.cuda.synchronize()
         times.append(a.elapsed_time(b))
-    out = {"pressure_fix": pfix, "level": level, "kind": kind, "riemann": riemann, "cells": ncells,
+    out = {"pressure_fix": pfix, "difmag": difmag or 0.0, "nvar": nvar, "level": level, "kind": kind, "riemann": riemann, "cells": ncells,
            "ms_per_sweep": sorted(times)[len(times) // 2], "ms_all": [round(t, 4) for t in times],
            "tile_sweeps": int(L.ramses_amd_amrres_tile_sweeps() - t0), "tree_sweeps": int(L.ramses_amd_amrres_tree_sweeps() - w0),
            "levels_in_tiles": int(L.ramses_amd_amrres_tiled_levels())}
@@ -78,13 +81,23 @@ def pfix_probe(level, kind, steps, riemann="llf"):
 
 if __name__ == "__main__":
     args = [a for a in sys.argv[1:] if a != "--pfix"]
+    difmag = None
+    if "--difmag" in args:
+        k = args.index("--difmag")
+        difmag = float(args[k + 1])
+        del args[k:k + 2]
+    nvar = 5
+    if "--nvar" in args:
+        k = args.index("--nvar")
+        nvar = int(args[k + 1])
+        del args[k:k + 2]
     level = int(args[0]) if len(args) > 0 else 8
     kind = args[1] if len(args) > 1 else "covered"
     steps = int(args[2]) if len(args) > 2 else 5
     import torch
     torch.cuda.init()
-    if "--pfix" in sys.argv[1:]:
-        print(json.dumps(pfix_probe(level, {"partial": "shell"}.get(kind, kind), steps, os.environ.get("RAMSES_AMD_BENCH_AMR_RIEMANN", "llf"))))
+    if "--pfix" in sys.argv[1:] or difmag is not None:
+        print(json.dumps(pfix_probe(level, {"partial": "shell"}.get(kind, kind), steps, os.environ.get("RAMSES_AMD_BENCH_AMR_RIEMANN", "llf"), difmag, nvar)))
     else:
         out = bench.amr_resident_bench(level, steps=steps, kind=kind)
         print(json.dumps({k: out[k] for k in ("ms_per_sweep", "tree_walking_ms_per_sweep", "cells", "workload")}))
