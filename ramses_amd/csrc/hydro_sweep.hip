@@ -24,6 +24,8 @@
 // contraction, rcp/rsq-based division and square root, fused LLF).
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "difmag_core.hpp"
 #include "hydro_core.hpp"
 #include "sweep_args.hpp"
@@ -1539,204 +1541,130 @@ __global__ __launch_bounds__(128) void surface_flux_difmag_kernel(SurfArgs A, Sw
 #endif
 #undef SURFACE_FLUX_BODY
 
-template <int ST, int RS, int NV, int SCHEME = 0>
-static hipError_t surface2(const SurfArgs &A, bool grav, hipStream_t s) {
-  const dim3 grid((unsigned)(((long)A.nevent * 4 + 127) / 128)), block(128);
-  if (grav) hipLaunchKernelGGL((surface_flux_kernel<ST, RS, NV, true, SCHEME>), grid, block, 0, s, A);
-  else hipLaunchKernelGGL((surface_flux_kernel<ST, RS, NV, false, SCHEME>), grid, block, 0, s, A);
-  return hipGetLastError();
-}
-template <int ST, int RS>
-static hipError_t surface1(const SurfArgs &A, int nvar, int scheme, bool grav, hipStream_t s) {
-  if constexpr (ST == 4 || ST == 5 || ST == 6) {
-    return hipErrorInvalidValue;
-  } else {
-#ifndef SWEEP_FLAGSHIP_ONLY
-    if (scheme == 1) return nvar == 5 ? surface2<ST, RS, 5, 1>(A, grav, s) : hipErrorInvalidValue;
-#endif
-    if (scheme != 0) return hipErrorInvalidValue;
-    if (nvar == 5) return surface2<ST, RS, 5>(A, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    if (nvar == 6) return surface2<ST, RS, 6>(A, grav, s);
-    if (nvar == 7) return surface2<ST, RS, 7>(A, grav, s);
-#endif
-    return hipErrorInvalidValue;
-  }
-}
-template <int ST>
-hipError_t surface0(const SurfArgs &A, int rs, int nvar, int scheme, bool grav, hipStream_t s) {
-  switch (rs) {
-    case RIEMANN_LLF: return surface1<ST, RIEMANN_LLF>(A, nvar, scheme, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case RIEMANN_HLLC: return surface1<ST, RIEMANN_HLLC>(A, nvar, scheme, grav, s);
-    case RIEMANN_HLL: return surface1<ST, RIEMANN_HLL>(A, nvar, scheme, grav, s);
-    case RIEMANN_ACOUSTIC: return surface1<ST, RIEMANN_ACOUSTIC>(A, nvar, scheme, grav, s);
-    case RIEMANN_EXACT: return surface1<ST, RIEMANN_EXACT>(A, nvar, scheme, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
-}
-#ifndef RAMSES_AMD_FAST
-// pressure_fix: muscl, NVAR 5 .. 7, every solver
-template <int ST, int RS, int NV>
-static hipError_t surface_pfix2(const SurfArgs &A, bool grav, hipStream_t s) {
-  const dim3 grid((unsigned)(((long)A.nevent * 4 + 127) / 128)), block(128);
-  if (grav) hipLaunchKernelGGL((surface_flux_pfix_kernel<ST, RS, NV, true>), grid, block, 0, s, A);
-  else hipLaunchKernelGGL((surface_flux_pfix_kernel<ST, RS, NV, false>), grid, block, 0, s, A);
-  return hipGetLastError();
-}
-template <int ST, int RS>
-static hipError_t surface_pfix1(const SurfArgs &A, int nvar, bool grav, hipStream_t s) {
-  if constexpr (ST == 4 || ST == 5 || ST == 6) {
-    return hipErrorInvalidValue;
-  } else {
-    if (nvar == 5) return surface_pfix2<ST, RS, 5>(A, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    if (nvar == 6) return surface_pfix2<ST, RS, 6>(A, grav, s);
-    if (nvar == 7) return surface_pfix2<ST, RS, 7>(A, grav, s);
-#endif
-    return hipErrorInvalidValue;
-  }
-}
-template <int ST>
-hipError_t surface0_pfix(const SurfArgs &A, int rs, int nvar, bool grav, hipStream_t s) {
-  switch (rs) {
-    case RIEMANN_LLF: return surface_pfix1<ST, RIEMANN_LLF>(A, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case RIEMANN_HLLC: return surface_pfix1<ST, RIEMANN_HLLC>(A, nvar, grav, s);
-    case RIEMANN_HLL: return surface_pfix1<ST, RIEMANN_HLL>(A, nvar, grav, s);
-    case RIEMANN_ACOUSTIC: return surface_pfix1<ST, RIEMANN_ACOUSTIC>(A, nvar, grav, s);
-    case RIEMANN_EXACT: return surface_pfix1<ST, RIEMANN_EXACT>(A, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
-}
-// difmag > 0: muscl, NVAR 5 .. 7, every solver
-template <int ST, int RS, int NV>
-static hipError_t surface_difmag2(const SurfArgs &A, const SweepDifmag &D, bool grav, hipStream_t s) {
-  const dim3 grid((unsigned)(((long)A.nevent * 4 + 127) / 128)), block(128);
-  if (grav) hipLaunchKernelGGL((surface_flux_difmag_kernel<ST, RS, NV, true>), grid, block, 0, s, A, D);
-  else hipLaunchKernelGGL((surface_flux_difmag_kernel<ST, RS, NV, false>), grid, block, 0, s, A, D);
-  return hipGetLastError();
-}
-template <int ST, int RS>
-static hipError_t surface_difmag1(const SurfArgs &A, const SweepDifmag &D, int nvar, bool grav, hipStream_t s) {
-  if constexpr (ST == 4 || ST == 5 || ST == 6) {
-    return hipErrorInvalidValue;
-  } else {
-    if (nvar == 5) return surface_difmag2<ST, RS, 5>(A, D, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    if (nvar == 6) return surface_difmag2<ST, RS, 6>(A, D, grav, s);
-    if (nvar == 7) return surface_difmag2<ST, RS, 7>(A, D, grav, s);
-#endif
-    return hipErrorInvalidValue;
-  }
-}
-template <int ST>
-hipError_t surface0_difmag(const SurfArgs &A, const SweepDifmag &D, int rs, int nvar, bool grav, hipStream_t s) {
-  switch (rs) {
-    case RIEMANN_LLF: return surface_difmag1<ST, RIEMANN_LLF>(A, D, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case RIEMANN_HLLC: return surface_difmag1<ST, RIEMANN_HLLC>(A, D, nvar, grav, s);
-    case RIEMANN_HLL: return surface_difmag1<ST, RIEMANN_HLL>(A, D, nvar, grav, s);
-    case RIEMANN_ACOUSTIC: return surface_difmag1<ST, RIEMANN_ACOUSTIC>(A, D, nvar, grav, s);
-    case RIEMANN_EXACT: return surface_difmag1<ST, RIEMANN_EXACT>(A, D, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
-}
-#endif
-// One translation unit per slope type (ramses_amd/build.py compiles this file once without SWEEP_ST -- the dispatchers -- and once
-// per slope type with -DSWEEP_ST=<type>, 3 standing for 3, 4, 5 and 6, for each arithmetic: the instantiations of the option
-// matrix build side by side instead of in two nine-minute compiles; the variant builds of scripts/build_variant.sh --
-// SWEEP_FLAGSHIP_ONLY -- keep one unit)
-#if defined(SWEEP_ST)
-template hipError_t surface0<SWEEP_ST>(const SurfArgs &, int, int, int, bool, hipStream_t);
-#ifndef RAMSES_AMD_FAST
-template hipError_t surface0_pfix<SWEEP_ST>(const SurfArgs &, int, int, bool, hipStream_t);
-template hipError_t surface0_difmag<SWEEP_ST>(const SurfArgs &, const SweepDifmag &, int, int, bool, hipStream_t);
-#endif
-#elif !defined(SWEEP_FLAGSHIP_ONLY)
-#define SWEEP_EXTERN_ST(K) extern template hipError_t surface0<K>(const SurfArgs &, int, int, int, bool, hipStream_t);
-SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
-#undef SWEEP_EXTERN_ST
-#ifndef RAMSES_AMD_FAST
-#define SWEEP_EXTERN_ST(K) extern template hipError_t surface0_pfix<K>(const SurfArgs &, int, int, bool, hipStream_t);
-SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
-#undef SWEEP_EXTERN_ST
-#define SWEEP_EXTERN_ST(K) extern template hipError_t surface0_difmag<K>(const SurfArgs &, const SweepDifmag &, int, int, bool, hipStream_t);
-SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
-#undef SWEEP_EXTERN_ST
-#endif
-#endif
-#ifndef SWEEP_ST
-hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, int nvar, int scheme, bool grav, hipStream_t s) {
-  if (A.nevent <= 0) return hipSuccess;
-  switch (slope_type) {
-    case 1: return surface0<1>(A, riemann, nvar, scheme, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case 0: return surface0<0>(A, riemann, nvar, scheme, grav, s);
-    case 2: return surface0<2>(A, riemann, nvar, scheme, grav, s);
-    case 3: return surface0<3>(A, riemann, nvar, scheme, grav, s);
-    case 7: return surface0<7>(A, riemann, nvar, scheme, grav, s);
-    case 8: return surface0<8>(A, riemann, nvar, scheme, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
-}
-#ifndef RAMSES_AMD_FAST
-hipError_t launch_surface_flux_pfix(const SurfArgs &A, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
-  if (A.nevent <= 0) return hipSuccess;
-  switch (slope_type) {
-    case 1: return surface0_pfix<1>(A, riemann, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case 0: return surface0_pfix<0>(A, riemann, nvar, grav, s);
-    case 2: return surface0_pfix<2>(A, riemann, nvar, grav, s);
-    case 3: return surface0_pfix<3>(A, riemann, nvar, grav, s);
-    case 7: return surface0_pfix<7>(A, riemann, nvar, grav, s);
-    case 8: return surface0_pfix<8>(A, riemann, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
-}
-hipError_t launch_surface_flux_difmag(const SurfArgs &A, const SweepDifmag &D, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
-  if (A.nevent <= 0) return hipSuccess;
-  switch (slope_type) {
-    case 1: return surface0_difmag<1>(A, D, riemann, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case 0: return surface0_difmag<0>(A, D, riemann, nvar, grav, s);
-    case 2: return surface0_difmag<2>(A, D, riemann, nvar, grav, s);
-    case 3: return surface0_difmag<3>(A, D, riemann, nvar, grav, s);
-    case 7: return surface0_difmag<7>(A, D, riemann, nvar, grav, s);
-    case 8: return surface0_difmag<8>(A, D, riemann, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
-}
-#endif
-#endif   // SWEEP_ST
-
 // ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
-template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, bool MASK = false>
-static hipError_t launch3(const SweepArgs &A, hipStream_t s) {
-  typedef Lds<ST, BY, NV, MASK, GRAV, 0, y_duty<ST, RS, BY, GRAV, SCHEME, NV, MASK>()> L;
-  static_assert(L::bytes <= 160 * 1024, "one workgroup's LDS");
-  const size_t lds = L::bytes;
-  dim3 block(BX, BY);
-  dim3 grid(A.nblocks);
-  auto k = godunov_sweep_kernel<ST, RS, BY, GRAV, SCHEME, NV, MASK>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, grid, block, lds, s, A);
-  return hipGetLastError();
+// The runtime options of a call -- slope type, solver, NVAR, scheme, gravity, tile rows, NENER, brick or tiles -- become template
+// arguments in one way: pick(v, IntList<...>(), f) calls f(std::integral_constant<int, V>()) for the V of the list that equals v
+// and returns hipErrorInvalidValue when there is none; pick(b, f) does the same for a bool.  The lists below are the option
+// matrix -- a value that is in no list has no kernel -- and a family is its preconditions, its Lds<...> and its kernel.
+// (tests/test_sweep_dispatch_host.py holds, from a CPU run, which kernel every combination of options launches)
+template <int... V>
+struct IntList {};
+template <int... V, class F>
+static hipError_t pick(int v, IntList<V...>, F &&f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)(... || (v == V && ((e = f(std::integral_constant<int, V>())), true)));
+  return e;
+}
+template <class F>
+static hipError_t pick(bool b, F &&f) {
+  return b ? f(std::true_type()) : f(std::false_type());
+}
+template <int... A, int... B>
+IntList<A..., B...> operator+(IntList<A...>, IntList<B...>);      // (two lists in a row; declared only, for decltype)
+
+#ifndef SWEEP_FLAGSHIP_ONLY
+using Slopes3D = IntList<1, 0, 2, 3, 7, 8>;
+using Slopes1D = IntList<4, 5, 6>;                         // the NDIM=1 slope types: the plain sweep only
+using Solvers = IntList<RIEMANN_LLF, RIEMANN_HLLC, RIEMANN_HLL, RIEMANN_ACOUSTIC, RIEMANN_EXACT>;
+using Nvars = IntList<5, 6, 7>;
+using Schemes = IntList<0, 1>;                             // muscl, plmde
+#else
+// (scripts/build_variant.sh, scripts/sweep_regs.sh, build_ab.py: minmod, LLF, NVAR 5, muscl only -- a one-minute compile)
+using Slopes3D = IntList<1>;
+using Slopes1D = IntList<>;
+using Solvers = IntList<RIEMANN_LLF>;
+using Nvars = IntList<5>;
+using Schemes = IntList<0>;
+#endif
+constexpr bool is_1d(int st) { return st == 4 || st == 5 || st == 6; }
+// (every family but the plain sweep picks its solver here: nothing for the NDIM=1 slope types)
+template <int ST>
+using SolversOf = std::conditional_t<is_1d(ST), IntList<>, Solvers>;
+// the (solver, NVAR, gravity) of a call: f(RS, NV, GRAV)
+template <class RSList, class F>
+static hipError_t pick_variant(RSList, int rs, int nvar, bool grav, F &&f) {
+  return pick(rs, RSList(), [&](auto r) { return pick(nvar, Nvars(), [&](auto nv) { return pick(grav, [&](auto g) { return f(r, nv, g); }); }); });
 }
 
-template <int ST, int RS, int BY, int SCHEME, int NV>
-static hipError_t launch2(const SweepArgs &A, bool grav, hipStream_t s) {
-  return grav ? launch3<ST, RS, BY, true, SCHEME, NV>(A, s) : launch3<ST, RS, BY, false, SCHEME, NV>(A, s);
+// Rows of the workgroup that sweeps a variant: 8 (two waves per SIMD, 256 VGPRs, smaller LDS planes) for the register/LDS-hungry
+// ones -- the Newton solver, the 27-point slope, the PLMDE tracing, runs with passive scalars --, else 12 on the brick and
+// TILE_SWEEP_BY on a level in tiles.  THE rule: the launchers choose kernels by it, the instantiations that exist follow from it
+// (sweep_variant), and the plan of csrc/capi_amr.hip cuts the work items of a level by it (tile_sweep_rows).
+constexpr int sweep_rows(int st, int rs, int nv, int scheme, bool tiles) {
+  if (rs == RIEMANN_EXACT || st == 3 || scheme != 0 || nv != 5) return 8;
+  if (tiles) return TILE_SWEEP_BY;
+  return is_1d(st) ? 8 : 12;
 }
+// the godunov_sweep_kernel instantiations that exist
+constexpr bool sweep_variant(int st, int rs, int by, bool grav, int scheme, int nv, bool tiles) {
+  // NDIM=1 slope types: the plain configuration only (the reference's 1-D tests: NVAR=3 embedded as 5, muscl, no gravity)
+  if (is_1d(st) && (grav || scheme != 0 || nv != 5 || tiles)) return false;
+  if (scheme == 1 && nv != 5) return false;                // plmde: the hydro variables only
+  return by == sweep_rows(st, rs, nv, scheme, tiles) || (by == 8 && !tiles);      // (the brick has every variant in 8 rows too)
+}
+// NENER > 0: LLF, HLL, HLLC
+constexpr bool nener_solver(int rs) { return rs == RIEMANN_LLF || rs == RIEMANN_HLL || rs == RIEMANN_HLLC; }
+
+template <class K, class... Args>
+static hipError_t launch_kernel(K k, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args &...args) {
+  if (lds > 0) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k, grid, block, lds, s, args...);
+  return hipGetLastError();
+}
+// the surface pass: one thread per (event, fine face)
+template <class K, class... Args>
+static hipError_t launch_surface(K k, hipStream_t s, const SurfArgs &A, const Args &...args) {
+  return launch_kernel(k, dim3((unsigned)(((long)A.nevent * 4 + 127) / 128)), dim3(128), 0, s, A, args...);
+}
+
+// The entry points of one slope type.  One translation unit per slope type (ramses_amd/build.py compiles this file once without
+// SWEEP_ST -- the dispatchers at the end -- and once per slope type with -DSWEEP_ST=<type>, 3 standing for 3, 4, 5 and 6, for
+// each arithmetic: the instantiations of the option matrix build side by side instead of in two nine-minute compiles; the
+// variant builds of scripts/build_variant.sh -- SWEEP_FLAGSHIP_ONLY -- keep one unit)
+template <int ST>
+struct SweepOf {
+  static hipError_t sweep(SweepArgs &A, int rs, int by, int scheme, int nvar, bool grav, hipStream_t s);
+  static hipError_t nener(SweepArgs &A, int rs, int nvar, int nener, hipStream_t s);
+  static hipError_t scalars(SweepArgs &A, int rs, int by, int nvar, int nener, bool grav, hipStream_t s);
+  static hipError_t surface(const SurfArgs &A, int rs, int nvar, int scheme, bool grav, hipStream_t s);
+#ifndef RAMSES_AMD_FAST
+  // pressure_fix, difmag > 0: a level in tiles, muscl, NVAR 5 .. 7, every solver
+  static hipError_t pfix(SweepArgs &A, const SweepPfix &X, int rs, int nvar, bool grav, hipStream_t s);
+  static hipError_t difmag(SweepArgs &A, const SweepDifmag &D, int rs, int nvar, bool grav, hipStream_t s);
+  static hipError_t surface_pfix(const SurfArgs &A, int rs, int nvar, bool grav, hipStream_t s);
+  static hipError_t surface_difmag(const SurfArgs &A, const SweepDifmag &D, int rs, int nvar, bool grav, hipStream_t s);
+#endif
+};
+
+template <int ST>
+hipError_t SweepOf<ST>::surface(const SurfArgs &A, int rs, int nvar, int scheme, bool grav, hipStream_t s) {
+  return pick_variant(SolversOf<ST>(), rs, nvar, grav, [&](auto r, auto nv, auto g) {
+    return pick(scheme, Schemes(), [&](auto sc) {
+      constexpr int RS = decltype(r)::value, NV = decltype(nv)::value, SCHEME = decltype(sc)::value;
+      if constexpr (SCHEME == 1 && NV != 5) return hipErrorInvalidValue;
+      else return launch_surface(surface_flux_kernel<ST, RS, NV, decltype(g)::value, SCHEME>, s, A);
+    });
+  });
+}
+#ifndef RAMSES_AMD_FAST
+template <int ST>
+hipError_t SweepOf<ST>::surface_pfix(const SurfArgs &A, int rs, int nvar, bool grav, hipStream_t s) {
+  return pick_variant(SolversOf<ST>(), rs, nvar, grav, [&](auto r, auto nv, auto g) {
+    return launch_surface(surface_flux_pfix_kernel<ST, decltype(r)::value, decltype(nv)::value, decltype(g)::value>, s, A);
+  });
+}
+template <int ST>
+hipError_t SweepOf<ST>::surface_difmag(const SurfArgs &A, const SweepDifmag &D, int rs, int nvar, bool grav, hipStream_t s) {
+  return pick_variant(SolversOf<ST>(), rs, nvar, grav, [&](auto r, auto nv, auto g) {
+    return launch_surface(surface_flux_difmag_kernel<ST, decltype(r)::value, decltype(nv)::value, decltype(g)::value>, s, A, D);
+  });
+}
+#endif
 
 // tiles of the whole brick, then the boxes this launch covers (A.region); 0 = nothing to sweep, -1 = bad region
 static int plan_boxes(SweepArgs &A, int by) {
@@ -1781,216 +1709,100 @@ static int plan_boxes(SweepArgs &A, int by) {
   return nblocks;
 }
 
-template <int ST, int RS>
-static hipError_t launch1(SweepArgs &A, int by, int scheme, int nvar, bool grav, hipStream_t s) {
-  // 8-row tiles (2 waves/SIMD, 256 VGPRs, smaller LDS planes) for the
-  // register/LDS-hungry variants: the Newton solver, the 27-point slope, the
-  // PLMDE tracing and runs with passive scalars
-  const bool heavy = (RS == RIEMANN_EXACT) || (ST == 3) || (ST == 4) || (ST == 5) || (ST == 6) || (scheme != 0) || (nvar != 5);
-  if (by == 0 || heavy) by = heavy ? 8 : 12;
-  const int planned = plan_boxes(A, by);
-  if (planned < 0) return hipErrorInvalidValue;
-  if (planned == 0) return hipSuccess;
-  if (A.stat) {
-    // a level of a resident AMR run in tiles: the 12-row muscl kernels on the periodic box of the level, one workgroup per
-    // work item (anything else: the caller keeps the tree-walking sweep)
-    if constexpr (ST != 4 && ST != 5 && ST != 6) {
-      if (!A.dir || !A.work || A.ng != 0 || (scheme != 0 && scheme != 1) || A.nwork <= 0) return hipErrorInvalidValue;
-      A.nblocks = A.nwork;
-      A.nbox = 1;          // (the box decode runs, its result is replaced by the work item)
-      // the plan's work items were cut for tile_sweep_rows(...) interior rows: 8 (12-row workgroups), or 4 for the variants that
-      // need 256 registers -- the Newton solver, the 27-point slope, the PLMDE tracing, runs with passive scalars (round 6)
-      if (by == 8) {
-        if (scheme == 1) {
-          if (nvar != 5) return hipErrorInvalidValue;
-          return grav ? launch3<ST, RS, 8, true, 1, 5, true>(A, s) : launch3<ST, RS, 8, false, 1, 5, true>(A, s);
-        }
-        if (nvar == 5) {
-          if constexpr (RS == RIEMANN_EXACT || ST == 3) return grav ? launch3<ST, RS, 8, true, 0, 5, true>(A, s) : launch3<ST, RS, 8, false, 0, 5, true>(A, s);
-          else return hipErrorInvalidValue;
-        }
-        if (nvar == 6) return grav ? launch3<ST, RS, 8, true, 0, 6, true>(A, s) : launch3<ST, RS, 8, false, 0, 6, true>(A, s);
-        if (nvar == 7) return grav ? launch3<ST, RS, 8, true, 0, 7, true>(A, s) : launch3<ST, RS, 8, false, 0, 7, true>(A, s);
-        return hipErrorInvalidValue;
-      }
-      if constexpr (RS != RIEMANN_EXACT && ST != 3) {
-        if (by == TILE_SWEEP_BY && nvar == 5 && scheme == 0)
-          return grav ? launch3<ST, RS, TILE_SWEEP_BY, true, 0, 5, true>(A, s) : launch3<ST, RS, TILE_SWEEP_BY, false, 0, 5, true>(A, s);
-      }
-      return hipErrorInvalidValue;
-    } else {
-      return hipErrorInvalidValue;
-    }
-  }
-  if constexpr (ST == 4 || ST == 5 || ST == 6) {
-    // NDIM=1 slope types: the plain configuration only (the reference's 1-D tests: NVAR=3 embedded as 5, muscl, no gravity)
-    if (nvar != 5 || scheme != 0 || grav) return hipErrorInvalidValue;
-    return launch3<ST, RS, 8, false, 0, 5>(A, s);
-  } else {
-    if (nvar == 6) return scheme == 0 ? launch2<ST, RS, 8, 0, 6>(A, grav, s) : hipErrorInvalidValue;
-    if (nvar == 7) return scheme == 0 ? launch2<ST, RS, 8, 0, 7>(A, grav, s) : hipErrorInvalidValue;
-    if (nvar != 5) return hipErrorInvalidValue;
-    if (scheme == 1) return launch2<ST, RS, 8, 1, 5>(A, grav, s);
-    if (by == 8) return launch2<ST, RS, 8, 0, 5>(A, grav, s);
-    if constexpr (ST != 3 && RS != RIEMANN_EXACT) {
-      if (by == 12) return launch2<ST, RS, 12, 0, 5>(A, grav, s);
-    }
+// a level of a resident AMR run in tiles: one workgroup per work item of the plan (the box decode runs, its result is replaced
+// by the work item)
+static bool tile_items(SweepArgs &A) {
+  if (!A.stat || !A.dir || !A.work || A.ng != 0 || A.nwork <= 0) return false;
+  A.nblocks = A.nwork;
+  A.nbox = 1;
+  return true;
+}
+
+template <int ST, int RS, int BY, bool GRAV, int SCHEME, int NV, bool MASK>
+static hipError_t launch_sweep(const SweepArgs &A, hipStream_t s) {
+  if constexpr (!sweep_variant(ST, RS, BY, GRAV, SCHEME, NV, MASK)) {
     return hipErrorInvalidValue;
+  } else {
+    typedef Lds<ST, BY, NV, MASK, GRAV, 0, y_duty<ST, RS, BY, GRAV, SCHEME, NV, MASK>()> L;
+    static_assert(L::bytes <= 160 * 1024, "one workgroup's LDS");
+    return launch_kernel(godunov_sweep_kernel<ST, RS, BY, GRAV, SCHEME, NV, MASK>, dim3(A.nblocks), dim3(BX, BY), L::bytes, s, A);
   }
+}
+// the brick (by = 8, 12 or 0: the rule's) or, with A.stat, a level in tiles (MASK; the plan's work items were cut for
+// tile_sweep_rows(...) interior rows; anything that has no kernel: the caller keeps the tree-walking sweep)
+template <int ST>
+hipError_t SweepOf<ST>::sweep(SweepArgs &A, int rs, int by, int scheme, int nvar, bool grav, hipStream_t s) {
+  return pick(rs, Solvers(), [&](auto r) {
+    constexpr int RS = decltype(r)::value;
+    const bool tiles = A.stat != nullptr;
+    const int rows = sweep_rows(ST, RS, nvar, scheme, tiles);
+    if (by == 0 || rows == 8) by = rows;
+    const int planned = plan_boxes(A, by);
+    if (planned < 0) return hipErrorInvalidValue;
+    if (planned == 0) return hipSuccess;
+    if (tiles) {
+      if (!tile_items(A)) return hipErrorInvalidValue;
+    } else if (!is_1d(ST) && nvar == 5 && scheme != 1) {
+      // (a scheme that is neither 0 nor 1 -- the C ABI passes no other -- runs as muscl in the 8-row tiles planned above: the
+      //  launcher has always taken it so, and the dispatch record holds it)
+      scheme = 0;
+    }
+    return pick(by, IntList<8, 12, TILE_SWEEP_BY>(), [&](auto b) { return pick(nvar, Nvars(), [&](auto nv) { return pick(scheme, Schemes(), [&](auto sc) {
+      return pick(grav, [&](auto g) { return pick(tiles, [&](auto m) {
+        return launch_sweep<ST, RS, decltype(b)::value, decltype(g)::value, decltype(sc)::value, decltype(nv)::value, decltype(m)::value>(A, s);
+      }); }); }); }); });
+  });
 }
 
 #ifndef RAMSES_AMD_FAST
-// pressure_fix on a level in tiles: one workgroup per work item of the plan (cut for tile_sweep_rows_pfix interior rows)
-template <int ST, int RS, bool GRAV, int NV>
-static hipError_t launch_pfix3(const SweepArgs &A, const SweepPfix &X, hipStream_t s) {
-  constexpr int BY = PfixRows<ST, NV>::BY;
-  const size_t lds = Lds<ST, BY, NV, true, GRAV, 2>::bytes;
-  auto k = godunov_sweep_pfix_kernel<ST, RS, BY, GRAV, NV>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(A.nblocks), dim3(BX, BY), lds, s, A, X);
-  return hipGetLastError();
-}
-template <int ST, int RS>
-static hipError_t launch_pfix1(SweepArgs &A, const SweepPfix &X, int nvar, bool grav, hipStream_t s) {
-  if constexpr (ST == 4 || ST == 5 || ST == 6) {
-    return hipErrorInvalidValue;
-  } else {
-    if (!A.stat || !A.dir || !A.work || !X.divu || !X.enew || A.ng != 0 || A.nwork <= 0) return hipErrorInvalidValue;
-    A.nblocks = A.nwork;
-    A.nbox = 1;          // (the box decode runs, its result is replaced by the work item)
-    A.box[0] = SweepBox{0, 1, 0, 1, 0, A.nz, A.nz, 0};
-    if (nvar == 5) return grav ? launch_pfix3<ST, RS, true, 5>(A, X, s) : launch_pfix3<ST, RS, false, 5>(A, X, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    if (nvar == 6) return grav ? launch_pfix3<ST, RS, true, 6>(A, X, s) : launch_pfix3<ST, RS, false, 6>(A, X, s);
-    if (nvar == 7) return grav ? launch_pfix3<ST, RS, true, 7>(A, X, s) : launch_pfix3<ST, RS, false, 7>(A, X, s);
-#endif
-    return hipErrorInvalidValue;
-  }
-}
+// pressure_fix on a level in tiles: the plan's work items were cut for tile_sweep_rows_pfix interior rows
 template <int ST>
-hipError_t launch0_pfix(SweepArgs &A, const SweepPfix &X, int rs, int nvar, bool grav, hipStream_t s) {
-  switch (rs) {
-    case RIEMANN_LLF: return launch_pfix1<ST, RIEMANN_LLF>(A, X, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case RIEMANN_HLLC: return launch_pfix1<ST, RIEMANN_HLLC>(A, X, nvar, grav, s);
-    case RIEMANN_HLL: return launch_pfix1<ST, RIEMANN_HLL>(A, X, nvar, grav, s);
-    case RIEMANN_ACOUSTIC: return launch_pfix1<ST, RIEMANN_ACOUSTIC>(A, X, nvar, grav, s);
-    case RIEMANN_EXACT: return launch_pfix1<ST, RIEMANN_EXACT>(A, X, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
+hipError_t SweepOf<ST>::pfix(SweepArgs &A, const SweepPfix &X, int rs, int nvar, bool grav, hipStream_t s) {
+  if (!X.divu || !X.enew || !tile_items(A)) return hipErrorInvalidValue;
+  A.box[0] = SweepBox{0, 1, 0, 1, 0, A.nz, A.nz, 0};
+  return pick_variant(SolversOf<ST>(), rs, nvar, grav, [&](auto r, auto nv, auto g) {
+    constexpr int RS = decltype(r)::value, NV = decltype(nv)::value, BY = PfixRows<ST, NV>::BY;
+    constexpr bool GRAV = decltype(g)::value;
+    return launch_kernel(godunov_sweep_pfix_kernel<ST, RS, BY, GRAV, NV>, dim3(A.nblocks), dim3(BX, BY), Lds<ST, BY, NV, true, GRAV, 2>::bytes, s, A, X);
+  });
 }
-#endif
-
-#ifndef RAMSES_AMD_FAST
-// difmag > 0 on a level in tiles: one workgroup per work item of the plan (cut for tile_sweep_rows_difmag interior rows)
-template <int ST, int RS, bool GRAV, int NV>
-static hipError_t launch_difmag3(const SweepArgs &A, const SweepDifmag &D, hipStream_t s) {
-  constexpr int BY = 8;
-  const size_t lds = Lds<ST, BY, NV, true, GRAV, 0, false, true, dif_parked<RS, NV>()>::bytes;
-  auto k = godunov_sweep_difmag_kernel<ST, RS, BY, GRAV, NV>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(A.nblocks), dim3(BX, BY), lds, s, A, D);
-  return hipGetLastError();
-}
-template <int ST, int RS>
-static hipError_t launch_difmag1(SweepArgs &A, const SweepDifmag &D, int nvar, bool grav, hipStream_t s) {
-  if constexpr (ST == 4 || ST == 5 || ST == 6) {
-    return hipErrorInvalidValue;
-  } else {
-    if (!A.stat || !A.dir || !A.work || !(D.difmag > 0.0) || A.ng != 0 || A.nwork <= 0) return hipErrorInvalidValue;
-    A.nblocks = A.nwork;
-    A.nbox = 1;          // (the box decode runs, its result is replaced by the work item)
-    A.box[0] = SweepBox{0, 1, 0, 1, 0, A.nz, A.nz, 0};
-    if (nvar == 5) return grav ? launch_difmag3<ST, RS, true, 5>(A, D, s) : launch_difmag3<ST, RS, false, 5>(A, D, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    if (nvar == 6) return grav ? launch_difmag3<ST, RS, true, 6>(A, D, s) : launch_difmag3<ST, RS, false, 6>(A, D, s);
-    if (nvar == 7) return grav ? launch_difmag3<ST, RS, true, 7>(A, D, s) : launch_difmag3<ST, RS, false, 7>(A, D, s);
-#endif
-    return hipErrorInvalidValue;
-  }
-}
+// difmag > 0 on a level in tiles: the plan's work items were cut for tile_sweep_rows_difmag interior rows
 template <int ST>
-hipError_t launch0_difmag(SweepArgs &A, const SweepDifmag &D, int rs, int nvar, bool grav, hipStream_t s) {
-  switch (rs) {
-    case RIEMANN_LLF: return launch_difmag1<ST, RIEMANN_LLF>(A, D, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case RIEMANN_HLLC: return launch_difmag1<ST, RIEMANN_HLLC>(A, D, nvar, grav, s);
-    case RIEMANN_HLL: return launch_difmag1<ST, RIEMANN_HLL>(A, D, nvar, grav, s);
-    case RIEMANN_ACOUSTIC: return launch_difmag1<ST, RIEMANN_ACOUSTIC>(A, D, nvar, grav, s);
-    case RIEMANN_EXACT: return launch_difmag1<ST, RIEMANN_EXACT>(A, D, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
+hipError_t SweepOf<ST>::difmag(SweepArgs &A, const SweepDifmag &D, int rs, int nvar, bool grav, hipStream_t s) {
+  if (!(D.difmag > 0.0) || !tile_items(A)) return hipErrorInvalidValue;
+  A.box[0] = SweepBox{0, 1, 0, 1, 0, A.nz, A.nz, 0};
+  return pick_variant(SolversOf<ST>(), rs, nvar, grav, [&](auto r, auto nv, auto g) {
+    constexpr int RS = decltype(r)::value, NV = decltype(nv)::value, BY = 8;
+    constexpr bool GRAV = decltype(g)::value;
+    return launch_kernel(godunov_sweep_difmag_kernel<ST, RS, BY, GRAV, NV>, dim3(A.nblocks), dim3(BX, BY),
+                         Lds<ST, BY, NV, true, GRAV, 0, false, true, dif_parked<RS, NV>()>::bytes, s, A, D);
+  });
 }
 #endif
 
 // NENER > 0: (NE, NV) = (1, 6), (1, 7) [one passive scalar], (2, 7); LLF, HLL, HLLC; muscl, no gravity, the plain brick
-template <int ST, int RS, int NV, int NE>
-static hipError_t launch_nener3(SweepArgs &A, hipStream_t s) {
-  const size_t lds = Lds<ST, 8, NV, false, false>::bytes;
-  auto k = godunov_sweep_nener_kernel<ST, RS, NV, NE>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(A.nblocks), dim3(BX, 8), lds, s, A);
-  return hipGetLastError();
-}
-template <int ST, int RS>
-static hipError_t launch_nener1(SweepArgs &A, int nvar, int nener, hipStream_t s) {
-  if (A.stat) return hipErrorInvalidValue;
-  const int planned = plan_boxes(A, 8);
-  if (planned < 0) return hipErrorInvalidValue;
-  if (planned == 0) return hipSuccess;
-  if (nener == 1 && nvar == 6) return launch_nener3<ST, RS, 6, 1>(A, s);
-  if (nener == 1 && nvar == 7) return launch_nener3<ST, RS, 7, 1>(A, s);
-  if (nener == 2 && nvar == 7) return launch_nener3<ST, RS, 7, 2>(A, s);
-  return hipErrorInvalidValue;
-}
 template <int ST>
-hipError_t launch0_nener(SweepArgs &A, int rs, int nvar, int nener, hipStream_t s) {
-  if constexpr (ST == 4 || ST == 5 || ST == 6) {
-    return hipErrorInvalidValue;
-  } else {
-    switch (rs) {
-      case RIEMANN_LLF: return launch_nener1<ST, RIEMANN_LLF>(A, nvar, nener, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-      case RIEMANN_HLLC: return launch_nener1<ST, RIEMANN_HLLC>(A, nvar, nener, s);
-      case RIEMANN_HLL: return launch_nener1<ST, RIEMANN_HLL>(A, nvar, nener, s);
-#endif
+hipError_t SweepOf<ST>::nener(SweepArgs &A, int rs, int nvar, int nener, hipStream_t s) {
+  return pick(rs, SolversOf<ST>(), [&](auto r) {
+    constexpr int RS = decltype(r)::value;
+    if constexpr (!nener_solver(RS)) {
+      return hipErrorInvalidValue;
+    } else {
+      if (A.stat) return hipErrorInvalidValue;
+      const int planned = plan_boxes(A, 8);
+      if (planned < 0) return hipErrorInvalidValue;
+      if (planned == 0) return hipSuccess;
+      return pick(nener, IntList<1, 2>(), [&](auto ne) { return pick(nvar, IntList<6, 7>(), [&](auto nv) {
+        constexpr int NE = decltype(ne)::value, NV = decltype(nv)::value;
+        if constexpr (NV < 5 + NE) return hipErrorInvalidValue;
+        else return launch_kernel(godunov_sweep_nener_kernel<ST, RS, NV, NE>, dim3(A.nblocks), dim3(BX, 8), Lds<ST, 8, NV, false, false>::bytes, s, A);
+      }); });
     }
-    return hipErrorInvalidValue;
-  }
+  });
 }
 
-// NVAR > 7: the scalar passes that follow the hydro pass (godunov_scalar_kernel), ceil(nscalars / G) launches of the whole
-// region; the last group may hold fewer than G scalars
-template <int ST, int RS, bool GRAV, int NE>
-static hipError_t launch_scalar3(const SweepArgs &A, int nvar, hipStream_t s) {
-  typedef ScalarGroup<ST, RS, NE> SG;
-  auto k = godunov_scalar_kernel<ST, RS, GRAV, NE>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SG::bytes);
-  if (e != hipSuccess) return e;
-  for (int s0 = SG::NH; s0 < nvar; s0 += SG::G) {
-    const int nlive = nvar - s0 < SG::G ? nvar - s0 : SG::G;
-    hipLaunchKernelGGL(k, dim3(A.nblocks), dim3(BX, 8), SG::bytes, s, A, s0, nlive);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-template <int ST, int RS>
-static hipError_t launch_scalar1(SweepArgs &A, int nvar, int nener, bool grav, hipStream_t s) {
-  if (nener == 0) return grav ? launch_scalar3<ST, RS, true, 0>(A, nvar, s) : launch_scalar3<ST, RS, false, 0>(A, nvar, s);
-  if constexpr (RS == RIEMANN_LLF || RS == RIEMANN_HLL || RS == RIEMANN_HLLC) {
-    if (grav) return hipErrorInvalidValue;
-    if (nener == 1) return launch_scalar3<ST, RS, false, 1>(A, nvar, s);
-    if (nener == 2) return launch_scalar3<ST, RS, false, 2>(A, nvar, s);
-  }
-  return hipErrorInvalidValue;
-}
 // The scalar pass updates exactly the cells that the hydro pass of the same region updated -- it reads their new density back
-// from unew -- so its boxes are planned in the hydro pass's tiles (launch1's rows: 12 or 8; the NENER kernels: 8) and re-cut
+// from unew -- so its boxes are planned in the hydro pass's tiles (sweep()'s rows: 12 or 8; the NENER kernels: 8) and re-cut
 // into its own 8-row tiles (4 interior rows; 8 = 2 x 4, so the cut is exact): a shell and an interior call each stand alone.
 static int plan_boxes_scalar(SweepArgs &A, int hydro_by) {
   const int planned = plan_boxes(A, hydro_by);
@@ -2009,178 +1821,103 @@ static int plan_boxes_scalar(SweepArgs &A, int hydro_by) {
   A.nblocks = nblocks;
   return nblocks;
 }
+// NVAR > 7: the scalar passes that follow the hydro pass (godunov_scalar_kernel), ceil(nscalars / G) launches of the whole
+// region; the last group may hold fewer than G scalars.  Gravity with nener = 0 only.
 template <int ST>
-hipError_t launch0_scalar(SweepArgs &A, int rs, int by, int nvar, int nener, bool grav, hipStream_t s) {
-  if constexpr (ST == 4 || ST == 5 || ST == 6) {
-    return hipErrorInvalidValue;
-  } else {
-    if (A.stat || nener < 0 || nener > MAX_NENER || nvar <= 7 || nvar > MAX_NVAR) return hipErrorInvalidValue;
-    const bool heavy = nener > 0 || rs == RIEMANN_EXACT || ST == 3;       // launch1 at NV = 5, muscl; launch_nener1
-    const int hydro_by = (by == 0 || heavy) ? (heavy ? 8 : 12) : by;
-    if (hydro_by != 8 && hydro_by != 12) return hipErrorInvalidValue;
-    const int planned = plan_boxes_scalar(A, hydro_by);
-    if (planned < 0) return hipErrorInvalidValue;
-    if (planned == 0) return hipSuccess;
-    switch (rs) {
-      case RIEMANN_LLF: return launch_scalar1<ST, RIEMANN_LLF>(A, nvar, nener, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-      case RIEMANN_HLLC: return launch_scalar1<ST, RIEMANN_HLLC>(A, nvar, nener, grav, s);
-      case RIEMANN_HLL: return launch_scalar1<ST, RIEMANN_HLL>(A, nvar, nener, grav, s);
-      case RIEMANN_ACOUSTIC: return launch_scalar1<ST, RIEMANN_ACOUSTIC>(A, nvar, nener, grav, s);
-      case RIEMANN_EXACT: return launch_scalar1<ST, RIEMANN_EXACT>(A, nvar, nener, grav, s);
-#endif
+hipError_t SweepOf<ST>::scalars(SweepArgs &A, int rs, int by, int nvar, int nener, bool grav, hipStream_t s) {
+  if (A.stat || nener < 0 || nener > MAX_NENER || nvar <= 7 || nvar > MAX_NVAR) return hipErrorInvalidValue;
+  const int rows = nener > 0 ? 8 : sweep_rows(ST, rs, 5, 0, false);          // of the hydro pass: sweep() at NV = 5, muscl; nener()
+  const int hydro_by = (by == 0 || rows == 8) ? rows : by;
+  if (hydro_by != 8 && hydro_by != 12) return hipErrorInvalidValue;
+  const int planned = plan_boxes_scalar(A, hydro_by);
+  if (planned < 0) return hipErrorInvalidValue;
+  if (planned == 0) return hipSuccess;
+  return pick(grav, [&](auto g) { return pick(rs, SolversOf<ST>(), [&](auto r) { return pick(nener, IntList<0, 1, 2>(), [&](auto ne) {
+    constexpr int RS = decltype(r)::value, NE = decltype(ne)::value;
+    constexpr bool GRAV = decltype(g)::value;
+    if constexpr (NE > 0 && (GRAV || !nener_solver(RS))) {
+      return hipErrorInvalidValue;
+    } else {
+      typedef ScalarGroup<ST, RS, NE> SG;
+      for (int s0 = SG::NH; s0 < nvar; s0 += SG::G) {
+        const int nlive = nvar - s0 < SG::G ? nvar - s0 : SG::G;
+        const hipError_t e = launch_kernel(godunov_scalar_kernel<ST, RS, GRAV, NE>, dim3(A.nblocks), dim3(BX, 8), SG::bytes, s, A, s0, nlive);
+        if (e != hipSuccess) return e;
+      }
+      return hipSuccess;
     }
-    return hipErrorInvalidValue;
-  }
-}
-
-template <int ST>
-hipError_t launch0(SweepArgs &A, int rs, int by, int scheme, int nvar, bool grav, hipStream_t s) {
-  switch (rs) {
-    case RIEMANN_LLF: return launch1<ST, RIEMANN_LLF>(A, by, scheme, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY   // (scripts/sweep_regs.sh, build_ab.py: the LLF + minmod instantiations only, a one-minute compile)
-    case RIEMANN_HLLC: return launch1<ST, RIEMANN_HLLC>(A, by, scheme, nvar, grav, s);
-    case RIEMANN_HLL: return launch1<ST, RIEMANN_HLL>(A, by, scheme, nvar, grav, s);
-    case RIEMANN_ACOUSTIC: return launch1<ST, RIEMANN_ACOUSTIC>(A, by, scheme, nvar, grav, s);
-    case RIEMANN_EXACT: return launch1<ST, RIEMANN_EXACT>(A, by, scheme, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
+  }); }); });
 }
 
 #if defined(SWEEP_ST)
-template hipError_t launch0<SWEEP_ST>(SweepArgs &, int, int, int, int, bool, hipStream_t);
-template hipError_t launch0_nener<SWEEP_ST>(SweepArgs &, int, int, int, hipStream_t);
-template hipError_t launch0_scalar<SWEEP_ST>(SweepArgs &, int, int, int, int, bool, hipStream_t);
-#ifndef RAMSES_AMD_FAST
-template hipError_t launch0_pfix<SWEEP_ST>(SweepArgs &, const SweepPfix &, int, int, bool, hipStream_t);
-template hipError_t launch0_difmag<SWEEP_ST>(SweepArgs &, const SweepDifmag &, int, int, bool, hipStream_t);
-#endif
+template struct SweepOf<SWEEP_ST>;
 #if SWEEP_ST == 3
-template hipError_t launch0<4>(SweepArgs &, int, int, int, int, bool, hipStream_t);
-template hipError_t launch0<5>(SweepArgs &, int, int, int, int, bool, hipStream_t);
-template hipError_t launch0<6>(SweepArgs &, int, int, int, int, bool, hipStream_t);
+template struct SweepOf<4>;
+template struct SweepOf<5>;
+template struct SweepOf<6>;
 #endif
 #elif !defined(SWEEP_FLAGSHIP_ONLY)
-#define SWEEP_EXTERN_ST(K) extern template hipError_t launch0<K>(SweepArgs &, int, int, int, int, bool, hipStream_t);
-SWEEP_EXTERN_ST(0) SWEEP_EXTERN_ST(1) SWEEP_EXTERN_ST(2) SWEEP_EXTERN_ST(3) SWEEP_EXTERN_ST(4) SWEEP_EXTERN_ST(5) SWEEP_EXTERN_ST(6)
-SWEEP_EXTERN_ST(7) SWEEP_EXTERN_ST(8)
-#undef SWEEP_EXTERN_ST
-#define SWEEP_EXTERN_NENER(K) extern template hipError_t launch0_nener<K>(SweepArgs &, int, int, int, hipStream_t);
-SWEEP_EXTERN_NENER(0) SWEEP_EXTERN_NENER(1) SWEEP_EXTERN_NENER(2) SWEEP_EXTERN_NENER(3) SWEEP_EXTERN_NENER(7) SWEEP_EXTERN_NENER(8)
-#undef SWEEP_EXTERN_NENER
-#define SWEEP_EXTERN_SCALAR(K) extern template hipError_t launch0_scalar<K>(SweepArgs &, int, int, int, int, bool, hipStream_t);
-SWEEP_EXTERN_SCALAR(0) SWEEP_EXTERN_SCALAR(1) SWEEP_EXTERN_SCALAR(2) SWEEP_EXTERN_SCALAR(3) SWEEP_EXTERN_SCALAR(7) SWEEP_EXTERN_SCALAR(8)
-#undef SWEEP_EXTERN_SCALAR
-#ifndef RAMSES_AMD_FAST
-#define SWEEP_EXTERN_PFIX(K) extern template hipError_t launch0_pfix<K>(SweepArgs &, const SweepPfix &, int, int, bool, hipStream_t);
-SWEEP_EXTERN_PFIX(0) SWEEP_EXTERN_PFIX(1) SWEEP_EXTERN_PFIX(2) SWEEP_EXTERN_PFIX(3) SWEEP_EXTERN_PFIX(7) SWEEP_EXTERN_PFIX(8)
-#undef SWEEP_EXTERN_PFIX
-#define SWEEP_EXTERN_DIFMAG(K) extern template hipError_t launch0_difmag<K>(SweepArgs &, const SweepDifmag &, int, int, bool, hipStream_t);
-SWEEP_EXTERN_DIFMAG(0) SWEEP_EXTERN_DIFMAG(1) SWEEP_EXTERN_DIFMAG(2) SWEEP_EXTERN_DIFMAG(3) SWEEP_EXTERN_DIFMAG(7) SWEEP_EXTERN_DIFMAG(8)
-#undef SWEEP_EXTERN_DIFMAG
-#endif
+extern template struct SweepOf<0>;
+extern template struct SweepOf<1>;
+extern template struct SweepOf<2>;
+extern template struct SweepOf<3>;
+extern template struct SweepOf<4>;
+extern template struct SweepOf<5>;
+extern template struct SweepOf<6>;
+extern template struct SweepOf<7>;
+extern template struct SweepOf<8>;
 #endif
 
 #ifndef SWEEP_ST
-// interior rows of a work item of the sweep of a level in tiles (the plan of csrc/capi_amr.hip cuts the level accordingly)
-int tile_sweep_rows(int riemann, int nvar, int slope_type, int scheme) {
-  return ((riemann == RIEMANN_EXACT || nvar != 5 || slope_type == 3 || scheme != 0) ? 8 : TILE_SWEEP_BY) - 4;
+// the public launchers (csrc/sweep_args.hpp): what does not depend on the variant, then the slope type
+// (lanes address a plane of the brick with a 32-bit byte offset; a cell vector of a level in tiles likewise)
+static bool brick_offsets_fit(const SweepArgs &A) {
+  return (unsigned long)A.pitch_z * 8ul < (1ul << 31) && (unsigned long)A.pitch_var * 8ul < (1ul << 32);
 }
+static bool tile_offsets_fit(const SweepArgs &A) { return (unsigned long)A.pitch_var * 8ul < (1ul << 31); }
 
 hipError_t launch_godunov_sweep(SweepArgs &A, int slope_type, int riemann, int by, int scheme, int nvar,
                                 bool grav, hipStream_t s) {
-  // lanes address a plane with a 32-bit byte offset
-  if ((unsigned long)A.pitch_z * 8ul >= (1ul << 31) || (unsigned long)A.pitch_var * 8ul >= (1ul << 32))
-    return hipErrorInvalidValue;
-  switch (slope_type) {
-    case 1: return launch0<1>(A, riemann, by, scheme, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case 0: return launch0<0>(A, riemann, by, scheme, nvar, grav, s);
-    case 2: return launch0<2>(A, riemann, by, scheme, nvar, grav, s);
-    case 3: return launch0<3>(A, riemann, by, scheme, nvar, grav, s);
-    case 4: return launch0<4>(A, riemann, by, scheme, nvar, grav, s);
-    case 5: return launch0<5>(A, riemann, by, scheme, nvar, grav, s);
-    case 6: return launch0<6>(A, riemann, by, scheme, nvar, grav, s);
-    case 7: return launch0<7>(A, riemann, by, scheme, nvar, grav, s);
-    case 8: return launch0<8>(A, riemann, by, scheme, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
+  if (!brick_offsets_fit(A)) return hipErrorInvalidValue;
+  return pick(slope_type, decltype(Slopes3D() + Slopes1D())(), [&](auto st) { return SweepOf<decltype(st)::value>::sweep(A, riemann, by, scheme, nvar, grav, s); });
 }
-
-#ifndef RAMSES_AMD_FAST
-// interior rows of a work item of the pressure_fix sweep of a level in tiles
-int tile_sweep_rows_pfix(int nvar, int slope_type) { return ((slope_type == 3 && nvar == 7) ? 6 : 8) - 4; }
-
-hipError_t launch_godunov_sweep_pfix(SweepArgs &A, const SweepPfix &X, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
-  if ((unsigned long)A.pitch_var * 8ul >= (1ul << 31)) return hipErrorInvalidValue;      // lane offsets into a cell vector
-  switch (slope_type) {
-    case 1: return launch0_pfix<1>(A, X, riemann, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case 0: return launch0_pfix<0>(A, X, riemann, nvar, grav, s);
-    case 2: return launch0_pfix<2>(A, X, riemann, nvar, grav, s);
-    case 3: return launch0_pfix<3>(A, X, riemann, nvar, grav, s);
-    case 7: return launch0_pfix<7>(A, X, riemann, nvar, grav, s);
-    case 8: return launch0_pfix<8>(A, X, riemann, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
-}
-#endif
-
-#ifndef RAMSES_AMD_FAST
-// interior rows of a work item of the difmag sweep of a level in tiles: the 8-row kernels for every NVAR and slope type
-int tile_sweep_rows_difmag(int nvar, int slope_type) { (void)nvar; (void)slope_type; return 8 - 4; }
-
-hipError_t launch_godunov_sweep_difmag(SweepArgs &A, const SweepDifmag &D, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
-  if ((unsigned long)A.pitch_var * 8ul >= (1ul << 31)) return hipErrorInvalidValue;      // lane offsets into a cell vector
-  switch (slope_type) {
-    case 1: return launch0_difmag<1>(A, D, riemann, nvar, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case 0: return launch0_difmag<0>(A, D, riemann, nvar, grav, s);
-    case 2: return launch0_difmag<2>(A, D, riemann, nvar, grav, s);
-    case 3: return launch0_difmag<3>(A, D, riemann, nvar, grav, s);
-    case 7: return launch0_difmag<7>(A, D, riemann, nvar, grav, s);
-    case 8: return launch0_difmag<8>(A, D, riemann, nvar, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
-}
-#endif
-
 hipError_t launch_godunov_sweep_nener(SweepArgs &A, int slope_type, int riemann, int nvar, int nener, hipStream_t s) {
-  if ((unsigned long)A.pitch_z * 8ul >= (1ul << 31) || (unsigned long)A.pitch_var * 8ul >= (1ul << 32))
-    return hipErrorInvalidValue;
-  switch (slope_type) {
-    case 1: return launch0_nener<1>(A, riemann, nvar, nener, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case 0: return launch0_nener<0>(A, riemann, nvar, nener, s);
-    case 2: return launch0_nener<2>(A, riemann, nvar, nener, s);
-    case 3: return launch0_nener<3>(A, riemann, nvar, nener, s);
-    case 7: return launch0_nener<7>(A, riemann, nvar, nener, s);
-    case 8: return launch0_nener<8>(A, riemann, nvar, nener, s);
-#endif
-  }
-  return hipErrorInvalidValue;
+  if (!brick_offsets_fit(A)) return hipErrorInvalidValue;
+  return pick(slope_type, Slopes3D(), [&](auto st) { return SweepOf<decltype(st)::value>::nener(A, riemann, nvar, nener, s); });
 }
-
 hipError_t launch_godunov_sweep_scalars(SweepArgs &A, int slope_type, int riemann, int by, int nvar, int nener, bool grav, hipStream_t s) {
-  if ((unsigned long)A.pitch_z * 8ul >= (1ul << 31) || (unsigned long)A.pitch_var * 8ul >= (1ul << 32))
-    return hipErrorInvalidValue;
-  switch (slope_type) {
-    case 1: return launch0_scalar<1>(A, riemann, by, nvar, nener, grav, s);
-#ifndef SWEEP_FLAGSHIP_ONLY
-    case 0: return launch0_scalar<0>(A, riemann, by, nvar, nener, grav, s);
-    case 2: return launch0_scalar<2>(A, riemann, by, nvar, nener, grav, s);
-    case 3: return launch0_scalar<3>(A, riemann, by, nvar, nener, grav, s);
-    case 7: return launch0_scalar<7>(A, riemann, by, nvar, nener, grav, s);
-    case 8: return launch0_scalar<8>(A, riemann, by, nvar, nener, grav, s);
-#endif
-  }
-  return hipErrorInvalidValue;
+  if (!brick_offsets_fit(A)) return hipErrorInvalidValue;
+  return pick(slope_type, Slopes3D(), [&](auto st) { return SweepOf<decltype(st)::value>::scalars(A, riemann, by, nvar, nener, grav, s); });
 }
+hipError_t launch_surface_flux(const SurfArgs &A, int slope_type, int riemann, int nvar, int scheme, bool grav, hipStream_t s) {
+  if (A.nevent <= 0) return hipSuccess;
+  return pick(slope_type, Slopes3D(), [&](auto st) { return SweepOf<decltype(st)::value>::surface(A, riemann, nvar, scheme, grav, s); });
+}
+// interior rows of a work item of the sweep of a level in tiles (the plan of csrc/capi_amr.hip cuts the level accordingly)
+int tile_sweep_rows(int riemann, int nvar, int slope_type, int scheme) { return sweep_rows(slope_type, riemann, nvar, scheme, true) - 4; }
 
+#ifndef RAMSES_AMD_FAST
+hipError_t launch_godunov_sweep_pfix(SweepArgs &A, const SweepPfix &X, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
+  if (!tile_offsets_fit(A)) return hipErrorInvalidValue;
+  return pick(slope_type, Slopes3D(), [&](auto st) { return SweepOf<decltype(st)::value>::pfix(A, X, riemann, nvar, grav, s); });
+}
+hipError_t launch_godunov_sweep_difmag(SweepArgs &A, const SweepDifmag &D, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
+  if (!tile_offsets_fit(A)) return hipErrorInvalidValue;
+  return pick(slope_type, Slopes3D(), [&](auto st) { return SweepOf<decltype(st)::value>::difmag(A, D, riemann, nvar, grav, s); });
+}
+hipError_t launch_surface_flux_pfix(const SurfArgs &A, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
+  if (A.nevent <= 0) return hipSuccess;
+  return pick(slope_type, Slopes3D(), [&](auto st) { return SweepOf<decltype(st)::value>::surface_pfix(A, riemann, nvar, grav, s); });
+}
+hipError_t launch_surface_flux_difmag(const SurfArgs &A, const SweepDifmag &D, int slope_type, int riemann, int nvar, bool grav, hipStream_t s) {
+  if (A.nevent <= 0) return hipSuccess;
+  return pick(slope_type, Slopes3D(), [&](auto st) { return SweepOf<decltype(st)::value>::surface_difmag(A, D, riemann, nvar, grav, s); });
+}
+// interior rows of a work item of the pressure_fix sweep of a level in tiles (PfixRows), and of the difmag sweep: the 8-row
+// kernels for every NVAR and slope type
+int tile_sweep_rows_pfix(int nvar, int slope_type) { return ((slope_type == 3 && nvar == 7) ? 6 : 8) - 4; }
+int tile_sweep_rows_difmag(int nvar, int slope_type) { (void)nvar; (void)slope_type; return 8 - 4; }
+#endif
 #endif   // SWEEP_ST
 
 }  // namespace SWEEP_NS

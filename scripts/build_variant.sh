@@ -1,7 +1,9 @@
 #!/bin/bash
 # scripts/build_variant.sh TAG "-DFLAG ..." : ramses_amd/lib/ab/libramses_amd_TAG.so with the LLF + minmod instantiations of the
 # sweep only (a ten-second compile; for kernel tuning with scripts/amr_tile_probe.py, RAMSES_AMD_LIB=...), the other objects
-# from the regular build
+# from the regular build.  SWEEP_FLAGSHIP_ONLY shortens the option lists of csrc/hydro_sweep.hip's dispatch: slope type 1, LLF,
+# NVAR 5 and muscl in every kernel family, the plain sweep included; the NENER and scalar-pass kernels of that slope type and
+# solver stay.
 set -e
 cd "$(dirname "$0")/.."
 tag=$1; shift

@@ -20,7 +20,7 @@ def parse(path):
                 funcs[name] = body
                 name = None
             elif line.strip():
-                body.append(re.sub(r"\.L(BB|tmp|func_begin|func_end)?\d+(_\d+)?", ".L", line.strip()))
+                body.append(re.sub(r"\.L(BB|tmp|func_begin|func_end|post_getpc)?\d+(_\d+)?", ".L", line.strip()))
             continue
         m = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", line)
         if m:
