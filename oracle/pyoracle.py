@@ -41,7 +41,16 @@ def build_oracle():
 
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
+_ip = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _lib = None
+
+
+def _bind_godunov_fine_amr(L):
+    L.ora_godunov_fine_amr.argtypes = [C.POINTER(HydroParams), C.c_int, _ip, _ip, _ip, _ip, C.c_long, C.c_long,
+                                       _dp, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                       C.c_int, C.c_int, C.c_int]
+    L.ora_godunov_fine_amr.restype = None
+    return L
 
 
 def lib():
@@ -77,11 +86,7 @@ def lib():
         L.ora_interpol_hydro.restype = None
         L.ora_upl.argtypes = [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]
         L.ora_upl.restype = None
-        _ip = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
-        L.ora_godunov_fine_amr.argtypes = [C.POINTER(HydroParams), C.c_int, _ip, _ip, _ip, _ip, C.c_long, C.c_long,
-                                           _dp, _dp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
-                                           C.c_int, C.c_int, C.c_int]
-        L.ora_godunov_fine_amr.restype = None
+        _bind_godunov_fine_amr(L)
         for fn in (L.ora_mg_gauss_seidel, L.ora_mg_residual, L.ora_mg_restrict, L.ora_mg_interp_correct,
                    L.ora_gradient_phi_uniform):
             fn.restype = None
@@ -147,11 +152,12 @@ def courant_uniform(p, uold, dx, courant_factor, grav=None):
 
 
 def godunov_fine_amr(p, igrid, son, nbor, father, ngridmax, ncoarse, uold, unew, dx, dt, nvector,
-                     interpol_var, interpol_type, f=None, divu=None, enew=None):
+                     interpol_var, interpol_type, f=None, divu=None, enew=None, library=None):
     """godunov_fine(ilevel) on an AMR level, on the reference's tree arrays (1-based indices);
-    unew (and divu, enew when given) are updated in place."""
+    unew (and divu, enew when given) are updated in place.  library: the path of another build of the oracle's
+    sources (scripts/oracle_branch_coverage.py: the one with coverage counters) instead of liboracle.so."""
     vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None  # noqa: E731
-    lib().ora_godunov_fine_amr(C.byref(p), len(igrid), np.ascontiguousarray(igrid, np.int32),
+    (lib() if library is None else _bind_godunov_fine_amr(C.CDLL(library))).ora_godunov_fine_amr(C.byref(p), len(igrid), np.ascontiguousarray(igrid, np.int32),
                                np.ascontiguousarray(son, np.int32), np.ascontiguousarray(nbor, np.int32),
                                np.ascontiguousarray(father, np.int32), ngridmax, ncoarse,
                                np.ascontiguousarray(uold), unew, vp(f), vp(divu), vp(enew), dx, dt, nvector,

@@ -3,7 +3,7 @@ CPU oracle (itself pinned bit-exact against the reference's unsplit)."""
 import numpy as np
 import pytest
 
-from helpers import random_brick, rel_linf
+from helpers import _set_uold_scalar_fix, random_brick, rel_linf
 
 pytestmark = pytest.mark.gpu
 
@@ -133,18 +133,6 @@ def test_sedov_steps_match_oracle(gpu_lib, oracle):
     known = [3.076e-05, 6.877e-05, 7.752e-05, 9.857e-05]
     for a, b in zip(dts, known):
         assert abs(a - b) <= 5e-4 * b, (dts, known)
-
-
-def _set_uold_scalar_fix(uold, unew, smallr):
-    """numpy restatement of the passive-scalar floor fix of set_uold
-    (hydro/godunov_fine.f90:176-190); test-side only."""
-    out = unew.copy()
-    a = (uold[0] < smallr) & (unew[0] > uold[0])
-    b = ~a & (unew[0] < smallr) & (uold[0] > unew[0])
-    for n in range(5, unew.shape[0]):
-        out[n][a] = (uold[n] * np.maximum(unew[0], smallr) / smallr)[a]
-        out[n][b] = (uold[n] * smallr / np.maximum(uold[0], smallr))[b]
-    return out
 
 
 @pytest.mark.parametrize("nvar", [6, 7])
