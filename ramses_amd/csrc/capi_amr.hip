@@ -256,21 +256,6 @@ __global__ __launch_bounds__(256) void lvl_flag_kernel(LvlArgs A, FlagCrit F, in
   }
 }
 
-// compact buffer buf[v][ind*ngrid+i] <-> cell vector (sync_level / load_level)
-template <bool GATHER>
-__global__ __launch_bounds__(256) void lvl_pack_kernel(LvlArgs A, double *__restrict__ buf) {
-  const long total = (long)A.ngrid * 8;
-  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const long c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
-    for (int v = 0; v < A.nvar; v++) {
-      if (GATHER) buf[(long)v * total + t] = A.uold[c + (long)v * A.ncell];
-      else A.uold[c + (long)v * A.ncell] = buf[(long)v * total + t];
-    }
-  }
-}
-
-
 // synchro_hydro_fine (hydro/synchro_hydro_fine.f90:5-136): momentum kick d*f*dteff with the kinetic energy taken out of
 // and put back into the total energy, on the level's cells
 __global__ __launch_bounds__(256) void lvl_synchro_kernel(LvlArgs A, const double *__restrict__ f, double dteff, double smallr) {
@@ -787,9 +772,29 @@ struct CommLevel {
 #ifndef EVENT_QMINOR_DEFAULT
 #define EVENT_QMINOR_DEFAULT 1      // RAMSES_AMD_EVENT_LANES=q: the four fine faces of an event in neighbouring lanes; e: 64 events of one fine face
 #endif
+// The fingerprint of a host oct list: its length, first and last entry and ten entries spread over it.  (Contract of the C ABI: an
+// oct list does not change between two calls of ramses_amd_amrres_tree other than as a whole -- it is active(ilevel)%igrid, which
+// only build_comm / refine_fine / load_balance rewrite.)  The list cache and the plan cache both rest on it; `h`, the array itself,
+// is NOT part of the comparison: the list cache asks for it on top, a plan does not care where the list lives.
+struct ListPrint {
+  const int *h = nullptr;
+  int n = -1, first = 0, last = 0;
+  int sample[10] = {0};
+  static ListPrint of(const int *igrid, int n) {
+    ListPrint F;
+    F.h = igrid; F.n = n;
+    if (n > 0) {
+      F.first = igrid[0]; F.last = igrid[n - 1];
+      for (int k = 0; k < 10; k++) F.sample[k] = igrid[(long)k * (n - 1) / 9];
+    }
+    return F;
+  }
+  bool operator==(const ListPrint &o) const { return n == o.n && first == o.first && last == o.last && memcmp(sample, o.sample, sizeof(sample)) == 0; }
+};
+
 struct LevelPlan {
-  int version = -1, ngrid = -1, ig_first = 0, ig_last = 0;      // the layout version of the level and the list the plan was made for
-  int ig_sample[10] = {0};                                        // (ten entries of it, spread over the list: the fingerprint of the list cache)
+  int version = -1;                                               // the layout version of the level ...
+  ListPrint list;                                                 // ... and the list the plan was made for
   int nghost = 0, nwork = 0, nevent = 0;
   int rows = 0;                                                   // interior rows of its work items (8, or 4 for the 8-row kernels)
   Buf gfather, gslot, gcell, gsten, work, corr, corr_tgt, evt_of, flag, events;
@@ -813,7 +818,7 @@ struct AmrRes {
   Buf stat, octpos, bad;                       // status byte per device cell; device oct -> position in the list of its level's plan; bad-index counter
   // the oct lists of the levels as they last arrived, translated: a level's list (active(ilevel)%igrid) comes down with every
   // routine of a step and changes only with the tree
-  struct ListSlot { const int *h = nullptr; int n = 0, serial = -1; int sample[10] = {0}; Buf dev, sorted, tmp; bool has_sorted = false; long stamp = 0; };
+  struct ListSlot { ListPrint print; int serial = -1; Buf dev, sorted, tmp; bool has_sorted = false; long stamp = 0; };
   ListSlot *cur_slot = nullptr;
   ListSlot lcache[16];
   long lstamp = 0;
@@ -896,18 +901,33 @@ int check_lists(AmrRes &R, const char *where) {
   }
   return 0;
 }
+// hipcub's radix sort on the key bits [0, end_bit), keys only or (key, value) pairs, in its two calls: the size query, then the sort
+// in the scratch buffer `tmp`, grown to that size
+template <class K>
+int radix_sort(Buf &tmp, const K *kin, K *kout, int n, int end_bit, hipStream_t s) {
+  size_t bytes = 0;
+  HCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, kin, kout, n, 0, end_bit, s), "sort");
+  HCHK(tmp.ensure(bytes), "hipMalloc");
+  HCHK(hipcub::DeviceRadixSort::SortKeys(tmp.p, bytes, kin, kout, n, 0, end_bit, s), "sort");
+  return 0;
+}
+template <class K, class V>
+int radix_sort(Buf &tmp, const K *kin, K *kout, const V *vin, V *vout, int n, int end_bit, hipStream_t s) {
+  size_t bytes = 0;
+  HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, kin, kout, vin, vout, n, 0, end_bit, s), "sort");
+  HCHK(tmp.ensure(bytes), "hipMalloc");
+  HCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, bytes, kin, kout, vin, vout, n, 0, end_bit, s), "sort");
+  return 0;
+}
 // The list of the routine under way in ascending DEVICE order, for the kernels whose result does not depend on the order of
 // the list (copies, source terms, restriction): neighbouring threads then touch neighbouring octs of a tile -- the host's
 // order is the order of creation, which the device numbering scatters.
 int sorted_list(AmrRes &R, LvlArgs &A) {
   AmrRes::ListSlot *S = R.cur_slot;
-  if (!R.map.on || !S || S->n < 2 || !env_on("RAMSES_AMD_SORTED_LISTS")) return 0;
+  if (!R.map.on || !S || S->print.n < 2 || !env_on("RAMSES_AMD_SORTED_LISTS")) return 0;
   if (!S->has_sorted) {
-    HCHK(S->sorted.ensure(sizeof(int) * (size_t)S->n), "hipMalloc");
-    size_t bytes = 0;
-    HCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, S->dev.as<int>(), S->sorted.as<int>(), S->n, 0, 32, (hipStream_t) nullptr), "sort");
-    HCHK(S->tmp.ensure(bytes), "hipMalloc");
-    HCHK(hipcub::DeviceRadixSort::SortKeys(S->tmp.p, bytes, S->dev.as<int>(), S->sorted.as<int>(), S->n, 0, 32, (hipStream_t) nullptr), "sort");
+    HCHK(S->sorted.ensure(sizeof(int) * (size_t)S->print.n), "hipMalloc");
+    if (int rc = radix_sort(S->tmp, S->dev.as<int>(), S->sorted.as<int>(), S->print.n, 32, nullptr)) return rc;
     S->has_sorted = true;
   }
   A.igrid = S->sorted.as<int>();
@@ -920,17 +940,16 @@ int set_level(AmrRes &R, int ngrid, const int *igrid, LvlArgs &A) {
     // the same list as before (same array, length, layout; first, last and eight entries in between equal): already there.
     // (Contract of the C ABI: an oct list does not change between two calls of ramses_amd_amrres_tree other than as a whole.)
     AmrRes::ListSlot *hit = nullptr, *lru = &R.lcache[0];
-    int sample[10] = {0};
-    if (ngrid > 0) for (int k = 0; k < 10; k++) sample[k] = igrid[(long)k * (ngrid - 1) / 9];
+    const ListPrint print = ListPrint::of(igrid, ngrid);
     for (AmrRes::ListSlot &S : R.lcache) {
-      if (S.h == igrid && S.n == ngrid && S.serial == R.map.serial && ngrid > 0 && memcmp(S.sample, sample, sizeof(sample)) == 0) { hit = &S; break; }
+      if (S.print.h == igrid && S.serial == R.map.serial && ngrid > 0 && S.print == print) { hit = &S; break; }
       if (S.stamp < lru->stamp) lru = &S;
     }
     if (!hit || !env_on("RAMSES_AMD_LIST_CACHE")) {
       hit = lru;
       hit->serial = -1;
       if (int rc = upload_list(R, hit->dev, igrid, ngrid)) return rc;
-      hit->h = igrid; hit->n = ngrid; hit->serial = R.map.serial; memcpy(hit->sample, sample, sizeof(sample));
+      hit->print = print; hit->serial = R.map.serial;
       hit->has_sorted = false;
     }
     hit->stamp = ++R.lstamp;
@@ -941,6 +960,81 @@ int set_level(AmrRes &R, int ngrid, const int *igrid, LvlArgs &A) {
   A.son = R.son.as<int>(); A.nbor = R.nbor.as<int>(); A.igrid = R.cur_ig;
   A.ngrid = ngrid; A.nvar = R.nvar; A.ncell = R.ncell; A.ncoarse = R.ncoarse; A.ngridmax = R.ngridmax;
   return 0;
+}
+
+// ---- one level between a device vector and a host vector: EVERY such move goes through the three functions below -----------
+// The n octs of a list have two names: d_ig[i] on the device (device indices, strides R.ncell / R.ngridmax) and h_ig[i] on the
+// host (the caller's list as it came, strides R.ncell_h / R.ngh).  In between the cells travel packed, [ncomp][8][n].
+int xfer_hip(hipError_t e, const char *step, const char *what) { return e == hipSuccess ? 0 : failf(RAMSES_AMD_EHIP, "%s %s: %s", step, what, hipGetErrorString(e)); }
+#define XCHK(call, step) do { if (int rc_ = xfer_hip((call), step, what)) return rc_; } while (0)
+// the device half of the way home: gather into R.pack, blocking copy into R.hpack
+int level_fetch(AmrRes &R, double *dvec, int ncomp, const int *d_ig, int n, hipStream_t s, const char *what) {
+  const size_t cnt = (size_t)n * 8 * (size_t)ncomp;
+  XCHK(R.pack.ensure(sizeof(double) * cnt), "hipMalloc");
+  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8)), dim3(256), 0, s, dvec, R.pack.as<double>(), d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax);
+  XCHK(hipGetLastError(), "pack launch");
+  R.hpack.resize(cnt);
+  XCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H");
+  return 0;
+}
+// hvec(cells of the octs, 1:ncomp) = dvec(...); synchronous
+int level_to_host(AmrRes &R, double *dvec, int ncomp, const int *d_ig, int n, const int *h_ig, double *hvec, hipStream_t s, const char *what) {
+  if (int rc = level_fetch(R, dvec, ncomp, d_ig, n, s, what)) return rc;
+  for (int k = 0; k < ncomp; k++)
+    for (int ind = 0; ind < 8; ind++) {
+      double *dst = hvec + (size_t)k * R.ncell_h + R.ncoarse + (size_t)ind * R.ngh - 1;
+      const double *src = R.hpack.data() + ((size_t)k * 8 + ind) * n;
+      for (int i = 0; i < n; i++) dst[h_ig[i]] = src[i];
+    }
+  return 0;
+}
+// dvec(cells of the octs, 1:ncomp) = hvec(...); synchronous
+int level_from_host(AmrRes &R, double *dvec, int ncomp, const int *d_ig, int n, const int *h_ig, const double *hvec, const char *what) {
+  const size_t cnt = (size_t)n * 8 * (size_t)ncomp;
+  R.hpack.resize(cnt);
+  for (int k = 0; k < ncomp; k++)
+    for (int ind = 0; ind < 8; ind++) {
+      const double *src = hvec + (size_t)k * R.ncell_h + R.ncoarse + (size_t)ind * R.ngh - 1;
+      double *dst = R.hpack.data() + ((size_t)k * 8 + ind) * n;
+      for (int i = 0; i < n; i++) dst[i] = src[h_ig[i]];
+    }
+  XCHK(R.pack.ensure(sizeof(double) * cnt), "hipMalloc");
+  XCHK(hipMemcpy(R.pack.p, R.hpack.data(), sizeof(double) * cnt, hipMemcpyHostToDevice), "H2D");
+  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8)), dim3(256), 0, nullptr, dvec, R.pack.as<double>(), d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax);
+  XCHK(hipGetLastError(), "unpack launch");
+  XCHK(hipStreamSynchronize(nullptr), "sync");
+  return 0;
+}
+#undef XCHK
+
+// ---- one level-by-level move of a variable between the device's numbering (dvec) and the host's (staging, on the device too):
+// EVERY renumbering of cell data goes through here.  Asynchronous; the caller asks hipGetLastError
+template <bool TO_DEVICE>
+void move_levels(AmrRes &R, int l_first, int l_last, double *staging, double *dvec) {
+  for (int l = l_first; l <= l_last; l++) {
+    amrlayout::LevelMap &L = R.map.lev[l];
+    hipLaunchKernelGGL(amrlayout::move_var_kernel<TO_DEVICE>, dim3(amrlayout::grid1((long)L.n * 8)), dim3(256), 0, nullptr, L.hoct.as<int>(), L.doct.as<int>(), L.n,
+                       R.ncoarse, R.ngh, R.ngridmax, staging, dvec);
+  }
+}
+
+// the device's copy of the acceleration, zero until a level arrives (load_f, take_f_device)
+int ensure_f(AmrRes &R) {
+  if (R.grav) return 0;
+  HCHK(R.f.ensure(sizeof(double) * 3 * (size_t)R.ncell), "hipMalloc f");
+  HCHK(hipMemsetAsync(R.f.p, 0, sizeof(double) * 3 * (size_t)R.ncell, nullptr), "memset f");
+  R.grav = true;
+  return 0;
+}
+
+// what the plan_* kernels take: the tree, the tiles of the level and the list of the call (R.cur_ig)
+PlanArgs plan_args(AmrRes &R, amrlayout::LevelMap &L, int ngrid) {
+  PlanArgs A;
+  A.son = R.son.as<int>(); A.nbor = R.nbor.as<int>(); A.father = R.father.as<int>(); A.iperm = R.map.iperm.as<int>();
+  A.stat = R.stat.as<unsigned char>(); A.octpos = R.octpos.as<int>(); A.ig = R.cur_ig; A.n = ngrid;
+  A.ncell = R.ncell; A.ncoarse = R.ncoarse; A.ngd = R.ngridmax;
+  A.dir = L.dir.as<int>(); A.tileid = L.tileid.as<int>(); A.base = L.base; A.no = L.no; A.ntx = L.ntx; A.nty = L.nty; A.ntz = L.ntz;
+  return A;
 }
 }  // namespace
 
@@ -1001,32 +1095,20 @@ int ramses_amd_amrres_tree(const int *son, const int *nbor, const int *father) {
     const int nvec = 2 * R.nvar + (R.grav ? 3 : 0);
     Buf park;
     HCHK(park.ensure(sizeof(double) * (size_t)nvec * (size_t)R.ncell_h), "hipMalloc (parking the kept levels)");
-    auto vec_of = [&](int v, double *&dev) {          // device vector v of the parked set
-      if (v < R.nvar) dev = R.uold.as<double>() + (long)v * R.ncell;
-      else if (v < 2 * R.nvar) dev = R.unew.as<double>() + (long)(v - R.nvar) * R.ncell;
-      else dev = R.f.as<double>() + (long)(v - 2 * R.nvar) * R.ncell;
+    auto vec_of = [&](int v) {                        // device vector v of the parked set
+      if (v < R.nvar) return R.uold.as<double>() + (long)v * R.ncell;
+      if (v < 2 * R.nvar) return R.unew.as<double>() + (long)(v - R.nvar) * R.ncell;
+      return R.f.as<double>() + (long)(v - 2 * R.nvar) * R.ncell;
     };
-    for (int l = 1; l <= kept; l++) {
-      amrlayout::LevelMap &L = R.map.lev[l];
-      for (int v = 0; v < nvec; v++) {
-        double *dev; vec_of(v, dev);
-        hipLaunchKernelGGL(amrlayout::move_var_kernel<false>, dim3(amrlayout::grid1((long)L.n * 8)), dim3(256), 0, nullptr, L.hoct.as<int>(), L.doct.as<int>(), L.n,
-                           R.ncoarse, R.ngh, R.ngridmax, park.as<double>() + (long)v * R.ncell_h, dev);
-      }
-    }
+    for (int l = 1; l <= kept; l++)
+      for (int v = 0; v < nvec; v++) move_levels<false>(R, l, l, park.as<double>() + (long)v * R.ncell_h, vec_of(v));
     HCHK(hipGetLastError(), "parking the kept levels");
     HCHK(hipDeviceSynchronize(), "sync");
     R.map.forget();
     e = R.map.build(son, nbor, father, R.son.as<int>(), R.nbor.as<int>(), R.father.as<int>(), R.stat.as<unsigned char>(), nullptr);
     if (e == hipSuccess) {
-      for (int l = 1; l <= kept && l <= R.map.nlev; l++) {
-        amrlayout::LevelMap &L = R.map.lev[l];
-        for (int v = 0; v < nvec; v++) {
-          double *dev; vec_of(v, dev);
-          hipLaunchKernelGGL(amrlayout::move_var_kernel<true>, dim3(amrlayout::grid1((long)L.n * 8)), dim3(256), 0, nullptr, L.hoct.as<int>(), L.doct.as<int>(), L.n,
-                             R.ncoarse, R.ngh, R.ngridmax, park.as<double>() + (long)v * R.ncell_h, dev);
-        }
-      }
+      for (int l = 1; l <= kept && l <= R.map.nlev; l++)
+        for (int v = 0; v < nvec; v++) move_levels<true>(R, l, l, park.as<double>() + (long)v * R.ncell_h, vec_of(v));
       HCHK(hipGetLastError(), "restoring the kept levels");
       HCHK(hipDeviceSynchronize(), "sync");
       R.relayouts++;
@@ -1089,11 +1171,7 @@ int ramses_amd_amrres_load(int nvar, int64_t ngridmax, int64_t ncoarse, const do
     for (int v = 0; v < nvar; v++) {
       HCHK(hipMemcpyAsync(R.work.p, uold + (size_t)v * R.ncell_h, sizeof(double) * (size_t)R.ncell_h, hipMemcpyHostToDevice, nullptr), "H2D uold");
       HCHK(hipMemcpyAsync(R.uold.as<double>() + (size_t)v * R.ncell, R.work.p, sizeof(double) * (size_t)ncoarse, hipMemcpyDeviceToDevice, nullptr), "coarse cells");
-      for (int l = 1; l <= R.map.nlev; l++) {
-        amrlayout::LevelMap &L = R.map.lev[l];
-        hipLaunchKernelGGL(amrlayout::move_var_kernel<true>, dim3(amrlayout::grid1((long)L.n * 8)), dim3(256), 0, nullptr, L.hoct.as<int>(), L.doct.as<int>(), L.n,
-                           R.ncoarse, R.ngh, R.ngridmax, R.work.as<double>(), R.uold.as<double>() + (size_t)v * R.ncell);
-      }
+      move_levels<true>(R, 1, R.map.nlev, R.work.as<double>(), R.uold.as<double>() + (size_t)v * R.ncell);
     }
     HCHK(hipGetLastError(), "uold into the device's numbering");
   }
@@ -1114,19 +1192,7 @@ int ramses_amd_amrres_sync_level(int ngrid, const int *igrid, double *uold) {
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (uold != R.h_uold) return failf(RAMSES_AMD_EINVAL, "sync_level: not the array the state was loaded from");
   if (ngrid == 0) return 0;
-  const size_t n = (size_t)ngrid * 8 * R.nvar;
-  HCHK(R.pack.ensure(sizeof(double) * n), "hipMalloc");
-  hipLaunchKernelGGL(lvl_pack_kernel<true>, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, A, R.pack.as<double>());
-  HCHK(hipGetLastError(), "pack launch");
-  R.hpack.resize(n);
-  HCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * n, hipMemcpyDeviceToHost), "D2H level");
-  const long tot = (long)ngrid * 8;
-  for (int v = 0; v < R.nvar; v++)
-    for (int ind = 0; ind < 8; ind++) {
-      double *dst = uold + (size_t)v * R.ncell_h + R.ncoarse + (size_t)ind * R.ngh - 1;
-      const double *src = R.hpack.data() + (size_t)v * tot + (size_t)ind * ngrid;
-      for (int i = 0; i < ngrid; i++) dst[igrid[i]] = src[i];
-    }
+  if (int rc = level_to_host(R, R.uold.as<double>(), R.nvar, R.cur_ig, ngrid, igrid, uold, nullptr, "level")) return rc;
   return check_lists(R, "sync_level");
 }
 
@@ -1136,21 +1202,7 @@ int ramses_amd_amrres_load_level(int ngrid, const int *igrid, const double *uold
   LvlArgs A;
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
-  const size_t n = (size_t)ngrid * 8 * R.nvar;
-  const long tot = (long)ngrid * 8;
-  R.hpack.resize(n);
-  for (int v = 0; v < R.nvar; v++)
-    for (int ind = 0; ind < 8; ind++) {
-      const double *src = uold + (size_t)v * R.ncell_h + R.ncoarse + (size_t)ind * R.ngh - 1;
-      double *dst = R.hpack.data() + (size_t)v * tot + (size_t)ind * ngrid;
-      for (int i = 0; i < ngrid; i++) dst[i] = src[igrid[i]];
-    }
-  HCHK(R.pack.ensure(sizeof(double) * n), "hipMalloc");
-  HCHK(hipMemcpy(R.pack.p, R.hpack.data(), sizeof(double) * n, hipMemcpyHostToDevice), "H2D level");
-  hipLaunchKernelGGL(lvl_pack_kernel<false>, dim3(grid_for(tot)), dim3(256), 0, nullptr, A, R.pack.as<double>());
-  HCHK(hipGetLastError(), "unpack launch");
-  HCHK(hipStreamSynchronize(nullptr), "sync");
-  return 0;
+  return level_from_host(R, R.uold.as<double>(), R.nvar, R.cur_ig, ngrid, igrid, uold, "level");
 }
 
 // the whole hydro state back (backup_hydro)
@@ -1169,11 +1221,7 @@ int ramses_amd_amrres_sync_all(double *uold) {
     double *hv = uold + (size_t)v * R.ncell_h;
     HCHK(hipMemcpyAsync(R.work.p, hv, sizeof(double) * (size_t)R.ncell_h, hipMemcpyHostToDevice, nullptr), "H2D staging");
     HCHK(hipMemcpyAsync(R.work.p, R.uold.as<double>() + (size_t)v * R.ncell, sizeof(double) * (size_t)R.ncoarse, hipMemcpyDeviceToDevice, nullptr), "coarse cells");
-    for (int l = 1; l <= R.map.nlev; l++) {
-      amrlayout::LevelMap &L = R.map.lev[l];
-      hipLaunchKernelGGL(amrlayout::move_var_kernel<false>, dim3(amrlayout::grid1((long)L.n * 8)), dim3(256), 0, nullptr, L.hoct.as<int>(), L.doct.as<int>(), L.n,
-                         R.ncoarse, R.ngh, R.ngridmax, R.work.as<double>(), R.uold.as<double>() + (size_t)v * R.ncell);
-    }
+    move_levels<false>(R, 1, R.map.nlev, R.work.as<double>(), R.uold.as<double>() + (size_t)v * R.ncell);
     HCHK(hipGetLastError(), "uold into the host's numbering");
     HCHK(hipMemcpy(hv, R.work.p, sizeof(double) * (size_t)R.ncell_h, hipMemcpyDeviceToHost), "D2H uold");
   }
@@ -1191,8 +1239,7 @@ int ramses_amd_amrres_set_unew(int ngrid, const int *igrid) {
 }
 
 int ramses_amd_amrres_set_uold(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_set_uold")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_set_uold")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1204,8 +1251,7 @@ int ramses_amd_amrres_set_uold(const ramses_amd_hydro_params *p, int ngrid, cons
 }
 
 int ramses_amd_amrres_upload_fine(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, int interpol_var) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_upload_fine")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_upload_fine")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_upload_fine")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   if (interpol_var < 0 || interpol_var > 2) return failf(RAMSES_AMD_EINVAL, "interpol_var must be 0, 1 or 2");
   LvlArgs A;
@@ -1224,8 +1270,7 @@ int ramses_amd_amrres_upload_fine(const ramses_amd_hydro_params *p, int ngrid, c
 
 // out4 = {dt_loc (min with dt_in), mass_loc, sum(E*vol), eint_loc} over the leaf cells of the level
 int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dx, double dt_in, double *out4) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_courant")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_courant")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_courant")) return rc_;
   if (!p || !out4) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1251,8 +1296,7 @@ int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const
 // for refinement come back as a compact list -- cells[0..*ncells), capacity 8*ngrid -- and nothing else crosses PCIe
 int ramses_amd_amrres_hydro_flag(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double err_grad_d, double err_grad_p,
                                  double err_grad_u, double floor_d, double floor_p, double floor_u, int *cells, int *ncells) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_hydro_flag")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_hydro_flag")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_hydro_flag")) return rc_;
   if (!p || !cells || !ncells) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   *ncells = 0;
   LvlArgs A;
@@ -1286,11 +1330,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   amrlayout::LevelMap &L = R.map.lev[ilevel];
   hipStream_t s = nullptr;
   P.version = -1;
-  PlanArgs A;
-  A.son = R.son.as<int>(); A.nbor = R.nbor.as<int>(); A.father = R.father.as<int>(); A.iperm = R.map.iperm.as<int>();
-  A.stat = R.stat.as<unsigned char>(); A.octpos = R.octpos.as<int>(); A.ig = R.cur_ig; A.n = ngrid;
-  A.ncell = R.ncell; A.ncoarse = R.ncoarse; A.ngd = R.ngridmax;
-  A.dir = L.dir.as<int>(); A.tileid = L.tileid.as<int>(); A.base = L.base; A.no = L.no; A.ntx = L.ntx; A.nty = L.nty; A.ntz = L.ntz;
+  const PlanArgs A = plan_args(R, L, ngrid);
   HCHK(P.gfather.ensure(sizeof(int) * (size_t)L.cap), "hipMalloc");
   const int gcap = (int)std::min<long>(L.cap - L.n, (long)ngrid * 26);
   HCHK(P.gslot.ensure(sizeof(int) * (size_t)(gcap > 0 ? gcap : 1)), "hipMalloc"); HCHK(P.gcell.ensure(sizeof(int) * (size_t)(gcap > 0 ? gcap : 1)), "hipMalloc");
@@ -1333,10 +1373,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
     HCHK(k1.ensure(sizeof(unsigned long long) * (size_t)P.nevent), "hipMalloc"); HCHK(k2.ensure(sizeof(unsigned long long) * (size_t)P.nevent), "hipMalloc");
     HCHK(v2.ensure(sizeof(int) * (size_t)P.nevent), "hipMalloc");
     hipLaunchKernelGGL(plan_event_keys_kernel, dim3((P.nevent + 255) / 256), dim3(256), 0, s, A, P.events.as<int>() + 1, P.nevent, k1.as<unsigned long long>(), event_order());
-    size_t bytes = 0;
-    HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k1.as<unsigned long long>(), k2.as<unsigned long long>(), P.events.as<int>() + 1, v2.as<int>(), P.nevent, 0, 35, s), "sort");
-    HCHK(R.work.ensure(bytes), "hipMalloc");
-    HCHK(hipcub::DeviceRadixSort::SortPairs(R.work.p, bytes, k1.as<unsigned long long>(), k2.as<unsigned long long>(), P.events.as<int>() + 1, v2.as<int>(), P.nevent, 0, 35, s), "sort");
+    if (int rc = radix_sort(R.work, k1.as<unsigned long long>(), k2.as<unsigned long long>(), P.events.as<int>() + 1, v2.as<int>(), P.nevent, 35, s)) return rc;
     HCHK(hipMemcpyAsync(P.events.as<int>() + 1, v2.p, sizeof(int) * (size_t)P.nevent, hipMemcpyDeviceToDevice, s), "copy");
     HCHK(hipStreamSynchronize(s), "sync");
     HCHK(P.corr.ensure(sizeof(double) * 4 * (size_t)(R.nvar + 2) * (size_t)P.nevent), "hipMalloc flux records");
@@ -1353,10 +1390,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
     // appended them in whatever order its waves arrived)
     amrlayout::Buf &k2 = P.gfather, &v2 = P.flag;          // (both free from here on: the ghost table's job is done, the flags are on the host)
     HCHK(k2.ensure(sizeof(int) * (size_t)P.nghost), "hipMalloc"); HCHK(v2.ensure(sizeof(int) * (size_t)P.nghost), "hipMalloc");
-    size_t bytes = 0;
-    HCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, P.gslot.as<int>(), k2.as<int>(), P.gcell.as<int>(), v2.as<int>(), P.nghost, 0, 32, s), "sort");
-    HCHK(R.work.ensure(bytes), "hipMalloc");
-    HCHK(hipcub::DeviceRadixSort::SortPairs(R.work.p, bytes, P.gslot.as<int>(), k2.as<int>(), P.gcell.as<int>(), v2.as<int>(), P.nghost, 0, 32, s), "sort");
+    if (int rc = radix_sort(R.work, P.gslot.as<int>(), k2.as<int>(), P.gcell.as<int>(), v2.as<int>(), P.nghost, 32, s)) return rc;
     HCHK(hipMemcpyAsync(P.gslot.p, k2.p, sizeof(int) * (size_t)P.nghost, hipMemcpyDeviceToDevice, s), "copy");
     HCHK(hipMemcpyAsync(P.gcell.p, v2.p, sizeof(int) * (size_t)P.nghost, hipMemcpyDeviceToDevice, s), "copy");
     HCHK(hipStreamSynchronize(s), "sync");
@@ -1442,8 +1476,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   if (nw > 0) HCHK(hipMemcpy(P.work.p, order.data(), sizeof(int) * 4 * (size_t)nw, hipMemcpyHostToDevice), "H2D work list");
   P.nwork = nw;
   P.rows = rows;
-  P.ngrid = ngrid; P.ig_first = ngrid > 0 ? h_igrid[0] : 0; P.ig_last = ngrid > 0 ? h_igrid[ngrid - 1] : 0;
-  for (int k = 0; k < 10; k++) P.ig_sample[k] = h_igrid[(long)k * (ngrid - 1) / 9];
+  P.list = ListPrint::of(h_igrid, ngrid);
   P.version = L.version;
   return 0;
 }
@@ -1498,8 +1531,7 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   // (the plan of a level that kept its layout survives a regrid of the finer levels: its octs, ghosts and work items are the same.
   //  The list of a level must not change between two regrids without its first or last entry or its length changing: it is
   //  active(ilevel)%igrid, which only build_comm / refine_fine / load_balance rewrite.)
-  bool same_list = P.version == L.version && P.rows == rows && P.ngrid == ngrid && P.ig_first == h_igrid[0] && P.ig_last == h_igrid[ngrid - 1];
-  for (int k = 0; same_list && k < 10; k++) same_list = P.ig_sample[k] == h_igrid[(long)k * (ngrid - 1) / 9];
+  const bool same_list = P.version == L.version && P.rows == rows && P.list == ListPrint::of(h_igrid, ngrid);
   if (!same_list)
     if (int rc = build_plan(R, ilevel, ngrid, h_igrid, rows, P)) return rc;
   if (P.nwork == 0) { done = true; return 0; }
@@ -1561,11 +1593,7 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   HCHK(e, "dense sweep of a level in tiles");
   // what the level owes to the leaf cells of the coarser one, replayed in the reference's order
   {
-    PlanArgs Q;
-    Q.son = R.son.as<int>(); Q.nbor = R.nbor.as<int>(); Q.father = R.father.as<int>(); Q.iperm = R.map.iperm.as<int>();
-    Q.stat = R.stat.as<unsigned char>(); Q.octpos = R.octpos.as<int>(); Q.ig = R.cur_ig; Q.n = ngrid;
-    Q.ncell = R.ncell; Q.ncoarse = R.ncoarse; Q.ngd = R.ngridmax;
-    Q.dir = L.dir.as<int>(); Q.tileid = L.tileid.as<int>(); Q.base = L.base; Q.no = L.no; Q.ntx = L.ntx; Q.nty = L.nty; Q.ntz = L.ntz;
+    const PlanArgs Q = plan_args(R, L, ngrid);
     if (P.nevent > 0) {
       hipLaunchKernelGGL(tile_coarse_update_kernel, dim3((P.nevent + 255) / 256), dim3(256), 0, s, Q, R.unew.as<double>(), P.corr.as<double>(), P.corr_tgt.as<int>(),
                          P.evt_of.as<int>(), P.events.as<int>() + 1, P.nevent, nvector, nvar, pfix ? R.divu.as<double>() : nullptr, pfix ? R.enew.as<double>() : nullptr);
@@ -1595,8 +1623,7 @@ extern "C" int ramses_amd_amrres_tiled_levels(void) { return g_ar.valid && g_ar.
 // godunov_fine(ilevel) on the resident arrays
 int ramses_amd_amrres_godunov(const ramses_amd_hydro_params *p, int ilevel, int ngrid, const int *igrid, double dx, double dt,
                               int nvector, int interpol_var, int interpol_type) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_godunov")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_godunov")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_godunov")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -1631,27 +1658,10 @@ int ramses_amd_amrres_load_f(int ngrid, const int *igrid, const double *f) {
   LvlArgs A;
   if (!f) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
-  if (!R.grav) {
-    HCHK(R.f.ensure(sizeof(double) * 3 * (size_t)R.ncell), "hipMalloc f");
-    HCHK(hipMemsetAsync(R.f.p, 0, sizeof(double) * 3 * (size_t)R.ncell, nullptr), "memset f");
-    R.grav = true;
-  }
+  if (int rc = ensure_f(R)) return rc;
   if (ngrid == 0) return 0;
-  const long tot = (long)ngrid * 8;
-  R.hpack.resize((size_t)tot * 3);
-  for (int k = 0; k < 3; k++)
-    for (int ind = 0; ind < 8; ind++) {
-      const double *src = f + (size_t)k * R.ncell_h + R.ncoarse + (size_t)ind * R.ngh - 1;
-      double *dst = R.hpack.data() + (size_t)k * tot + (size_t)ind * ngrid;
-      for (int i = 0; i < ngrid; i++) dst[i] = src[igrid[i]];
-    }
-  HCHK(R.pack.ensure(sizeof(double) * (size_t)tot * 3), "hipMalloc");
-  HCHK(hipMemcpy(R.pack.p, R.hpack.data(), sizeof(double) * (size_t)tot * 3, hipMemcpyHostToDevice), "H2D f");
-  R.f_up_bytes += (int64_t)sizeof(double) * tot * 3;
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for(tot)), dim3(256), 0, nullptr, R.f.as<double>(), R.pack.as<double>(), R.cur_ig, ngrid, 3,
-                     R.ncell, R.ncoarse, R.ngridmax);
-  HCHK(hipGetLastError(), "f unpack launch");
-  HCHK(hipStreamSynchronize(nullptr), "sync");
+  if (int rc = level_from_host(R, R.f.as<double>(), 3, R.cur_ig, ngrid, igrid, f, "f")) return rc;
+  R.f_up_bytes += (int64_t)sizeof(double) * 3 * 8 * ngrid;
   return 0;
 }
 int ramses_amd_amrres_has_gravity(void) { return g_ar.valid && g_ar.grav ? 1 : 0; }
@@ -1664,11 +1674,7 @@ int ramses_amd_amrres_take_f_device(int ngrid, const int *igrid, const double *d
   LvlArgs A;
   if (!d_fpack) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
-  if (!R.grav) {
-    HCHK(R.f.ensure(sizeof(double) * 3 * (size_t)R.ncell), "hipMalloc f");
-    HCHK(hipMemsetAsync(R.f.p, 0, sizeof(double) * 3 * (size_t)R.ncell, nullptr), "memset f");
-    R.grav = true;
-  }
+  if (int rc = ensure_f(R)) return rc;
   if (ngrid == 0) return 0;
   hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, R.f.as<double>(), const_cast<double *>(d_fpack), R.cur_ig,
                      ngrid, 3, R.ncell, R.ncoarse, R.ngridmax);
@@ -1683,20 +1689,8 @@ int ramses_amd_amrres_sync_f(int ngrid, const int *igrid, double *f) {
   if (!R.grav) return failf(RAMSES_AMD_EINVAL, "sync_f: no acceleration on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
-  const long tot = (long)ngrid * 8;
-  HCHK(R.pack.ensure(sizeof(double) * (size_t)tot * 3), "hipMalloc");
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for(tot)), dim3(256), 0, nullptr, R.f.as<double>(), R.pack.as<double>(), R.cur_ig, ngrid, 3,
-                     R.ncell, R.ncoarse, R.ngridmax);
-  HCHK(hipGetLastError(), "f pack launch");
-  R.hpack.resize((size_t)tot * 3);
-  HCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * (size_t)tot * 3, hipMemcpyDeviceToHost), "D2H f");
-  R.f_down_bytes += (int64_t)sizeof(double) * tot * 3;
-  for (int k = 0; k < 3; k++)
-    for (int ind = 0; ind < 8; ind++) {
-      double *dst = f + (size_t)k * R.ncell_h + R.ncoarse + (size_t)ind * R.ngh - 1;
-      const double *src = R.hpack.data() + (size_t)k * tot + (size_t)ind * ngrid;
-      for (int i = 0; i < ngrid; i++) dst[igrid[i]] = src[i];
-    }
+  if (int rc = level_to_host(R, R.f.as<double>(), 3, R.cur_ig, ngrid, igrid, f, nullptr, "f")) return rc;
+  R.f_down_bytes += (int64_t)sizeof(double) * 3 * 8 * ngrid;
   return 0;
 }
 // RAMSES_AMD_F_CHECK=1 (patch/force_fine.f90): the largest |device f - host f| over the listed octs, and how many cells differ
@@ -1708,17 +1702,11 @@ int ramses_amd_amrres_compare_f(int ngrid, const int *igrid, const double *f, do
   if (!R.grav) return failf(RAMSES_AMD_EINVAL, "compare_f: no acceleration on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
-  const long tot = (long)ngrid * 8;
-  HCHK(R.pack.ensure(sizeof(double) * (size_t)tot * 3), "hipMalloc");
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for(tot)), dim3(256), 0, nullptr, R.f.as<double>(), R.pack.as<double>(), R.cur_ig, ngrid, 3,
-                     R.ncell, R.ncoarse, R.ngridmax);
-  HCHK(hipGetLastError(), "f pack launch");
-  std::vector<double> h((size_t)tot * 3);
-  HCHK(hipMemcpy(h.data(), R.pack.p, sizeof(double) * (size_t)tot * 3, hipMemcpyDeviceToHost), "D2H f");
+  if (int rc = level_fetch(R, R.f.as<double>(), 3, R.cur_ig, ngrid, nullptr, "f")) return rc;
   for (int k = 0; k < 3; k++)
     for (int ind = 0; ind < 8; ind++) {
       const double *ref = f + (size_t)k * R.ncell_h + R.ncoarse + (size_t)ind * R.ngh - 1;
-      const double *dev = h.data() + (size_t)k * tot + (size_t)ind * ngrid;
+      const double *dev = R.hpack.data() + ((size_t)k * 8 + ind) * ngrid;
       for (int i = 0; i < ngrid; i++) {
         const double d = std::fabs(dev[i] - ref[igrid[i]]);
         if (d > 0.0 || dev[i] != ref[igrid[i]]) { (*ndiff)++; if (d > *maxdiff) *maxdiff = d; }
@@ -1763,8 +1751,7 @@ int ramses_amd_amrres_xg(const double *xg) {
 //   levelmin (written when ilevel == levelmin, where the reference has just reset them; untouched otherwise)
 int ramses_amd_amrres_rho_fine(const ramses_amd_hydro_params *p, int ilevel, int nlevelmax, int levelmin, int nvector,
                                const int *first, const int *igrid_all, double boxlen_over_nx, double *rho, double *multipole4) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_rho_fine")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_rho_fine")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_rho_fine")) return rc_;
   AmrRes &R = g_ar;
   if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
   if (!p || !first || !igrid_all || !rho || !multipole4) return failf(RAMSES_AMD_EINVAL, "NULL argument");
@@ -1797,19 +1784,7 @@ int ramses_amd_amrres_rho_fine(const ramses_amd_hydro_params *p, int ilevel, int
       HCHK(hipMemcpyAsync(multipole4, R.red.p, sizeof(double) * 4, hipMemcpyDeviceToHost, s), "D2H multipole");
     }
     // the deposit of the level back into the host vector (multigrid_fine / phi_fine_cg / force_fine's diagnostics read it there)
-    const long tot = (long)n * 8;
-    HCHK(R.pack.ensure(sizeof(double) * (size_t)tot), "hipMalloc");
-    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for(tot)), dim3(256), 0, s, R.rho.as<double>(), R.pack.as<double>(), d_ig, n, 1,
-                       R.ncell, R.ncoarse, R.ngridmax);
-    HCHK(hipGetLastError(), "rho pack launch");
-    R.hpack.resize((size_t)tot);
-    HCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost), "D2H rho");
-    const int *ig = igrid_all + lo;
-    for (int ind = 0; ind < 8; ind++) {
-      double *dst = rho + R.ncoarse + (size_t)ind * R.ngh - 1;
-      const double *src = R.hpack.data() + (size_t)ind * n;
-      for (int i = 0; i < n; i++) dst[ig[i]] = src[i];
-    }
+    if (int rc = level_to_host(R, R.rho.as<double>(), 1, d_ig, n, igrid_all + lo, rho, s, "rho")) return rc;
   }
   HCHK(hipStreamSynchronize(s), "sync");
   return 0;
@@ -1825,8 +1800,7 @@ int ramses_amd_amrres_rho_fine(const ramses_amd_hydro_params *p, int ilevel, int
 //                   multipole sums (the caller's MPI_ALLREDUCE follows, :176-183)
 int ramses_amd_amrres_rho_mpi_multipole(const ramses_amd_hydro_params *p, int ilevel, int n_own, int n_all, const int *igrid_all,
                                         double boxlen_over_nx) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_rho_mpi_multipole")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_rho_mpi_multipole")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_rho_mpi_multipole")) return rc_;
   AmrRes &R = g_ar;
   if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
   if (!p || (n_all > 0 && !igrid_all)) return failf(RAMSES_AMD_EINVAL, "NULL argument");
@@ -1873,19 +1847,8 @@ int ramses_amd_amrres_rho_mpi_finish(int ilevel, int levelmin, int nvector, cons
   // (ramses_amd_amrres_rho_keep(1): the solver and force_fine of this level read the deposit on the device -- the distributed
   //  dense multigrid of a uniform run, round 6 -- and the host vector is fetched by ramses_amd_amrres_sync_rho when somebody asks)
   if (n > 0 && !R.rho_keep) {
-    const long tot = (long)n * 8;
-    HCHK(R.pack.ensure(sizeof(double) * (size_t)tot), "hipMalloc");
-    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for(tot)), dim3(256), 0, s, R.rho.as<double>(), R.pack.as<double>(), R.lists.as<int>(), n, 1,
-                       R.ncell, R.ncoarse, R.ngridmax);
-    HCHK(hipGetLastError(), "rho pack launch");
-    R.hpack.resize((size_t)tot);
-    HCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost), "D2H rho");
-    R.rho_down_bytes += (int64_t)sizeof(double) * tot;
-    for (int ind = 0; ind < 8; ind++) {
-      double *dst = rho + R.ncoarse + (size_t)ind * R.ngh - 1;
-      const double *src = R.hpack.data() + (size_t)ind * n;
-      for (int i = 0; i < n; i++) dst[igrid_all[i]] = src[i];
-    }
+    if (int rc = level_to_host(R, R.rho.as<double>(), 1, R.lists.as<int>(), n, igrid_all, rho, s, "rho")) return rc;
+    R.rho_down_bytes += (int64_t)sizeof(double) * 8 * n;
   }
   HCHK(hipStreamSynchronize(s), "sync");
   return 0;
@@ -1899,19 +1862,8 @@ int ramses_amd_amrres_sync_rho(int ngrid, const int *igrid, double *rho) {
   if (!R.rho.p) return failf(RAMSES_AMD_EINVAL, "sync_rho: rho_fine has not run on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
-  const long tot = (long)ngrid * 8;
-  HCHK(R.pack.ensure(sizeof(double) * (size_t)tot), "hipMalloc");
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for(tot)), dim3(256), 0, nullptr, R.rho.as<double>(), R.pack.as<double>(), R.cur_ig, ngrid, 1,
-                     R.ncell, R.ncoarse, R.ngridmax);
-  HCHK(hipGetLastError(), "rho pack launch");
-  R.hpack.resize((size_t)tot);
-  HCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost), "D2H rho");
-  R.rho_down_bytes += (int64_t)sizeof(double) * tot;
-  for (int ind = 0; ind < 8; ind++) {
-    double *dst = rho + R.ncoarse + (size_t)ind * R.ngh - 1;
-    const double *src = R.hpack.data() + (size_t)ind * ngrid;
-    for (int i = 0; i < ngrid; i++) dst[igrid[i]] = src[i];
-  }
+  if (int rc = level_to_host(R, R.rho.as<double>(), 1, R.cur_ig, ngrid, igrid, rho, nullptr, "rho")) return rc;
+  R.rho_down_bytes += (int64_t)sizeof(double) * 8 * ngrid;
   return 0;
 }
 // the deposit of the rank's own octs into a dense brick on the device: brick[order[ind * ngrid + g]] = rho(cell ind of oct igrid[g])
@@ -1971,24 +1923,11 @@ int ramses_amd_amrres_sync_density(int ngrid, const int *igrid, double *uold) {
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (uold != R.h_uold) return failf(RAMSES_AMD_EINVAL, "sync_density: not the array the state was loaded from");
   if (ngrid == 0) return 0;
-  const long tot = (long)ngrid * 8;
-  HCHK(R.pack.ensure(sizeof(double) * (size_t)tot), "hipMalloc");
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for(tot)), dim3(256), 0, nullptr, R.uold.as<double>(), R.pack.as<double>(), R.cur_ig, ngrid, 1,
-                     R.ncell, R.ncoarse, R.ngridmax);
-  HCHK(hipGetLastError(), "density pack launch");
-  R.hpack.resize((size_t)tot);
-  HCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost), "D2H density");
-  for (int ind = 0; ind < 8; ind++) {
-    double *dst = uold + R.ncoarse + (size_t)ind * R.ngh - 1;
-    const double *src = R.hpack.data() + (size_t)ind * ngrid;
-    for (int i = 0; i < ngrid; i++) dst[igrid[i]] = src[i];
-  }
-  return 0;
+  return level_to_host(R, R.uold.as<double>(), 1, R.cur_ig, ngrid, igrid, uold, nullptr, "density");
 }
 
 int ramses_amd_amrres_synchro(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dteff) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_synchro")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_synchro")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_synchro")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -2002,8 +1941,7 @@ int ramses_amd_amrres_synchro(const ramses_amd_hydro_params *p, int ngrid, const
 
 // set_uold with poisson: add_gravity_source_terms on unew, then the scalar fix and uold = unew
 int ramses_amd_amrres_set_uold_grav(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_set_uold_grav")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_set_uold_grav")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold_grav")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -2029,8 +1967,7 @@ int ramses_amd_amrres_enable_pfix(void) {
 }
 // set_unew with pressure_fix: unew = uold, divu = 0, enew = internal energy
 int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_set_unew_pfix")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_set_unew_pfix")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_unew_pfix")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -2046,8 +1983,7 @@ int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid,
 // set_uold with pressure_fix: (add_gravity_source_terms,) add_pdv_source_terms, the scalar fix and uold = unew, the energy switch
 int ramses_amd_amrres_set_uold_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt, double dx_loc, double beta_fix,
                                     double hexp) {
-  if (int rc_ = refuse_nener(p, "ramses_amd_amrres_set_uold_pfix")) return rc_;
-  if (int rc_ = refuse_scalars(p, "ramses_amd_amrres_set_uold_pfix")) return rc_;
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold_pfix")) return rc_;
   if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
@@ -2072,22 +2008,8 @@ int ramses_amd_amrres_sync_pfix(int ngrid, const int *igrid, double *divu, doubl
   LvlArgs A;
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
-  const long tot = (long)ngrid * 8;
-  HCHK(R.pack.ensure(sizeof(double) * (size_t)tot), "hipMalloc");
-  R.hpack.resize((size_t)tot);
-  for (int v = 0; v < 2; v++) {
-    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for(tot)), dim3(256), 0, nullptr, v == 0 ? R.divu.as<double>() : R.enew.as<double>(), R.pack.as<double>(),
-                       R.cur_ig, ngrid, 1, R.ncell, R.ncoarse, R.ngridmax);
-    HCHK(hipGetLastError(), "divu / enew pack launch");
-    HCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * (size_t)tot, hipMemcpyDeviceToHost), "D2H divu / enew");
-    double *host = v == 0 ? divu : enew;
-    for (int ind = 0; ind < 8; ind++) {
-      double *dst = host + R.ncoarse + (size_t)ind * R.ngh - 1;
-      const double *src = R.hpack.data() + (size_t)ind * ngrid;
-      for (int i = 0; i < ngrid; i++) dst[igrid[i]] = src[i];
-    }
-  }
-  return 0;
+  if (int rc = level_to_host(R, R.divu.as<double>(), 1, R.cur_ig, ngrid, igrid, divu, nullptr, "divu")) return rc;
+  return level_to_host(R, R.enew.as<double>(), 1, R.cur_ig, ngrid, igrid, enew, nullptr, "enew");
 }
 
 

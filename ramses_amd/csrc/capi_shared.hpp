@@ -106,6 +106,11 @@ static inline int refuse_scalars(const ramses_amd_hydro_params *p, const char *w
                 "resident and MPI-resident bricks), not on AMR levels, tiles or the tree walker", who, p->nvar);
   return 0;
 }
+// both, in this order: how every entry point of the AMR levels opens
+static inline int refuse_amr(const ramses_amd_hydro_params *p, const char *who) {
+  if (int rc = refuse_nener(p, who)) return rc;
+  return refuse_scalars(p, who);
+}
 
 // capi_host.hip: the staged entry points reuse the staging buffers of the resident level; refuses while that level holds
 // the only current copy of the hydro state
