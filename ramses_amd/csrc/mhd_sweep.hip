@@ -570,8 +570,9 @@ int MHD_BRICK_FN(const ramses_amd_mhd_params *p, int nx, int ny, int nz, const d
   A.nx = nx; A.ny = ny; A.nz = nz; A.ncell = N; A.dt = dt; A.dx = dx;
   HCHK(hipMemsetAsync(A.bad, 0, sizeof(int), s), "memset");
   // ctoprim, the edge fields and the trace: one launch over tiles of 32 x 4 x 4 cells (RAMSES_AMD_MHD_FUSED=0: the three kernels)
-  static int fused = -1;
-  if (fused < 0) { const char *e = getenv("RAMSES_AMD_MHD_FUSED"); fused = (e && e[0] == '0') ? 0 : 1; }
+  // (read on every call, like RAMSES_AMD_MHD_FAST: the tests run both paths inside one process)
+  const char *ef = getenv("RAMSES_AMD_MHD_FUSED");
+  const bool fused = !(ef && ef[0] == '0');
   if (!fused) {
     hipLaunchKernelGGL(mhd_prim_kernel, dim3(grid_for(N, 256)), dim3(256), 0, s, A);
     hipLaunchKernelGGL(mhd_efield_kernel, dim3(grid_for(N, 256)), dim3(256), 0, s, A);

@@ -139,4 +139,96 @@ def tree_state_shares(T, L, u, smallr=0.6, gamma=1.4):
     return float((v2 > c2).mean()), float((rho < smallr).mean())
 
 
+def harsh_mhd_brick(nx, ny, nz, seed, gamma=5.0 / 3.0):
+    """A super-fast, floored, partly unmagnetised state of the eleven MHD fields on a periodic nx x ny x nz brick (even extents
+    >= 4): u[11, nz, ny, nx] = rho, rho u, rho v, rho w, E, the field on the left faces, the field on the right faces.
+
+    rho, velocity and pressure are those of random_brick (blocky pressure jumps over five decades, velocities of sigma 0.7, half
+    of the densities below 0.6).  The face fields are the discrete curl of an edge potential (already divided by dx) of N(0, 1)
+    times 0.15 where i < nx/2 and 0.8 elsewhere -- plasma beta on either side of 1 -- set to zero in the corner
+    [: nz/2 + 1, : ny/2 + 1, : nx/3 + 1], so that the cells [: nz/2, : ny/2, : nx/3] carry B == 0 exactly; div B = 0 to rounding
+    and the right faces are the neighbours' left faces bit for bit.  Two features are laid over that:
+
+      * a weak-field block (nz/2 <= k < nz/2 + 2, i < min(4, nx/2), every j) of cold gas above the floor (rho >= 1, p = 0.05 rho)
+        moving diagonally at +-4 per component, the signs changing every two cells: several fast speeds in every direction, all
+        four sign pairs around the edges (the doubly super-fast corners of the 2-D HLLD solver);
+      * where the unmagnetised corner has room for it (nx/3 >= 4, ny/2 >= 3, nz/2 >= 3): a thin flux tube Bx = 1 along the whole
+        line j = k = 1, threading a patch [0:3, 0:3, 0:4] of nearly uniform gas (rho = 1, p = 0.1, u = 0.3 to 1e-6, v = w = 0.3)
+        whose Alfven speed exceeds its sound speed.  The tube's own cells have v = w = 0, so its field stays purely normal: c_fast
+        = c_Alfven there, the degenerate star states of HLLD and Roe's slow = sound speed."""
+    assert min(nx, ny, nz) >= 4 and nx % 2 == 0 and ny % 2 == 0 and nz % 2 == 0, "even extents >= 4 (the reference works oct by oct)"
+    u5 = random_brick(nx, ny, nz, seed, gamma=gamma)
+    rho = u5[0].copy()
+    vel = u5[1:4] / rho
+    p = (gamma - 1.0) * (u5[4] - 0.5 * rho * (vel ** 2).sum(0))
+    rng = np.random.default_rng(seed + 1000)
+    shp = (nz, ny, nx)
+    amp = np.where(np.arange(nx) < nx // 2, 0.15, 0.8)[None, None, :]
+    A = [rng.standard_normal(shp) * amp for _ in range(3)]          # Ax, Ay, Az on the low x-, y-, z-edges of each cell
+    for a in A:
+        a[: nz // 2 + 1, : ny // 2 + 1, : nx // 3 + 1] = 0.0
+    # the cold diagonal block
+    k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    blk = (k >= nz // 2) & (k < nz // 2 + 2) & (i < min(4, nx // 2))
+    rho = np.where(blk, np.maximum(rho, 1.0), rho)
+    p = np.where(blk, 0.05 * rho, p)
+    for d, idx in enumerate((i, j, k)):
+        vel[d] = np.where(blk, 4.0 * np.where((idx // 2) % 2 == 0, 1.0, -1.0), vel[d])
+    rollp = lambda a, ax: np.roll(a, -1, axis=ax)      # noqa: E731  value at +1 along ax (axes: 0 z, 1 y, 2 x)
+    bx = (rollp(A[2], 1) - A[2]) - (rollp(A[1], 0) - A[1])          # on low x faces
+    by = (rollp(A[0], 0) - A[0]) - (rollp(A[2], 2) - A[2])          # on low y faces
+    bz = (rollp(A[1], 2) - A[1]) - (rollp(A[0], 1) - A[0])          # on low z faces
+    if nx // 3 >= 4 and ny // 2 >= 3 and nz // 2 >= 3:
+        bx[1, 1, :] += 1.0
+        patch = (slice(0, 3), slice(0, 3), slice(0, 4))
+        rho[patch] = 1.0 + 1e-6 * rng.uniform(-1, 1, (3, 3, 4))
+        p[patch] = 0.1 * (1.0 + 1e-6 * rng.uniform(-1, 1, (3, 3, 4)))
+        vel[0][patch] = 0.3 * (1.0 + 1e-6 * rng.uniform(-1, 1, (3, 3, 4)))
+        vel[1][patch] = 0.3                            # (gas at rest across an unmagnetised edge is 0 / 0 in the HLLA solver)
+        vel[2][patch] = 0.3
+        vel[1][1, 1, :] = 0.0
+        vel[2][1, 1, :] = 0.0
+    u = np.zeros((11,) + shp)
+    u[5], u[6], u[7] = bx, by, bz
+    u[8], u[9], u[10] = rollp(bx, 2), rollp(by, 1), rollp(bz, 0)
+    bc = [0.5 * (u[5 + c] + u[8 + c]) for c in range(3)]
+    u[0] = rho
+    for c in range(3):
+        u[1 + c] = rho * vel[c]
+    u[4] = p / (gamma - 1.0) + 0.5 * rho * (vel ** 2).sum(0) + 0.5 * sum(b * b for b in bc)
+    return u
+
+
+def oct_stencils(u):
+    """the 6^3 stencils godfine1 gathers around the octs of a periodic brick u[nvar, nz, ny, nx] (even extents), octs in z, y, x
+    order: [nvar, 6, 6, 6, nocts] in C order, which is the reference's uin(1:nocts, -1:4, -1:4, -1:4, 1:nvar)"""
+    nz, ny, nx = u.shape[1:]
+    off = np.arange(-2, 4)
+    kk = (2 * np.arange(nz // 2)[:, None] + off) % nz            # [oct][6]
+    jj = (2 * np.arange(ny // 2)[:, None] + off) % ny
+    ii = (2 * np.arange(nx // 2)[:, None] + off) % nx
+    s = u[:, kk[:, None, None, :, None, None], jj[None, :, None, None, :, None], ii[None, None, :, None, None, :]]   # [v][ok][oj][oi][6][6][6]
+    s = s.reshape(u.shape[0], -1, 6, 6, 6)
+    return np.ascontiguousarray(np.moveaxis(s, 1, -1))
+
+
+def mhd_brick_shares(u, gamma=5.0 / 3.0, smallr=0.6):
+    """what harsh_mhd_brick promises, from the state alone: dict of min p, the shares of cells above the fast speed, above the
+    sound speed, with rho < smallr, with plasma beta < 1 and with B == 0 exactly, max |div B| (field units: dx = 1) and whether
+    the right faces are the neighbours' left faces bit for bit"""
+    rho = u[0]
+    v2 = (u[1:4] ** 2).sum(0) / rho ** 2
+    bc = 0.5 * (u[5:8] + u[8:11])
+    b2 = (bc ** 2).sum(0)
+    p = (gamma - 1.0) * (u[4] - 0.5 * rho * v2 - 0.5 * b2)
+    c2 = gamma * p / rho
+    fast2 = c2 + b2 / rho                      # the largest fast speed over directions (field across the direction)
+    with np.errstate(divide="ignore"):
+        beta = np.where(b2 > 0, p / np.where(b2 > 0, 0.5 * b2, 1.0), np.inf)
+    div = (u[8] - u[5]) + (u[9] - u[6]) + (u[10] - u[7])
+    faces = all(np.array_equal(u[8 + c], np.roll(u[5 + c], -1, axis=ax)) for c, ax in ((0, 2), (1, 1), (2, 0)))
+    return dict(pmin=float(p.min()), fast=float((v2 > fast2).mean()), sonic=float((v2 > c2).mean()), low=float((rho < smallr).mean()),
+                beta=float((beta < 1).mean()), b0=float(((np.abs(u[5:11]) == 0).all(0)).mean()), divb=float(np.abs(div).max()), faces=faces)
+
+
 from ramses_amd.ic import _morton_rank, uniform_tree  # noqa: E402,F401  (synthetic trees live with the other synthetic inputs)

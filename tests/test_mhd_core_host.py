@@ -4,6 +4,9 @@ mhd_host_check.cpp) and driven over batches of the reference's own 6^3 stencils;
 reference (mhd/umuscl.f90:31-238 behind oracle/ref_shim_mhd.f90, oracle/_ref/libref_kernels3d_mhd.so) sees the same
 stencils.  Fluxes of the five Euler variables and the three edge EMFs must be equal bit for bit, for every supported
 combination of 1-D solver (llf, roe, hll, hlld, upwind, hydro), 2-D solver (llf, roe, upwind, hll, hlla, hlld) and slope type (0, 1, 2, 7, 8, and 3 with slope_mag_type 1 / 8).
+A third kind of input, "harsh", are the 6^3 stencils around the octs of tests/helpers.py harsh_mhd_brick(12, 18, 10): super-fast,
+floored (smallr 1e-10 and 0.6), partly unmagnetised -- the input that reaches the branches the smooth and jump stencils leave
+untaken (tests/test_mhd_harsh_state_branches.py, profiles/mhd_harsh_state_branches.txt).
 SURVEY.md 8 row f4; the GPU leg is tests/test_mhd_gpu.py."""
 import ctypes as C
 import os
@@ -11,6 +14,8 @@ import subprocess
 
 import numpy as np
 import pytest
+
+from helpers import harsh_mhd_brick, oct_stencils
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "libref_kernels3d_mhd.so")
@@ -32,7 +37,10 @@ def libs(tmp_path_factory):
 
 def stencils(nvec, seed, kind):
     """uin(nvector,-1:4,-1:4,-1:4,11) in Fortran order: a smooth magnetised flow with a jump across a tilted plane; the
-    face fields are consistent (the right face of a cell is the left face of its neighbour), as on a real level"""
+    face fields are consistent (the right face of a cell is the left face of its neighbour), as on a real level.
+    kind "harsh": all the oct stencils of harsh_mhd_brick(12, 18, 10, seed) instead (270 of them, whatever nvec)"""
+    if kind == "harsh":
+        return oct_stencils(harsh_mhd_brick(*HARSH_SHAPE, seed=seed))
     rng = np.random.default_rng(seed)
     u = np.zeros((11, 6, 6, 6, nvec))           # C order [var][k][j][i][l]  == Fortran (l,i,j,k,var)
     k, j, i = np.meshgrid(np.arange(6), np.arange(6), np.arange(6), indexing="ij")
@@ -61,42 +69,85 @@ def stencils(nvec, seed, kind):
     return np.ascontiguousarray(u)
 
 
-@pytest.mark.parametrize("slope_type", [1, 2, 0, 7, 8, (3, 1), (3, 8)])
-@pytest.mark.parametrize("riemann,riemann2d", [(0, 0), (3, 5), (2, 3), (3, 0), (0, 5), (4, 0), (3, 4), (0, 2), (2, 2), (4, 4), (5, 0), (5, 5), (1, 0), (1, 1), (3, 1), (1, 5)])
-@pytest.mark.parametrize("kind", ["smooth", "jump"])
-def test_headers_equal_the_compiled_reference(libs, slope_type, riemann, riemann2d, kind):
+SLOPES = [1, 2, 0, 7, 8, (3, 1), (3, 8)]
+PAIRS = [(0, 0), (3, 5), (2, 3), (3, 0), (0, 5), (4, 0), (3, 4), (0, 2), (2, 2), (4, 4), (5, 0), (5, 5), (1, 0), (1, 1), (3, 1), (1, 5)]
+GRAVITY = [(3, 5, 2), (0, 0, 1), (1, 1, 8)]                 # (riemann, riemann2d, slope_type) of the gravity case
+TESTS_DX, TESTS_DT = 1.0 / 64, 0.2 / 64                     # the smooth and jump stencils
+HARSH_SEED, HARSH_SHAPE = 12, (12, 18, 10)                  # (nx, ny, nz) of the harsh brick: 270 octs
+HARSH_DX, HARSH_DT = 1.0 / 32, 0.02 / 32
+# (scripts/mhd_branch_coverage.py imports all of these: the record of the branches taken is of these very cases)
+
+
+def slope_pair(slope_type):
+    """(slope_type, slope_mag_type): uslope has no branch 3 for the face fields, slope_type = 3 goes with an explicit slope_mag_type"""
+    return slope_type if isinstance(slope_type, tuple) else (slope_type, slope_type)
+
+
+def case_seed(slope_type, riemann, riemann2d):
+    return 100 * slope_pair(slope_type)[0] + 10 * riemann + riemann2d
+
+
+def gravity_case(nvec, riemann):
+    """the stencils and the gravity field of the gravity case"""
+    return stencils(nvec, 4242 + riemann, "jump"), np.ascontiguousarray(np.random.default_rng(7).normal(0.0, 2.0, (3, 6, 6, 6, nvec)))
+
+
+def _compare(libs, uin, dx, dt, smallr, slope_type, riemann, riemann2d):
+    """fluxes and EMFs of the headers against the compiled reference on the stencils uin[11, 6, 6, 6, n], nvec at a time"""
     host, ref, nvec = libs
-    # (slope_type, slope_mag_type): uslope has no branch 3 for the face fields, slope_type = 3 goes with an explicit slope_mag_type
-    slope_type, slope_mag_type = slope_type if isinstance(slope_type, tuple) else (slope_type, slope_type)
-    gamma, smallr, smallc, theta = 5.0 / 3.0, 1e-10, 1e-10, 1.5
-    uin = stencils(nvec, 100 * slope_type + 10 * riemann + riemann2d, kind)
-    dx, dt = 1.0 / 64, 0.2 / 64
-    grav = np.zeros((3, 6, 6, 6, nvec))
+    slope_type, slope_mag_type = slope_pair(slope_type)
+    gamma, smallc, theta = 5.0 / 3.0, 1e-10, 1.5
     vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     dbl = C.c_double
-    # the reference
-    flux_r = np.full((3, 8, 3, 3, 3, nvec), np.nan)
-    tmp_r = np.full((3, 2, 3, 3, 3, nvec), np.nan)
-    emf_r = [np.full((3, 3, 3, nvec), np.nan) for _ in range(3)]
     ref.ref_mhd_set_params(dbl(gamma), dbl(smallr), dbl(smallc), slope_type, slope_mag_type, dbl(theta), riemann, riemann2d)
-    ref.ref_mag_unsplit(vp(uin), vp(grav), vp(flux_r), vp(emf_r[0]), vp(emf_r[1]), vp(emf_r[2]), vp(tmp_r), dbl(dx), dbl(dx), dbl(dx), dbl(dt), nvec)
-    # the product's headers on the host
-    flux_h = np.full_like(flux_r, np.nan)
-    emf_h = [np.full_like(e, np.nan) for e in emf_r]
-    rc = host.mhd_host_unsplit(vp(uin), nvec, nvec, dbl(dx), dbl(dt), dbl(gamma), dbl(smallr), dbl(smallc), slope_type, slope_mag_type, dbl(theta),
-                               riemann, riemann2d, vp(flux_h), vp(emf_h[0]), vp(emf_h[1]), vp(emf_h[2]))
-    assert rc == 0
-    # where mag_unsplit defines its outputs (:100-236): fluxes through the faces of the central 2^3 cells, EMFs on their edges
-    for d in range(3):
-        sl = [slice(0, 3 if d == 2 else 2), slice(0, 3 if d == 1 else 2), slice(0, 3 if d == 0 else 2)]      # [k][j][i]
-        a, b = flux_h[d][:5][:, sl[0], sl[1], sl[2]], flux_r[d][:5][:, sl[0], sl[1], sl[2]]
-        assert np.isfinite(b).all()
-        assert np.array_equal(a, b), (d, np.abs(a - b).max())
-    for e in range(3):
-        sl = [slice(0, 2 if e == 2 else 3), slice(0, 2 if e == 1 else 3), slice(0, 2 if e == 0 else 3)]
-        a, b = emf_h[e][sl[0], sl[1], sl[2]], emf_r[e][sl[0], sl[1], sl[2]]
-        assert np.isfinite(b).all()
-        assert np.array_equal(a, b), (e, np.abs(a - b).max())
+    for b0 in range(0, uin.shape[-1], nvec):
+        ng = min(nvec, uin.shape[-1] - b0)
+        batch = np.zeros(uin.shape[:-1] + (nvec,))
+        batch[..., :ng] = uin[..., b0:b0 + ng]
+        grav = np.zeros((3, 6, 6, 6, nvec))
+        # the reference
+        flux_r = np.full((3, 8, 3, 3, 3, nvec), np.nan)
+        tmp_r = np.full((3, 2, 3, 3, 3, nvec), np.nan)
+        emf_r = [np.full((3, 3, 3, nvec), np.nan) for _ in range(3)]
+        ref.ref_mag_unsplit(vp(batch), vp(grav), vp(flux_r), vp(emf_r[0]), vp(emf_r[1]), vp(emf_r[2]), vp(tmp_r), dbl(dx), dbl(dx), dbl(dx), dbl(dt), ng)
+        # the product's headers on the host
+        flux_h = np.full_like(flux_r, np.nan)
+        emf_h = [np.full_like(e, np.nan) for e in emf_r]
+        rc = host.mhd_host_unsplit(vp(batch), ng, nvec, dbl(dx), dbl(dt), dbl(gamma), dbl(smallr), dbl(smallc), slope_type, slope_mag_type, dbl(theta),
+                                   riemann, riemann2d, vp(flux_h), vp(emf_h[0]), vp(emf_h[1]), vp(emf_h[2]))
+        assert rc == 0
+        # where mag_unsplit defines its outputs (:100-236): fluxes through the faces of the central 2^3 cells, EMFs on their edges
+        for d in range(3):
+            sl = [slice(0, 3 if d == 2 else 2), slice(0, 3 if d == 1 else 2), slice(0, 3 if d == 0 else 2)]      # [k][j][i]
+            a, b = flux_h[d][:5][:, sl[0], sl[1], sl[2], :ng], flux_r[d][:5][:, sl[0], sl[1], sl[2], :ng]
+            assert np.isfinite(b).all()
+            assert np.array_equal(a, b), (b0, d, np.abs(a - b).max())
+        for e in range(3):
+            sl = [slice(0, 2 if e == 2 else 3), slice(0, 2 if e == 1 else 3), slice(0, 2 if e == 0 else 3)]
+            a, b = emf_h[e][sl[0], sl[1], sl[2], :ng], emf_r[e][sl[0], sl[1], sl[2], :ng]
+            assert np.isfinite(b).all()
+            assert np.array_equal(a, b), (b0, e, np.abs(a - b).max())
+
+
+@pytest.mark.parametrize("slope_type", SLOPES)
+@pytest.mark.parametrize("riemann,riemann2d", PAIRS)
+@pytest.mark.parametrize("kind", ["smooth", "jump"])
+def test_headers_equal_the_compiled_reference(libs, slope_type, riemann, riemann2d, kind):
+    nvec = libs[2]
+    _compare(libs, stencils(nvec, case_seed(slope_type, riemann, riemann2d), kind), TESTS_DX, TESTS_DT, 1e-10, slope_type, riemann, riemann2d)
+
+
+@pytest.fixture(scope="module")
+def harsh_uin():
+    return stencils(0, HARSH_SEED, "harsh")
+
+
+@pytest.mark.parametrize("slope_type", SLOPES)
+@pytest.mark.parametrize("riemann,riemann2d", PAIRS)
+@pytest.mark.parametrize("smallr", [1e-10, 0.6])
+def test_headers_equal_the_compiled_reference_on_the_harsh_state(libs, harsh_uin, slope_type, riemann, riemann2d, smallr):
+    """kind = "harsh": the same solver x slope matrix, bit for bit, with the density floor out of reach and binding"""
+    _compare(libs, harsh_uin, HARSH_DX, HARSH_DT, smallr, slope_type, riemann, riemann2d)
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
@@ -140,16 +191,14 @@ def test_cmpdt_cell_equals_the_compiled_reference(libs, seed):
             assert np.float64(got).view(np.int64) == np.float64(dt.value).view(np.int64)
 
 
-@pytest.mark.parametrize("riemann,riemann2d,slope_type", [(3, 5, 2), (0, 0, 1), (1, 1, 8)])
+@pytest.mark.parametrize("riemann,riemann2d,slope_type", GRAVITY)
 def test_gravity_predictor_of_ctoprim_equals_the_compiled_reference(libs, riemann, riemann2d, slope_type):
     """ctoprim's half-step gravity kick (mhd/umuscl.f90 ctoprim: u, v, w += gravin * dt / 2) through the whole of mag_unsplit:
     the branch of ctoprim_cell the device does not use yet (self-gravitating MHD runs stay the reference's), held ready"""
     host, ref, nvec = libs
     gamma, smallr, smallc, theta = 5.0 / 3.0, 1e-10, 1e-10, 1.5
-    uin = stencils(nvec, 4242 + riemann, "jump")
-    rng = np.random.default_rng(7)
-    grav = np.ascontiguousarray(rng.normal(0.0, 2.0, (3, 6, 6, 6, nvec)))
-    dx, dt = 1.0 / 64, 0.2 / 64
+    uin, grav = gravity_case(nvec, riemann)
+    dx, dt = TESTS_DX, TESTS_DT
     vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
     dbl = C.c_double
     flux_r = np.full((3, 8, 3, 3, 3, nvec), np.nan)

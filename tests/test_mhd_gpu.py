@@ -64,9 +64,9 @@ class StencilReference:
                                     riemann, riemann2d)
 
     def step(self, u, dx, dt):
-        n = u.shape[1]
-        no = n // 2
-        octs = [(ok, oj, oi) for ok in range(no) for oj in range(no) for oi in range(no)]
+        nz, ny, nx = u.shape[1:]                    # (a cube for the tests of this file; any even extents)
+        assert nz % 2 == 0 and ny % 2 == 0 and nx % 2 == 0
+        octs = [(ok, oj, oi) for ok in range(nz // 2) for oj in range(ny // 2) for oi in range(nx // 2)]
         unew = u.copy()
         nv = self.nvec
         vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
@@ -76,7 +76,7 @@ class StencilReference:
             ng = len(batch)
             uin = np.zeros((11, 6, 6, 6, nv))
             for l, (ok, oj, oi) in enumerate(batch):
-                kk, jj, ii = (2 * ok + off) % n, (2 * oj + off) % n, (2 * oi + off) % n
+                kk, jj, ii = (2 * ok + off) % nz, (2 * oj + off) % ny, (2 * oi + off) % nx
                 uin[..., l] = u[:, kk[:, None, None], jj[None, :, None], ii[None, None, :]]
             grav = np.zeros((3, 6, 6, 6, nv))
             flux = np.zeros((3, 8, 3, 3, 3, nv))
