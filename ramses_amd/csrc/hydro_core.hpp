@@ -45,6 +45,13 @@ struct HydroConst {
 
 #define RA_DEV __device__ __forceinline__
 
+// b of any lane of the wavefront, in every lane (a host compiler that only parses this header -- tests/native -- has no wavefront)
+#ifdef __HIP__
+RA_DEV bool wave_any(bool b) { return __builtin_amdgcn_ballot_w64(b) != 0; }
+#else
+RA_DEV bool wave_any(bool b) { return b; }
+#endif
+
 RA_DEV double dmaxd(double a, double b) { return __builtin_fmax(a, b); }
 RA_DEV double dmind(double a, double b) { return __builtin_fmin(a, b); }
 RA_DEV double fsignd(double a, double b) { return __builtin_copysign(a, b); }
@@ -271,7 +278,12 @@ RA_DEV void slope3_var(const double (&nb)[27], double (&d)[3]) {
 // ---------------------------------------------------------------------------
 // (fast build, rinv_in: ctoprim_cell's 1 / rho of this same cell -- ddiv(1, rho) = 1 * rcp_fast(rho), the bits of the rcp_fast(r)
 // it replaces -- where the caller has kept it)
-template <int NV, int NE = 0>
+// (fast build, RHO6: the caller consumes all six traced densities and calls wave-uniformly -- the full rows of the dense sweep.
+// The density floor of the six then sits behind ONE test per wave: six compares, an OR, a ballot, and the twelve selects only
+// in the branch of a wave that holds a density below smallr.  The same comparisons pick the same values on either path, a NaN
+// compares false on both.  A caller that uses one or two of the six keeps the per-value selects: the common test would keep
+// the dead densities alive.)
+template <int NV, int NE = 0, bool RHO6 = false>
 RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
                          double dtdx, double dtdy, double dtdz,
                          const HydroConst &P, double (&qm)[3][NV],
@@ -282,6 +294,7 @@ RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
   const double drz = dq[2][0], duz = dq[2][1], dvz = dq[2][2], dwz = dq[2][3], dpz = dq[2][4];
   const double div = dux + dvy + dwz;
 #ifdef RAMSES_AMD_FAST
+  constexpr bool RHO6_UNIFORM = RHO6;
   // s = -(u dq/dx + v dq/dy + w dq/dz + source) as explicit FMA chains
   const double rinv = rinv_in ? *rinv_in : rcp_fast(r);
   auto adv = [&](double ax, double ay, double az, double c0, double c1) {
@@ -304,6 +317,7 @@ RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
     se0[i] = adv(dq[0][5 + i], dq[1][5 + i], dq[2][5 + i], div * P.gamma_rad[i], q[5 + i]);
   }
 #else
+  constexpr bool RHO6_UNIFORM = false;   // the strict build keeps the reference's form
   const double sr0 = -u * drx - v * dry - w * drz - (div)*r;
   const double sp0 = -u * dpx - v * dpy - w * dpz - (div)*P.gamma * p;
   double su0 = -u * dux - v * duy - w * duz - (dpx) / r;
@@ -341,8 +355,10 @@ RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
       qm[d][n] = q[n] + hd + st;
     }
 #endif
-    if (qp[d][0] < P.smallr) qp[d][0] = r;
-    if (qm[d][0] < P.smallr) qm[d][0] = r;
+    if constexpr (!RHO6_UNIFORM) {
+      if (qp[d][0] < P.smallr) qp[d][0] = r;
+      if (qm[d][0] < P.smallr) qm[d][0] = r;
+    }
 #pragma unroll
     for (int i = 0; i < NE; i++) {
       const int n = 5 + i;
@@ -356,6 +372,17 @@ RA_DEV void trace3d_cell(const double (&q)[NV], const double (&dq)[3][NV],
       qp[d][n] = q[n] - hd + st;
       qm[d][n] = q[n] + hd + st;
 #endif
+    }
+  }
+  if constexpr (RHO6_UNIFORM) {
+    const bool low = (qp[0][0] < P.smallr) | (qm[0][0] < P.smallr) | (qp[1][0] < P.smallr) | (qm[1][0] < P.smallr) |
+                     (qp[2][0] < P.smallr) | (qm[2][0] < P.smallr);
+    if (__builtin_expect(wave_any(low), 0)) {
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        if (qp[d][0] < P.smallr) qp[d][0] = r;
+        if (qm[d][0] < P.smallr) qm[d][0] = r;
+      }
     }
   }
   // passive scalars, umuscl.f90:681-706

@@ -93,17 +93,28 @@ template <int RS, int NV>
 constexpr int dif_parked() { return (NV == 5 && RS == RIEMANN_EXACT) ? 2 * NV + 2 : ((NV == 6) ? NV + 2 : 0); }
 
 // wavefront shift by one lane: lane i receives the value of lane i-1 (shr) or
-// i+1 (shl); the edge lane keeps its own value (a halo lane, never stored).
+// i+1 (shl).  shr: lane 0 keeps its own value.  shl: lane 63 receives 0 (old = 0, bound_ctrl) -- the shift then writes a fresh
+// register and a source that stays live (px = ucur + (fx - wave_shl1(fx))) is not copied first, ten v_mov_b32 per plane of a
+// full row; shr's sources are dead at the shift and are shifted in place.  Either edge lane is a halo lane: a cell is owned
+// by lanes 2 .. 61 (r_upd: sweep_march, the tile kernels and scalar_march alike) and only those store.  The one thing lane 63
+// gets from a left shift is the -x face flux "of column 64" in its own x flux difference: that ends in lane 63's own partial
+// update (px -> registers or park[..][63], read by lane 63 alone) and is dropped by the store's range check.  No other lane
+// reads it: shr hands lane 63's values to nobody, and what lane 62 takes from lane 63 (fx) is unshifted.
 __device__ __forceinline__ double wave_shr1(double v) {
   int lo = __double2loint(v), hi = __double2hiint(v);
   lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xf, 0xf, false);
   hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
 }
+// (TIED: the shift as it was, lane 63 keeps its own value -- for the difmag tile kernels, strict only and at 256 VGPRs with
+// scratch: the untied form costs their NV = 6, 7 instantiations 4 - 8 B more of it.  There lane 63's corner divergences at
+// tx+1, and through them the coefficients of its own y and z faces, come from a left shift too, with the same fate: lane 63's
+// own fluxes, parked or in the y slots at [..][63], which lane 63 of rows ty-1 and ty+1 reads)
+template <bool TIED = false>
 __device__ __forceinline__ double wave_shl1(double v) {
   int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false);
-  hi = __builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false);
+  lo = TIED ? __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xf, 0xf, false) : __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, true);
+  hi = TIED ? __builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xf, 0xf, false) : __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, true);
   return __hiloint2double(hi, lo);
 }
 
@@ -195,7 +206,7 @@ __device__ __forceinline__ void plane_store(double *var_base, unsigned plane_byt
 }
 
 __device__ __forceinline__ int wave_shr1_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int wave_shl1_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x130, 0xf, 0xf, false); }
+__device__ __forceinline__ int wave_shl1_i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xf, 0xf, true); }   // (lane 63: 0, as wave_shl1)
 // status byte of a cell: lane part and wave-uniform part of the cell index; a lane without a tile (index beyond ncell) reads 0
 __device__ __forceinline__ int stat_load(const unsigned char *base, unsigned ncell, unsigned lane_cell, unsigned plane_cell) {
   __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(base), 0, ncell, 0x00020000);
@@ -643,8 +654,9 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       }
       double qm[3][NV], qp[3][NV];
       if (SCHEME == 0) {
-        if constexpr (TRIM) trace3d_cell<NV, NE>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp, &rinv_c);
-        else trace3d_cell<NV, NE>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp);
+        // (a full row consumes all six traced densities: their floor behind one wave-uniform test, trace3d_cell RHO6)
+        if constexpr (TRIM) trace3d_cell<NV, NE, r_fxz>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp, &rinv_c);
+        else trace3d_cell<NV, NE, r_fxz>(qb, dq, dtdx, dtdx, dtdx, P, qm, qp);
       } else {
         const double cc = ctoprim_sound(qb[0], qb[4], P);
         tracexyz_cell<NV>(qb, dq, cc, dtdx, dtdx, dtdx, P, qm, qp);
@@ -792,10 +804,10 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
 #pragma unroll
         for (int n = 0; n < NV; n++) fzlo[n] = dpark[n][ty - 2][tx];
       }
-      const double c0x = wave_shl1(dif_c0), n0x = wave_shl1(dn[0]);     // the corners at tx+1
+      const double c0x = wave_shl1<true>(dif_c0), n0x = wave_shl1<true>(dn[0]);     // the corners at tx+1
       dif_cy = difmag::consup_coef(D.difmag, difmag::consup_div1_y(dif_c0, c0x, dn[0], n0x));
       if constexpr (r_fxz) {
-        const double c1x = wave_shl1(dif_c1);
+        const double c1x = wave_shl1<true>(dif_c1);
         const double cx = difmag::consup_coef(D.difmag, difmag::consup_div1_x(dif_c0, dif_c1, dn[0], dn[1]));
         const double cz = difmag::consup_coef(D.difmag, difmag::consup_div1_z(dif_c0, c0x, dif_c1, c1x));
         // hydro/godunov_fine.f90:720-747 after consup: the flux through a face is reset when the cell on either side is refined
@@ -808,7 +820,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
           const double fxn = zx ? 0.0 : fxd, fzn = zz ? 0.0 : fzd;
           dz[n] = fzlo[n] - fzn;              // z flux difference of plane c-1
           fzlo[n] = fzn;
-          px[n] = ucur[n] + (fxn - wave_shl1(fxn));
+          px[n] = ucur[n] + (fxn - wave_shl1<true>(fxn));
         }
       }
       dif_c0 = dn[0]; dif_c1 = dn[1];
