@@ -28,24 +28,11 @@
 #include <cstdlib>
 #include <vector>
 
+#include "host_util.hpp"
 #include "sweep_args.hpp"
 
 namespace ramses_amd {
 namespace amrlayout {
-
-struct Buf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    if (bytes == 0) bytes = 8;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
 
 typedef unsigned long long u64;
 constexpr int KEY_BITS = 19;                  // oct coordinates of levels <= 20
@@ -239,8 +226,8 @@ struct LevelMap {
   int layout = 0;              // 0: compact (Z-order), 1: tiles
   long base = 0, cap = 0;      // device indices [base, base + cap), 1-based
   int no = 0, ntx = 0, nty = 0, ntz = 0, ntiles = 0;
-  Buf hoct, key, doct;         // the level's octs: host index, position, device index (same order)
-  Buf dir, tileid;             // tiles: directory [ntz][nty][ntx], rank -> tile
+  DevBuf hoct, key, doct;         // the level's octs: host index, position, device index (same order)
+  DevBuf dir, tileid;             // tiles: directory [ntz][nty][ntx], rank -> tile
 };
 
 inline int grid1(long n, int b = 256) { long g = (n + b - 1) / b; return (int)(g < 1 ? 1 : g); }
@@ -251,9 +238,9 @@ struct DevMap {
   int serial = 0;              // bumped by every build(): whatever was derived from device indices is stale
   int nlev = 0;
   std::vector<LevelMap> lev;   // [0] unused, [l] level l
-  Buf perm, iperm, okey, son_h, nbor_h, father_h;
-  Buf need, rank, cubtmp, cnt, mkey, mkey2, idx, idx2;
-  Buf c_hoct[2], c_key[2];     // BFS double buffer
+  DevBuf perm, iperm, okey, son_h, nbor_h, father_h;
+  DevBuf need, rank, cubtmp, cnt, mkey, mkey2, idx, idx2;
+  DevBuf c_hoct[2], c_key[2];     // BFS double buffer
   int first_changed = 0;       // of the last build: the coarsest level that was laid out again (nlev + 1: none)
   long kept_end = 1;           // of the last build: first device index after the levels that kept their layout
   int version_counter = 0;
@@ -264,7 +251,7 @@ struct DevMap {
 #define LCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
 
   static void drop(LevelMap &L) {
-    for (Buf *b : {&L.hoct, &L.key, &L.doct, &L.dir, &L.tileid}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    for (DevBuf *b : {&L.hoct, &L.key, &L.doct, &L.dir, &L.tileid}) b->release();
   }
   void reset(long ngh_, long ngd_, long ncoarse_, bool want) {
     for (size_t l = 1; l < lev.size(); l++) drop(lev[l]);
@@ -331,7 +318,7 @@ struct DevMap {
     bool keeping = !fresh;
     int k0 = 0, nnew = 0;
     for (int l = 1; l <= MAX_LEVEL + 1; l++) {
-      Buf &bo = c_hoct[l & 1], &bk = c_key[l & 1];
+      DevBuf &bo = c_hoct[l & 1], &bk = c_key[l & 1];
       int nc = 0;
       if (l == 1) {
         const u64 kz = 0;

@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -434,28 +433,26 @@ int64_t ramses_amd_mg_workspace_doubles(int level) {
   return (int64_t)(mg_hier_size(level) + MG_MAX_PARTIALS + 8);
 }
 
-#define MGCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(e_, what); } while (0)
-
 int ramses_amd_mg_gauss_seidel(double *d_phi, const double *d_rhs, int n, double dx2, int redstep, void *stream) {
   if (!d_phi || !d_rhs || n < 2 || (n & (n - 1))) return fail(RAMSES_AMD_EINVAL, "bad argument (n must be a power of two)");
-  MGCHK(mg_launch_gs(d_phi, d_rhs, n, dx2, redstep ? 0 : 1, reinterpret_cast<hipStream_t>(stream)), "mg gs launch");
+  HCHK(mg_launch_gs(d_phi, d_rhs, n, dx2, redstep ? 0 : 1, reinterpret_cast<hipStream_t>(stream)), "mg gs launch");
   return 0;
 }
 int ramses_amd_mg_residual(const double *d_phi, const double *d_rhs, double *d_res, int n, double dx,
                            double *d_work, double *d_norm2, void *stream) {
   if (!d_phi || !d_rhs || !d_res || n < 2 || (n & (n - 1))) return fail(RAMSES_AMD_EINVAL, "bad argument (n must be a power of two)");
   if (d_norm2 && !d_work) return fail(RAMSES_AMD_EINVAL, "norm needs a workspace of %d doubles", MG_MAX_PARTIALS);
-  MGCHK(mg_launch_residual(d_phi, d_rhs, d_res, n, dx, d_work, d_norm2, reinterpret_cast<hipStream_t>(stream)), "mg residual launch");
+  HCHK(mg_launch_residual(d_phi, d_rhs, d_res, n, dx, d_work, d_norm2, reinterpret_cast<hipStream_t>(stream)), "mg residual launch");
   return 0;
 }
 int ramses_amd_mg_restrict(const double *d_res_f, double *d_rhs_c, double *d_u1_c, int nf, void *stream) {
   if (!d_res_f || !d_rhs_c || !d_u1_c || nf < 2 || (nf & (nf - 1))) return fail(RAMSES_AMD_EINVAL, "bad argument (nf must be a power of two)");
-  MGCHK(mg_launch_restrict(d_res_f, d_rhs_c, d_u1_c, nf, reinterpret_cast<hipStream_t>(stream)), "mg restrict launch");
+  HCHK(mg_launch_restrict(d_res_f, d_rhs_c, d_u1_c, nf, reinterpret_cast<hipStream_t>(stream)), "mg restrict launch");
   return 0;
 }
 int ramses_amd_mg_interp_correct(double *d_phi_f, const double *d_corr_c, int nf, void *stream) {
   if (!d_phi_f || !d_corr_c || nf < 2 || (nf & (nf - 1))) return fail(RAMSES_AMD_EINVAL, "bad argument (nf must be a power of two)");
-  MGCHK(mg_launch_interp(d_phi_f, d_corr_c, nf, reinterpret_cast<hipStream_t>(stream)), "mg interp launch");
+  HCHK(mg_launch_interp(d_phi_f, d_corr_c, nf, reinterpret_cast<hipStream_t>(stream)), "mg interp launch");
   return 0;
 }
 
@@ -507,7 +504,7 @@ int ramses_amd_mg_smooth_fused(const double *d_phi_in, double *d_phi_out, const 
   if (npass != 2 && npass != 4) return fail(RAMSES_AMD_EINVAL, "npass must be 2 or 4");
   if (n < 64) return fail(RAMSES_AMD_EINVAL, "the fused smoother needs n >= 64 (got %d); use the per-colour kernels", n);
   if ((d_res || d_norm2) && !d_work) return fail(RAMSES_AMD_EINVAL, "residual/norm need a workspace of %d doubles", MG_MAX_PARTIALS);
-  MGCHK(mg_launch_smooth_fused(d_phi_in, d_phi_out, d_rhs, d_res, d_work, d_norm2, n, dx, npass, reinterpret_cast<hipStream_t>(stream)), "mg fused smoother launch");
+  HCHK(mg_launch_smooth_fused(d_phi_in, d_phi_out, d_rhs, d_res, d_work, d_norm2, n, dx, npass, reinterpret_cast<hipStream_t>(stream)), "mg fused smoother launch");
   return 0;
 }
 
@@ -517,7 +514,7 @@ int ramses_amd_gradient_phi_brick(int level, const double *d_phi, double *d_f, v
   const double dx = std::ldexp(1.0, -level);
   const double a = 0.50 * 4.0 / 3.0 / dx;   // force_fine.f90:233-234
   const double b = 0.25 * 1.0 / 3.0 / dx;
-  MGCHK(mg_launch_gradient(d_phi, d_f, n, a, b, reinterpret_cast<hipStream_t>(stream)), "gradient_phi launch");
+  HCHK(mg_launch_gradient(d_phi, d_f, n, a, b, reinterpret_cast<hipStream_t>(stream)), "gradient_phi launch");
   return 0;
 }
 
@@ -599,20 +596,20 @@ int ramses_amd_mg_smooth_fused_ghost(const double *d_phi_in, double *d_phi_out, 
   const int H = (d_res || d_norm2) ? npass + 1 : npass;
   if (ng < H) return fail(RAMSES_AMD_EINVAL, "ghost width %d does not cover the %d-cell dependency cone of %d colour passes", ng, H, npass);
   if ((d_res || d_norm2) && !d_work) return fail(RAMSES_AMD_EINVAL, "residual/norm need a workspace of %d doubles", MG_MAX_PARTIALS);
-  MGCHK(mg_launch_smooth_fused(d_phi_in, d_phi_out, d_rhs, d_res, d_work, d_norm2, nx, dx, npass, reinterpret_cast<hipStream_t>(stream), ng,
+  HCHK(mg_launch_smooth_fused(d_phi_in, d_phi_out, d_rhs, d_res, d_work, d_norm2, nx, dx, npass, reinterpret_cast<hipStream_t>(stream), ng,
                                nullptr, nullptr, nullptr, ny, nz), "mg fused smoother launch");
   return 0;
 }
 // f2 = fourpi*(rho - rho_tot) over N doubles (make_fine_bc_rhs on an unmasked level)
 int ramses_amd_mg_rhs(const double *d_rho, double *d_f2, int64_t N, double fourpi, double rho_tot, void *stream) {
   if (!d_rho || !d_f2 || N < 1) return fail(RAMSES_AMD_EINVAL, "bad argument");
-  MGCHK(mg_launch_rhs(d_rho, d_f2, (long)N, fourpi, rho_tot, reinterpret_cast<hipStream_t>(stream)), "mg rhs launch");
+  HCHK(mg_launch_rhs(d_rho, d_f2, (long)N, fourpi, rho_tot, reinterpret_cast<hipStream_t>(stream)), "mg rhs launch");
   return 0;
 }
 int ramses_amd_mg_restrict_ghost(const double *d_res_f, double *d_rhs_c, int nfx, int nfy, int nfz, int ngf, int ngc, void *stream) {
   if (!d_res_f || !d_rhs_c || !brick_extent_ok(nfx) || !brick_extent_ok(nfy) || !brick_extent_ok(nfz) || ngf < 0 || ngc < 0)
     return fail(RAMSES_AMD_EINVAL, "bad argument (brick extents must be powers of two)");
-  MGCHK(mg_launch_restrict_ghost(d_res_f, d_rhs_c, nfx, nfy, nfz, ngf, ngc, reinterpret_cast<hipStream_t>(stream)), "mg restrict launch");
+  HCHK(mg_launch_restrict_ghost(d_res_f, d_rhs_c, nfx, nfy, nfz, ngf, ngc, reinterpret_cast<hipStream_t>(stream)), "mg restrict launch");
   return 0;
 }
 int ramses_amd_mg_interp_correct_ghost(double *d_phi_f, int nfx, int nfy, int nfz, int ngf, const double *d_corr_c, int ngc,
@@ -622,7 +619,7 @@ int ramses_amd_mg_interp_correct_ghost(double *d_phi_f, int nfx, int nfy, int nf
   if (cglob == 0 && ngc < 1) return fail(RAMSES_AMD_EINVAL, "the local coarse brick needs >= 1 ghost layer");
   if (cglob != 0 && !coarse_origin) return fail(RAMSES_AMD_EINVAL, "replicated coarse level needs the origin of this rank's part");
   const int ox = coarse_origin ? coarse_origin[0] : 0, oy = coarse_origin ? coarse_origin[1] : 0, oz = coarse_origin ? coarse_origin[2] : 0;
-  MGCHK(mg_launch_interp_ghost(d_phi_f, nfx, nfy, nfz, ngf, d_corr_c, ngc, cglob, ox, oy, oz, reinterpret_cast<hipStream_t>(stream)), "mg interp launch");
+  HCHK(mg_launch_interp_ghost(d_phi_f, nfx, nfy, nfz, ngf, d_corr_c, ngc, cglob, ox, oy, oz, reinterpret_cast<hipStream_t>(stream)), "mg interp launch");
   return 0;
 }
 int ramses_amd_gradient_phi_ghost(const double *d_phi, double *d_f, int nx, int ny, int nz, int ng, double dx, void *stream) {
@@ -630,7 +627,7 @@ int ramses_amd_gradient_phi_ghost(const double *d_phi, double *d_f, int nx, int 
     return fail(RAMSES_AMD_EINVAL, "gradient_phi needs a brick of power-of-two extents with 2 ghost layers of phi");
   const double a = 0.50 * 4.0 / 3.0 / dx;   // force_fine.f90:233-234
   const double b = 0.25 * 1.0 / 3.0 / dx;
-  MGCHK(mg_launch_gradient_ghost(d_phi, d_f, nx, ny, nz, ng, a, b, reinterpret_cast<hipStream_t>(stream)), "gradient_phi launch");
+  HCHK(mg_launch_gradient_ghost(d_phi, d_f, nx, ny, nz, ng, a, b, reinterpret_cast<hipStream_t>(stream)), "gradient_phi launch");
   return 0;
 }
 // recursive_multigrid_coarse on a dense periodic level (a replicated coarse level
@@ -642,10 +639,10 @@ int ramses_amd_mg_coarse_solve_dense(int level, const double *d_rhs, double *d_u
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const size_t N = mg_level_cells(level);
   double *u1 = d_work + mg_hier_offset(level + 1, level, 0), *u2 = d_work + mg_hier_offset(level + 1, level, 1);
-  MGCHK(hipMemcpyAsync(u2, d_rhs, sizeof(double) * N, hipMemcpyDeviceToDevice, s), "rhs copy");
-  MGCHK(hipMemsetAsync(u1, 0, sizeof(double) * N, s), "memset");
-  MGCHK(mg_coarse_cycle(d_work, level + 1, level, safe, s), "mg coarse cycle");
-  MGCHK(hipMemcpyAsync(d_u1, u1, sizeof(double) * N, hipMemcpyDeviceToDevice, s), "u1 copy");
+  HCHK(hipMemcpyAsync(u2, d_rhs, sizeof(double) * N, hipMemcpyDeviceToDevice, s), "rhs copy");
+  HCHK(hipMemsetAsync(u1, 0, sizeof(double) * N, s), "memset");
+  HCHK(mg_coarse_cycle(d_work, level + 1, level, safe, s), "mg coarse cycle");
+  HCHK(hipMemcpyAsync(d_u1, u1, sizeof(double) * N, hipMemcpyDeviceToDevice, s), "u1 copy");
   return 0;
 }
 
@@ -663,7 +660,7 @@ int ramses_amd_multigrid_fine_brick(int level, const double *d_rho, double rho_t
   const double dx = std::ldexp(1.0, -level), dx2 = dx * dx;
   double *partial = d_work + mg_hier_size(level);
   double *d_norm = partial + MG_MAX_PARTIALS;
-  MGCHK(mg_launch_rhs(d_rho, d_f2, N, fourpi, rho_tot, s), "mg rhs launch");
+  HCHK(mg_launch_rhs(d_rho, d_f2, N, fourpi, rho_tot, s), "mg rhs launch");
   int iter = 0;
   double err = 1.0, last_err, i_res_norm2 = 0.0, res_norm2 = 0.0;
   const bool fused = (n >= MG_FUSED_MIN_N) && g_mg_fused;
@@ -673,39 +670,39 @@ int ramses_amd_multigrid_fine_brick(int level, const double *d_rho, double rho_t
     double *cur = d_phi, *oth = d_phi2;
     bool restricted = false;
     if (fused) {
-      MGCHK(mg_smooth4(&cur, &oth, d_f2, d_f1, partial, iter == 1 ? d_norm : nullptr, n, dx, s,
+      HCHK(mg_smooth4(&cur, &oth, d_f2, d_f1, partial, iter == 1 ? d_norm : nullptr, n, dx, s,
                        level > 1 ? d_work + mg_hier_offset(level, level - 1, 1) : nullptr,
                        level > 1 ? d_work + mg_hier_offset(level, level - 1, 0) : nullptr, &restricted), "mg fused smoother launch");
     } else {
       for (int i = 0; i < ngs_fine; i++) {
-        MGCHK(mg_launch_gs(d_phi, d_f2, n, dx2, 0, s), "mg gs launch");
-        MGCHK(mg_launch_gs(d_phi, d_f2, n, dx2, 1, s), "mg gs launch");
+        HCHK(mg_launch_gs(d_phi, d_f2, n, dx2, 0, s), "mg gs launch");
+        HCHK(mg_launch_gs(d_phi, d_f2, n, dx2, 1, s), "mg gs launch");
       }
-      MGCHK(mg_launch_residual(d_phi, d_f2, d_f1, n, dx, partial, iter == 1 ? d_norm : nullptr, s), "mg residual launch");
+      HCHK(mg_launch_residual(d_phi, d_f2, d_f1, n, dx, partial, iter == 1 ? d_norm : nullptr, s), "mg residual launch");
     }
     if (iter == 1) {
-      MGCHK(hipMemcpyAsync(&i_res_norm2, d_norm, sizeof(double), hipMemcpyDeviceToHost, s), "norm copy");
+      HCHK(hipMemcpyAsync(&i_res_norm2, d_norm, sizeof(double), hipMemcpyDeviceToHost, s), "norm copy");
     }
     if (level > 1) {
-      if (!restricted) MGCHK(mg_launch_restrict(d_f1, d_work + mg_hier_offset(level, level - 1, 1), d_work + mg_hier_offset(level, level - 1, 0), n, s), "mg restrict launch");
-      MGCHK(mg_coarse_cycle(d_work, level, level - 1, *safe_mode, s), "mg coarse cycle");
-      if (!fused) MGCHK(mg_launch_interp(cur, d_work + mg_hier_offset(level, level - 1, 0), n, s), "mg interp launch");
+      if (!restricted) HCHK(mg_launch_restrict(d_f1, d_work + mg_hier_offset(level, level - 1, 1), d_work + mg_hier_offset(level, level - 1, 0), n, s), "mg restrict launch");
+      HCHK(mg_coarse_cycle(d_work, level, level - 1, *safe_mode, s), "mg coarse cycle");
+      if (!fused) HCHK(mg_launch_interp(cur, d_work + mg_hier_offset(level, level - 1, 0), n, s), "mg interp launch");
     }
     if (fused) {
       // prolongation + post-smoothing: only the norm of the residual is needed (f(:,1) is scratch in
       // the reference and force_fine overwrites it next): it is not written to HBM
-      MGCHK(mg_smooth4(&cur, &oth, d_f2, nullptr, partial, d_norm + 1, n, dx, s, nullptr, nullptr, nullptr,
+      HCHK(mg_smooth4(&cur, &oth, d_f2, nullptr, partial, d_norm + 1, n, dx, s, nullptr, nullptr, nullptr,
                        level > 1 ? d_work + mg_hier_offset(level, level - 1, 0) : nullptr), "mg fused smoother launch");
       // the result is back in d_phi (two buffer swaps, or none)
     } else {
       for (int i = 0; i < ngs_fine; i++) {
-        MGCHK(mg_launch_gs(d_phi, d_f2, n, dx2, 0, s), "mg gs launch");
-        MGCHK(mg_launch_gs(d_phi, d_f2, n, dx2, 1, s), "mg gs launch");
+        HCHK(mg_launch_gs(d_phi, d_f2, n, dx2, 0, s), "mg gs launch");
+        HCHK(mg_launch_gs(d_phi, d_f2, n, dx2, 1, s), "mg gs launch");
       }
-      MGCHK(mg_launch_residual(d_phi, d_f2, d_f1, n, dx, partial, d_norm + 1, s), "mg residual launch");
+      HCHK(mg_launch_residual(d_phi, d_f2, d_f1, n, dx, partial, d_norm + 1, s), "mg residual launch");
     }
-    MGCHK(hipMemcpyAsync(&res_norm2, d_norm + 1, sizeof(double), hipMemcpyDeviceToHost, s), "norm copy");
-    MGCHK(hipStreamSynchronize(s), "stream sync");
+    HCHK(hipMemcpyAsync(&res_norm2, d_norm + 1, sizeof(double), hipMemcpyDeviceToHost, s), "norm copy");
+    HCHK(hipStreamSynchronize(s), "stream sync");
     last_err = err;
     err = std::sqrt(res_norm2 / (i_res_norm2 + 1e-20 * (rho_tot * rho_tot)));
     if (err < epsilon || iter >= MAXITER) break;

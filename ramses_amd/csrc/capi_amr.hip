@@ -16,7 +16,6 @@
 // Compiled with -ffp-contract=off: the reference's operation order.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -37,17 +36,6 @@
 #include "capi_shared.hpp"
 
 using namespace ramses_amd;
-
-extern "C" int ramses_amd_set_error(int code, const char *msg);
-static int failf(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return ramses_amd_set_error(code, buf);
-}
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failf(RAMSES_AMD_EHIP, "%s: %s", what, hipGetErrorString(e_)); } while (0)
 
 namespace {
 
@@ -739,21 +727,7 @@ __global__ __launch_bounds__(256) void bnd_store_kernel(BndArgs A) {
   }
 }
 
-using amrlayout::Buf;
-
-struct PinBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    if (bytes == 0) bytes = 8;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
+using Buf = DevBuf;
 
 // MPI: the communicators of one level as build_comm left them (amr/amr_commons.f90:170-179, emission(icpu,l)%igrid and
 // reception(icpu,l)%igrid concatenated in icpu order)
@@ -799,7 +773,7 @@ struct LevelPlan {
   int rows = 0;                                                   // interior rows of its work items (8, or 4 for the 8-row kernels)
   Buf gfather, gslot, gcell, gsten, work, corr, corr_tgt, evt_of, flag, events;
   void release() {
-    for (Buf *b : {&gfather, &gslot, &gcell, &gsten, &work, &corr, &corr_tgt, &evt_of, &flag, &events}) { if (b->p) (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+    for (Buf *b : {&gfather, &gslot, &gcell, &gsten, &work, &corr, &corr_tgt, &evt_of, &flag, &events}) b->release();
     version = -1;
   }
 };
@@ -849,12 +823,7 @@ struct AmrRes {
 };
 AmrRes g_ar;
 
-inline int grid_for(long n) {
-  long g = (n + 255) / 256;
-  if (g < 1) g = 1;
-  if (g > 8192) g = 8192;
-  return (int)g;
-}
+constexpr int GRID_CAP = 8192;   // blocks of this unit's one-dimensional launches: grid_for(n, GRID_CAP)
 
 // RAMSES_AMD_EVENT_ORDER (A/B of the order the surface pass visits the (oct, face) events in): face | tile | oct
 int event_order() {
@@ -889,7 +858,7 @@ int check_lists(AmrRes &R, const char *where) {
     R.err_pending = 0;
     if (miss) {
       HCHK(hipMemset(R.err.p, 0, sizeof(int)), "memset");
-      return failf(RAMSES_AMD_EINVAL, "%s: %d father cells needed by an oct do not exist (tree inconsistent; godunov_fine up to level %d since the last check)", where, miss, lev);
+      return fail(RAMSES_AMD_EINVAL, "%s: %d father cells needed by an oct do not exist (tree inconsistent; godunov_fine up to level %d since the last check)", where, miss, lev);
     }
   }
   if (!R.map.on) return 0;
@@ -897,7 +866,7 @@ int check_lists(AmrRes &R, const char *where) {
   HCHK(hipMemcpy(&bad, R.bad.p, sizeof(int), hipMemcpyDeviceToHost), "D2H");
   if (bad) {
     HCHK(hipMemset(R.bad.p, 0, sizeof(int)), "memset");
-    return failf(RAMSES_AMD_EINVAL, "%s: %d octs of a list are not in the tree the device holds", where, bad);
+    return fail(RAMSES_AMD_EINVAL, "%s: %d octs of a list are not in the tree the device holds", where, bad);
   }
   return 0;
 }
@@ -934,8 +903,8 @@ int sorted_list(AmrRes &R, LvlArgs &A) {
   return 0;
 }
 int set_level(AmrRes &R, int ngrid, const int *igrid, LvlArgs &A) {
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
-  if (ngrid < 0 || (ngrid > 0 && !igrid)) return failf(RAMSES_AMD_EINVAL, "bad oct list");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
+  if (ngrid < 0 || (ngrid > 0 && !igrid)) return fail(RAMSES_AMD_EINVAL, "bad oct list");
   {
     // the same list as before (same array, length, layout; first, last and eight entries in between equal): already there.
     // (Contract of the C ABI: an oct list does not change between two calls of ramses_amd_amrres_tree other than as a whole.)
@@ -965,13 +934,13 @@ int set_level(AmrRes &R, int ngrid, const int *igrid, LvlArgs &A) {
 // ---- one level between a device vector and a host vector: EVERY such move goes through the three functions below -----------
 // The n octs of a list have two names: d_ig[i] on the device (device indices, strides R.ncell / R.ngridmax) and h_ig[i] on the
 // host (the caller's list as it came, strides R.ncell_h / R.ngh).  In between the cells travel packed, [ncomp][8][n].
-int xfer_hip(hipError_t e, const char *step, const char *what) { return e == hipSuccess ? 0 : failf(RAMSES_AMD_EHIP, "%s %s: %s", step, what, hipGetErrorString(e)); }
+int xfer_hip(hipError_t e, const char *step, const char *what) { return e == hipSuccess ? 0 : fail(RAMSES_AMD_EHIP, "%s %s: %s", step, what, hipGetErrorString(e)); }
 #define XCHK(call, step) do { if (int rc_ = xfer_hip((call), step, what)) return rc_; } while (0)
 // the device half of the way home: gather into R.pack, blocking copy into R.hpack
 int level_fetch(AmrRes &R, double *dvec, int ncomp, const int *d_ig, int n, hipStream_t s, const char *what) {
   const size_t cnt = (size_t)n * 8 * (size_t)ncomp;
   XCHK(R.pack.ensure(sizeof(double) * cnt), "hipMalloc");
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8)), dim3(256), 0, s, dvec, R.pack.as<double>(), d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax);
+  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, s, dvec, R.pack.as<double>(), d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax);
   XCHK(hipGetLastError(), "pack launch");
   R.hpack.resize(cnt);
   XCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H");
@@ -1000,7 +969,7 @@ int level_from_host(AmrRes &R, double *dvec, int ncomp, const int *d_ig, int n, 
     }
   XCHK(R.pack.ensure(sizeof(double) * cnt), "hipMalloc");
   XCHK(hipMemcpy(R.pack.p, R.hpack.data(), sizeof(double) * cnt, hipMemcpyHostToDevice), "H2D");
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8)), dim3(256), 0, nullptr, dvec, R.pack.as<double>(), d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax);
+  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, dvec, R.pack.as<double>(), d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax);
   XCHK(hipGetLastError(), "unpack launch");
   XCHK(hipStreamSynchronize(nullptr), "sync");
   return 0;
@@ -1082,8 +1051,8 @@ int ramses_amd_amrres_active(void) { return g_ar.valid ? 1 : 0; }
 // whose octs changed (and every finer one) are laid out again in device numbers; the others keep theirs, and their data.
 int ramses_amd_amrres_tree(const int *son, const int *nbor, const int *father) {
   AmrRes &R = g_ar;
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state");
-  if (!son || !nbor || !father) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state");
+  if (!son || !nbor || !father) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   hipError_t e = R.map.build(son, nbor, father, R.son.as<int>(), R.nbor.as<int>(), R.father.as<int>(), R.stat.as<unsigned char>(), nullptr);
   if (e == hipErrorInvalidValue && R.map.on && R.map.overflow) {
     // A legitimate regrid: the finer levels grew, and the free tile slots of the levels that kept their layout are in the way
@@ -1115,7 +1084,7 @@ int ramses_amd_amrres_tree(const int *son, const int *nbor, const int *father) {
     }
     if (park.p) (void)hipFree(park.p);
   }
-  if (e != hipSuccess) return failf(e == hipErrorInvalidValue ? RAMSES_AMD_EINVAL : RAMSES_AMD_EHIP, "tree layout on the device: %s", e == hipErrorInvalidValue ? R.map.why_not : hipGetErrorString(e));
+  if (e != hipSuccess) return fail(e == hipErrorInvalidValue ? RAMSES_AMD_EINVAL : RAMSES_AMD_EHIP, "tree layout on the device: %s", e == hipErrorInvalidValue ? R.map.why_not : hipGetErrorString(e));
   if (R.map.on) {
     // (list positions of the levels that were laid out again; the kept levels keep their plans)
     const long k = R.map.kept_end;
@@ -1133,8 +1102,8 @@ int ramses_amd_amrres_tree(const int *son, const int *nbor, const int *father) {
 // everything: the hydro state uold(1:ncell,1:nvar) and the tree
 int ramses_amd_amrres_load(int nvar, int64_t ngridmax, int64_t ncoarse, const double *uold, const int *son, const int *nbor,
                            const int *father) {
-  if (!uold || !son || !nbor || !father) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (nvar < 5 || nvar > 7 || ngridmax < 1 || ncoarse < 1) return failf(RAMSES_AMD_EUNSUPPORTED, "AMR residency implements NVAR=5..7");
+  if (!uold || !son || !nbor || !father) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (nvar < 5 || nvar > 7 || ngridmax < 1 || ncoarse < 1) return fail(RAMSES_AMD_EUNSUPPORTED, "AMR residency implements NVAR=5..7");
   AmrRes &R = g_ar;
   { static bool registered = false; if (!registered) { registered = true; atexit(amrres_report); } }
   R.valid = false; R.grav = false; R.pfix = false;
@@ -1190,7 +1159,7 @@ int ramses_amd_amrres_sync_level(int ngrid, const int *igrid, double *uold) {
   AmrRes &R = g_ar;
   LvlArgs A;
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
-  if (uold != R.h_uold) return failf(RAMSES_AMD_EINVAL, "sync_level: not the array the state was loaded from");
+  if (uold != R.h_uold) return fail(RAMSES_AMD_EINVAL, "sync_level: not the array the state was loaded from");
   if (ngrid == 0) return 0;
   if (int rc = level_to_host(R, R.uold.as<double>(), R.nvar, R.cur_ig, ngrid, igrid, uold, nullptr, "level")) return rc;
   return check_lists(R, "sync_level");
@@ -1209,7 +1178,7 @@ int ramses_amd_amrres_load_level(int ngrid, const int *igrid, const double *uold
 int ramses_amd_amrres_sync_all(double *uold) {
   AmrRes &R = g_ar;
   if (!R.valid) return 0;
-  if (uold != R.h_uold) return failf(RAMSES_AMD_EINVAL, "sync_all: not the array the state was loaded from");
+  if (uold != R.h_uold) return fail(RAMSES_AMD_EINVAL, "sync_all: not the array the state was loaded from");
   if (!R.map.on) {
     HCHK(hipMemcpy(uold, R.uold.p, sizeof(double) * (size_t)R.nvar * (size_t)R.ncell, hipMemcpyDeviceToHost), "D2H uold");
     return 0;
@@ -1233,32 +1202,32 @@ int ramses_amd_amrres_set_unew(int ngrid, const int *igrid) {
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  hipLaunchKernelGGL(lvl_copy_kernel, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, A, A.unew, A.uold);
+  hipLaunchKernelGGL(lvl_copy_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, A.unew, A.uold);
   HCHK(hipGetLastError(), "set_unew launch");
   return 0;
 }
 
 int ramses_amd_amrres_set_uold(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold")) return rc_;
-  if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  hipLaunchKernelGGL(lvl_set_uold_kernel, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, A, p->smallr);
+  hipLaunchKernelGGL(lvl_set_uold_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, p->smallr);
   HCHK(hipGetLastError(), "set_uold launch");
   return 0;
 }
 
 int ramses_amd_amrres_upload_fine(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, int interpol_var) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_upload_fine")) return rc_;
-  if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (interpol_var < 0 || interpol_var > 2) return failf(RAMSES_AMD_EINVAL, "interpol_var must be 0, 1 or 2");
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (interpol_var < 0 || interpol_var > 2) return fail(RAMSES_AMD_EINVAL, "interpol_var must be 0, 1 or 2");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  const dim3 g(grid_for((long)ngrid * 8)), b(256);
+  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
   switch (A.nvar) {
     case 5: hipLaunchKernelGGL(lvl_upload_kernel<5>, g, b, 0, nullptr, A, interpol_var, p->smallr); break;
     case 6: hipLaunchKernelGGL(lvl_upload_kernel<6>, g, b, 0, nullptr, A, interpol_var, p->smallr); break;
@@ -1271,7 +1240,7 @@ int ramses_amd_amrres_upload_fine(const ramses_amd_hydro_params *p, int ngrid, c
 // out4 = {dt_loc (min with dt_in), mass_loc, sum(E*vol), eint_loc} over the leaf cells of the level
 int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dx, double dt_in, double *out4) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_courant")) return rc_;
-  if (!p || !out4) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p || !out4) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   AmrRes &R = g_ar;
@@ -1280,7 +1249,7 @@ int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const
   const double dt0 = p->courant_factor * dx / p->smallc;
   hipLaunchKernelGGL(lvl_courant_init_kernel, dim3(1), dim3(1), 0, nullptr, R.red.as<double>(), dt0);
   if (ngrid > 0) {
-    int g = grid_for((long)ngrid * 8);
+    int g = grid_for((long)ngrid * 8, GRID_CAP);
     if (g > 2048) g = 2048;
     if (R.grav) hipLaunchKernelGGL(lvl_courant_kernel<true>, dim3(g), dim3(256), 0, nullptr, A, R.f.as<double>(), make_const_amr(p), dx, dx * dx * dx, p->courant_factor, dt0, R.red.as<double>());
     else hipLaunchKernelGGL(lvl_courant_kernel<false>, dim3(g), dim3(256), 0, nullptr, A, (const double *)nullptr, make_const_amr(p), dx, dx * dx * dx, p->courant_factor, dt0, R.red.as<double>());
@@ -1297,23 +1266,23 @@ int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const
 int ramses_amd_amrres_hydro_flag(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double err_grad_d, double err_grad_p,
                                  double err_grad_u, double floor_d, double floor_p, double floor_u, int *cells, int *ncells) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_hydro_flag")) return rc_;
-  if (!p || !cells || !ncells) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p || !cells || !ncells) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   *ncells = 0;
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
-  if (A.nvar < 5) return failf(RAMSES_AMD_EUNSUPPORTED, "NVAR");
+  if (A.nvar < 5) return fail(RAMSES_AMD_EUNSUPPORTED, "NVAR");
   AmrRes &R = g_ar;
   if (int rc = sorted_list(R, A)) return rc;          // (the flagged cells come back sorted anyway)
   HCHK(R.okbuf.ensure(sizeof(int) * (8 * (size_t)ngrid + 1)), "hipMalloc");
   int *d_count = R.okbuf.as<int>(), *d_list = d_count + 1;
   HCHK(hipMemsetAsync(d_count, 0, sizeof(int), nullptr), "memset");
   FlagCrit F = {err_grad_d, err_grad_p, err_grad_u, floor_d, floor_p, floor_u, p->gamma, p->smallr};
-  hipLaunchKernelGGL(lvl_flag_kernel, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, A, F, d_list, d_count);
+  hipLaunchKernelGGL(lvl_flag_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, F, d_list, d_count);
   HCHK(hipGetLastError(), "hydro_flag launch");
   int n = 0;
   HCHK(hipMemcpy(&n, d_count, sizeof(int), hipMemcpyDeviceToHost), "D2H flag count");
-  if (n < 0 || (long)n > 8L * ngrid) return failf(RAMSES_AMD_EHIP, "hydro_flag: bad flag count %d", n);
+  if (n < 0 || (long)n > 8L * ngrid) return fail(RAMSES_AMD_EHIP, "hydro_flag: bad flag count %d", n);
   if (n > 0) {
     if (R.map.on) hipLaunchKernelGGL(amrlayout::cells_d2h_kernel, dim3(amrlayout::grid1(n)), dim3(256), 0, nullptr, d_list, n, R.map.iperm.as<int>(), R.ncoarse, R.ngh, R.ngridmax);
     HCHK(hipMemcpy(cells, d_list, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost), "D2H flagged cells");
@@ -1343,12 +1312,12 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   HCHK(R.okbuf.ensure(sizeof(int) * 2), "hipMalloc");
   int *cnt = R.okbuf.as<int>();
   HCHK(hipMemsetAsync(cnt, 0, sizeof(int) * 2, s), "memset");
-  hipLaunchKernelGGL(plan_clear_kernel, dim3(grid_for(L.cap * 8)), dim3(256), 0, s, A.stat, A.octpos, R.ncoarse, R.ngridmax, L.base, L.cap, P.gfather.as<int>());
-  hipLaunchKernelGGL(plan_owned_kernel, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(plan_clear_kernel, dim3(grid_for(L.cap * 8, GRID_CAP)), dim3(256), 0, s, A.stat, A.octpos, R.ncoarse, R.ngridmax, L.base, L.cap, P.gfather.as<int>());
+  hipLaunchKernelGGL(plan_owned_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, s, A);
   // (a level that holds every oct of the periodic box has no neighbour position without an oct)
   if ((long)L.n < (long)L.no * L.no * L.no)
-    hipLaunchKernelGGL(plan_ghost_kernel, dim3(grid_for((long)ngrid * 26)), dim3(256), 0, s, A, P.gfather.as<int>(), P.gslot.as<int>(), P.gcell.as<int>(), cnt, gcap, cnt + 1);
-  hipLaunchKernelGGL(plan_target_kernel, dim3(grid_for((long)ngrid * 6)), dim3(256), 0, s, A, P.corr_tgt.as<int>());
+    hipLaunchKernelGGL(plan_ghost_kernel, dim3(grid_for((long)ngrid * 26, GRID_CAP)), dim3(256), 0, s, A, P.gfather.as<int>(), P.gslot.as<int>(), P.gcell.as<int>(), cnt, gcap, cnt + 1);
+  hipLaunchKernelGGL(plan_target_kernel, dim3(grid_for((long)ngrid * 6, GRID_CAP)), dim3(256), 0, s, A, P.corr_tgt.as<int>());
   HCHK(P.events.ensure(sizeof(int) * ((size_t)ngrid * 6 + 1)), "hipMalloc");
   HCHK(hipMemsetAsync(P.events.p, 0, sizeof(int), s), "memset");
   hipLaunchKernelGGL(plan_events_kernel, dim3((unsigned)(((long)ngrid * 6 + 255) / 256)), dim3(256), 0, s, A, P.corr_tgt.as<int>(), P.events.as<int>() + 1, P.events.as<int>(), P.evt_of.as<int>());
@@ -1358,7 +1327,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   const size_t nflag = (size_t)wtx * wty * wz;
   HCHK(P.flag.ensure(nflag), "hipMalloc");
   HCHK(hipMemsetAsync(P.flag.p, 0, nflag, s), "memset");
-  hipLaunchKernelGGL(plan_work_kernel, dim3(grid_for(ngrid)), dim3(256), 0, s, A, wtx, rows, wz, P.flag.as<unsigned char>());
+  hipLaunchKernelGGL(plan_work_kernel, dim3(grid_for(ngrid, GRID_CAP)), dim3(256), 0, s, A, wtx, rows, wz, P.flag.as<unsigned char>());
   HCHK(hipGetLastError(), "plan launch");
   int hc[2] = {0, 0};
   std::vector<unsigned char> flag(nflag);
@@ -1369,7 +1338,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   HCHK(P.corr.ensure(sizeof(double) * 4 * (size_t)(R.nvar + 2) * (size_t)(P.nevent > 0 ? P.nevent : 1)), "hipMalloc flux records");
   if (P.nevent > 1) {
     // (once per plan) the events sorted by face and device oct, their index table after the sort
-    amrlayout::Buf &k1 = P.corr, &k2 = P.gfather, &v2 = P.flag;        // (free here: the records are written by the first sweep, the ghost table and the flags have done their job)
+    Buf &k1 = P.corr, &k2 = P.gfather, &v2 = P.flag;        // (free here: the records are written by the first sweep, the ghost table and the flags have done their job)
     HCHK(k1.ensure(sizeof(unsigned long long) * (size_t)P.nevent), "hipMalloc"); HCHK(k2.ensure(sizeof(unsigned long long) * (size_t)P.nevent), "hipMalloc");
     HCHK(v2.ensure(sizeof(int) * (size_t)P.nevent), "hipMalloc");
     hipLaunchKernelGGL(plan_event_keys_kernel, dim3((P.nevent + 255) / 256), dim3(256), 0, s, A, P.events.as<int>() + 1, P.nevent, k1.as<unsigned long long>(), event_order());
@@ -1382,13 +1351,13 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
     hipLaunchKernelGGL(plan_event_index_kernel, dim3((P.nevent + 255) / 256), dim3(256), 0, s, A, P.events.as<int>() + 1, P.nevent, P.evt_of.as<int>());
     HCHK(hipGetLastError(), "event index");
   }
-  if (hc[1]) return failf(RAMSES_AMD_EINVAL, "level %d: %d neighbour positions of an oct have no father cell or no tile (tree inconsistent)", ilevel, hc[1]);
-  if (hc[0] > gcap) return failf(RAMSES_AMD_EINVAL, "level %d: more ghost octs (%d) than free slots in the level's tiles (%d)", ilevel, hc[0], gcap);
+  if (hc[1]) return fail(RAMSES_AMD_EINVAL, "level %d: %d neighbour positions of an oct have no father cell or no tile (tree inconsistent)", ilevel, hc[1]);
+  if (hc[0] > gcap) return fail(RAMSES_AMD_EINVAL, "level %d: more ghost octs (%d) than free slots in the level's tiles (%d)", ilevel, hc[0], gcap);
   P.nghost = hc[0];
   if (P.nghost > 1) {
     // the ghost octs in slot order: neighbouring threads of the fill kernel then write neighbouring octs of a tile (the search
     // appended them in whatever order its waves arrived)
-    amrlayout::Buf &k2 = P.gfather, &v2 = P.flag;          // (both free from here on: the ghost table's job is done, the flags are on the host)
+    Buf &k2 = P.gfather, &v2 = P.flag;          // (both free from here on: the ghost table's job is done, the flags are on the host)
     HCHK(k2.ensure(sizeof(int) * (size_t)P.nghost), "hipMalloc"); HCHK(v2.ensure(sizeof(int) * (size_t)P.nghost), "hipMalloc");
     if (int rc = radix_sort(R.work, P.gslot.as<int>(), k2.as<int>(), P.gcell.as<int>(), v2.as<int>(), P.nghost, 32, s)) return rc;
     HCHK(hipMemcpyAsync(P.gslot.p, k2.p, sizeof(int) * (size_t)P.nghost, hipMemcpyDeviceToDevice, s), "copy");
@@ -1397,7 +1366,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   }
   if (P.nghost > 0) {
     HCHK(P.gsten.ensure(sizeof(int) * 7 * (size_t)P.nghost), "hipMalloc");
-    hipLaunchKernelGGL(plan_ghost_stencil_kernel, dim3(grid_for((long)P.nghost * 7)), dim3(256), 0, s, R.son.as<int>(), R.nbor.as<int>(), P.gcell.as<int>(), P.nghost,
+    hipLaunchKernelGGL(plan_ghost_stencil_kernel, dim3(grid_for((long)P.nghost * 7, GRID_CAP)), dim3(256), 0, s, R.son.as<int>(), R.nbor.as<int>(), P.gcell.as<int>(), P.nghost,
                        R.ncoarse, R.ngridmax, P.gsten.as<int>());
     HCHK(hipGetLastError(), "ghost stencil");
   }
@@ -1624,7 +1593,7 @@ extern "C" int ramses_amd_amrres_tiled_levels(void) { return g_ar.valid && g_ar.
 int ramses_amd_amrres_godunov(const ramses_amd_hydro_params *p, int ilevel, int ngrid, const int *igrid, double dx, double dt,
                               int nvector, int interpol_var, int interpol_type) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_godunov")) return rc_;
-  if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
@@ -1656,7 +1625,7 @@ int ramses_amd_amrres_godunov(const ramses_amd_hydro_params *p, int ilevel, int 
 int ramses_amd_amrres_load_f(int ngrid, const int *igrid, const double *f) {
   AmrRes &R = g_ar;
   LvlArgs A;
-  if (!f) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!f) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (int rc = ensure_f(R)) return rc;
   if (ngrid == 0) return 0;
@@ -1672,11 +1641,11 @@ int ramses_amd_amrres_has_gravity(void) { return g_ar.valid && g_ar.grav ? 1 : 0
 int ramses_amd_amrres_take_f_device(int ngrid, const int *igrid, const double *d_fpack) {
   AmrRes &R = g_ar;
   LvlArgs A;
-  if (!d_fpack) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!d_fpack) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (int rc = ensure_f(R)) return rc;
   if (ngrid == 0) return 0;
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, R.f.as<double>(), const_cast<double *>(d_fpack), R.cur_ig,
+  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, R.f.as<double>(), const_cast<double *>(d_fpack), R.cur_ig,
                      ngrid, 3, R.ncell, R.ncoarse, R.ngridmax);
   HCHK(hipGetLastError(), "f unpack launch");
   return 0;
@@ -1685,8 +1654,8 @@ int ramses_amd_amrres_take_f_device(int ngrid, const int *igrid, const double *d
 int ramses_amd_amrres_sync_f(int ngrid, const int *igrid, double *f) {
   AmrRes &R = g_ar;
   LvlArgs A;
-  if (!f) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (!R.grav) return failf(RAMSES_AMD_EINVAL, "sync_f: no acceleration on the device");
+  if (!f) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.grav) return fail(RAMSES_AMD_EINVAL, "sync_f: no acceleration on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   if (int rc = level_to_host(R, R.f.as<double>(), 3, R.cur_ig, ngrid, igrid, f, nullptr, "f")) return rc;
@@ -1697,9 +1666,9 @@ int ramses_amd_amrres_sync_f(int ngrid, const int *igrid, double *f) {
 int ramses_amd_amrres_compare_f(int ngrid, const int *igrid, const double *f, double *maxdiff, int64_t *ndiff) {
   AmrRes &R = g_ar;
   LvlArgs A;
-  if (!f || !maxdiff || !ndiff) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!f || !maxdiff || !ndiff) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   *maxdiff = 0.0; *ndiff = 0;
-  if (!R.grav) return failf(RAMSES_AMD_EINVAL, "compare_f: no acceleration on the device");
+  if (!R.grav) return fail(RAMSES_AMD_EINVAL, "compare_f: no acceleration on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   if (int rc = level_fetch(R, R.f.as<double>(), 3, R.cur_ig, ngrid, nullptr, "f")) return rc;
@@ -1716,7 +1685,7 @@ int ramses_amd_amrres_compare_f(int ngrid, const int *igrid, const double *f, do
 }
 // bytes of f that crossed PCIe since the start: out[0] host -> device (ramses_amd_amrres_load_f), out[1] device -> host
 int ramses_amd_amrres_f_traffic(int64_t *out2) {
-  if (!out2) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!out2) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   out2[0] = g_ar.f_up_bytes; out2[1] = g_ar.f_down_bytes;
   return 0;
 }
@@ -1724,8 +1693,8 @@ int ramses_amd_amrres_f_traffic(int64_t *out2) {
 // the oct centres xg(1:ngridmax,1:3) (after refine_fine, with the tree): what rho_fine's deposit needs beyond the tree
 int ramses_amd_amrres_xg(const double *xg) {
   AmrRes &R = g_ar;
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state");
-  if (!xg) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state");
+  if (!xg) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   HCHK(R.xg.ensure(sizeof(double) * 3 * (size_t)R.ngridmax), "hipMalloc xg");
   if (!R.map.on) {
     HCHK(hipMemcpy(R.xg.p, xg, sizeof(double) * 3 * (size_t)R.ngridmax, hipMemcpyHostToDevice), "H2D xg");
@@ -1753,14 +1722,14 @@ int ramses_amd_amrres_rho_fine(const ramses_amd_hydro_params *p, int ilevel, int
                                const int *first, const int *igrid_all, double boxlen_over_nx, double *rho, double *multipole4) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_rho_fine")) return rc_;
   AmrRes &R = g_ar;
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
-  if (!p || !first || !igrid_all || !rho || !multipole4) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (!R.xg_valid) return failf(RAMSES_AMD_EINVAL, "rho_fine: no oct centres on the device (ramses_amd_amrres_xg)");
-  if (ilevel < 2 || nlevelmax < ilevel || nvector < 1) return failf(RAMSES_AMD_EINVAL, "rho_fine: bad level range / nvector");
-  if (R.ncoarse != 1) return failf(RAMSES_AMD_EUNSUPPORTED, "rho_fine on the device covers a periodic box of one coarse cell");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
+  if (!p || !first || !igrid_all || !rho || !multipole4) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.xg_valid) return fail(RAMSES_AMD_EINVAL, "rho_fine: no oct centres on the device (ramses_amd_amrres_xg)");
+  if (ilevel < 2 || nlevelmax < ilevel || nvector < 1) return fail(RAMSES_AMD_EINVAL, "rho_fine: bad level range / nvector");
+  if (R.ncoarse != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "rho_fine on the device covers a periodic box of one coarse cell");
   const int nlev = nlevelmax - ilevel + 1;
   const int ntot = first[nlev];
-  if (first[0] != 0 || ntot < 0) return failf(RAMSES_AMD_EINVAL, "rho_fine: bad list offsets");
+  if (first[0] != 0 || ntot < 0) return fail(RAMSES_AMD_EINVAL, "rho_fine: bad list offsets");
   hipStream_t s = nullptr;
   const size_t cb = sizeof(double) * (size_t)R.ncell;
   HCHK(R.mp.ensure(4 * cb), "hipMalloc multipoles"); HCHK(R.rho.ensure(cb), "hipMalloc rho");
@@ -1771,7 +1740,7 @@ int ramses_amd_amrres_rho_fine(const ramses_amd_hydro_params *p, int ilevel, int
   if (int rc = upload_list(R, R.lists, igrid_all, ntot)) return rc;
   for (int lev = nlevelmax; lev >= ilevel; lev--) {
     const int lo = first[lev - ilevel], n = first[lev - ilevel + 1] - lo;
-    if (n < 0 || lo + n > ntot || n > R.ngridmax) return failf(RAMSES_AMD_EINVAL, "rho_fine: bad list of level %d", lev);
+    if (n < 0 || lo + n > ntot || n > R.ngridmax) return fail(RAMSES_AMD_EINVAL, "rho_fine: bad list of level %d", lev);
     if (n == 0) continue;
     const int *d_ig = R.lists.as<int>() + lo;
     HCHK(launch_amr_rho_level(R.uold.as<double>(), R.mp.as<double>(), R.rho.as<double>(), R.xg.as<double>(), R.son.as<int>(), R.nbor.as<int>(),
@@ -1802,11 +1771,11 @@ int ramses_amd_amrres_rho_mpi_multipole(const ramses_amd_hydro_params *p, int il
                                         double boxlen_over_nx) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_rho_mpi_multipole")) return rc_;
   AmrRes &R = g_ar;
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
-  if (!p || (n_all > 0 && !igrid_all)) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (!R.xg_valid) return failf(RAMSES_AMD_EINVAL, "rho_fine: no oct centres on the device (ramses_amd_amrres_xg)");
-  if (ilevel < 2 || ilevel > 30 || n_own < 0 || n_all < n_own || n_all > R.ngridmax) return failf(RAMSES_AMD_EINVAL, "rho_fine: bad level / list");
-  if (R.ncoarse != 1) return failf(RAMSES_AMD_EUNSUPPORTED, "rho_fine on the device covers a periodic box of one coarse cell");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
+  if (!p || (n_all > 0 && !igrid_all)) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.xg_valid) return fail(RAMSES_AMD_EINVAL, "rho_fine: no oct centres on the device (ramses_amd_amrres_xg)");
+  if (ilevel < 2 || ilevel > 30 || n_own < 0 || n_all < n_own || n_all > R.ngridmax) return fail(RAMSES_AMD_EINVAL, "rho_fine: bad level / list");
+  if (R.ncoarse != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "rho_fine on the device covers a periodic box of one coarse cell");
   hipStream_t s = nullptr;
   const size_t cb = sizeof(double) * (size_t)R.ncell;
   if (R.mp.cap < 4 * cb) { HCHK(R.mp.ensure(4 * cb), "hipMalloc multipoles"); HCHK(hipMemsetAsync(R.mp.p, 0, 4 * cb, s), "memset"); }
@@ -1819,8 +1788,8 @@ int ramses_amd_amrres_rho_mpi_multipole(const ramses_amd_hydro_params *p, int il
 }
 int ramses_amd_amrres_rho_mpi_deposit(int ilevel, int nvector, double boxlen_over_nx) {
   AmrRes &R = g_ar;
-  if (!R.valid || R.rl_level != ilevel) return failf(RAMSES_AMD_EINVAL, "rho_fine: level %d was not opened by ramses_amd_amrres_rho_mpi_multipole", ilevel);
-  if (nvector < 1) return failf(RAMSES_AMD_EINVAL, "rho_fine: bad nvector");
+  if (!R.valid || R.rl_level != ilevel) return fail(RAMSES_AMD_EINVAL, "rho_fine: level %d was not opened by ramses_amd_amrres_rho_mpi_multipole", ilevel);
+  if (nvector < 1) return fail(RAMSES_AMD_EINVAL, "rho_fine: bad nvector");
   unsigned hcap = 1024;
   while (hcap < 2u * (unsigned)R.rl_nown) hcap <<= 1;
   HCHK(R.hkeys.ensure(sizeof(unsigned long long) * (size_t)hcap), "hipMalloc"); HCHK(R.hvals.ensure(sizeof(int) * (size_t)hcap), "hipMalloc");
@@ -1830,8 +1799,8 @@ int ramses_amd_amrres_rho_mpi_deposit(int ilevel, int nvector, double boxlen_ove
 }
 int ramses_amd_amrres_rho_mpi_finish(int ilevel, int levelmin, int nvector, const int *igrid_all, double *rho, double *multipole4) {
   AmrRes &R = g_ar;
-  if (!R.valid || R.rl_level != ilevel) return failf(RAMSES_AMD_EINVAL, "rho_fine: level %d was not opened by ramses_amd_amrres_rho_mpi_multipole", ilevel);
-  if (!rho || !multipole4 || (R.rl_nall > 0 && !igrid_all)) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.valid || R.rl_level != ilevel) return fail(RAMSES_AMD_EINVAL, "rho_fine: level %d was not opened by ramses_amd_amrres_rho_mpi_multipole", ilevel);
+  if (!rho || !multipole4 || (R.rl_nall > 0 && !igrid_all)) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   hipStream_t s = nullptr;
   const int n_own = R.rl_nown, n = R.rl_nall;
   R.rl_level = 0;
@@ -1858,8 +1827,8 @@ int ramses_amd_amrres_rho_keep(int on) { g_ar.rho_keep = on != 0; return 0; }
 int ramses_amd_amrres_sync_rho(int ngrid, const int *igrid, double *rho) {
   AmrRes &R = g_ar;
   LvlArgs A;
-  if (!rho) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (!R.rho.p) return failf(RAMSES_AMD_EINVAL, "sync_rho: rho_fine has not run on the device");
+  if (!rho) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.rho.p) return fail(RAMSES_AMD_EINVAL, "sync_rho: rho_fine has not run on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   if (int rc = level_to_host(R, R.rho.as<double>(), 1, R.cur_ig, ngrid, igrid, rho, nullptr, "rho")) return rc;
@@ -1886,8 +1855,8 @@ __global__ __launch_bounds__(256) void rho_absmax_kernel(const double *__restric
 int ramses_amd_amrres_rho_to_brick(int ngrid, const int *igrid, const int *d_order, double *d_brick) {
   AmrRes &R = g_ar;
   LvlArgs A;
-  if (!d_order || !d_brick) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (!R.rho.p) return failf(RAMSES_AMD_EINVAL, "rho_to_brick: rho_fine has not run on the device");
+  if (!d_order || !d_brick) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.rho.p) return fail(RAMSES_AMD_EINVAL, "rho_to_brick: rho_fine has not run on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   hipLaunchKernelGGL(rho_to_brick_kernel, dim3((unsigned)(((long)ngrid * 8 + 255) / 256)), dim3(256), 0, nullptr, R.rho.as<double>(), R.cur_ig, d_order, (long)ngrid,
@@ -1898,15 +1867,15 @@ int ramses_amd_amrres_rho_to_brick(int ngrid, const int *igrid, const int *d_ord
 int ramses_amd_amrres_rho_absmax(int ngrid, const int *igrid, double *out) {
   AmrRes &R = g_ar;
   LvlArgs A;
-  if (!out) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!out) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   *out = 0.0;
-  if (!R.rho.p) return failf(RAMSES_AMD_EINVAL, "rho_absmax: rho_fine has not run on the device");
+  if (!R.rho.p) return fail(RAMSES_AMD_EINVAL, "rho_absmax: rho_fine has not run on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   HCHK(R.okbuf.ensure(sizeof(unsigned long long) * 2), "hipMalloc");
   unsigned long long *d = reinterpret_cast<unsigned long long *>(R.okbuf.p);
   HCHK(hipMemsetAsync(d, 0, sizeof(unsigned long long), nullptr), "memset");
-  hipLaunchKernelGGL(rho_absmax_kernel, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, R.rho.as<double>(), R.cur_ig, (long)ngrid, R.ncoarse, R.ngridmax, d);
+  hipLaunchKernelGGL(rho_absmax_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, R.rho.as<double>(), R.cur_ig, (long)ngrid, R.ncoarse, R.ngridmax, d);
   HCHK(hipGetLastError(), "max |rho| launch");
   unsigned long long bits = 0;
   HCHK(hipMemcpy(&bits, d, sizeof(bits), hipMemcpyDeviceToHost), "D2H");
@@ -1921,20 +1890,20 @@ int ramses_amd_amrres_sync_density(int ngrid, const int *igrid, double *uold) {
   AmrRes &R = g_ar;
   LvlArgs A;
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
-  if (uold != R.h_uold) return failf(RAMSES_AMD_EINVAL, "sync_density: not the array the state was loaded from");
+  if (uold != R.h_uold) return fail(RAMSES_AMD_EINVAL, "sync_density: not the array the state was loaded from");
   if (ngrid == 0) return 0;
   return level_to_host(R, R.uold.as<double>(), 1, R.cur_ig, ngrid, igrid, uold, nullptr, "density");
 }
 
 int ramses_amd_amrres_synchro(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dteff) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_synchro")) return rc_;
-  if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
-  if (!g_ar.grav) return failf(RAMSES_AMD_EINVAL, "synchro_hydro_fine: no acceleration on the device (ramses_amd_amrres_load_f)");
+  if (!g_ar.grav) return fail(RAMSES_AMD_EINVAL, "synchro_hydro_fine: no acceleration on the device (ramses_amd_amrres_load_f)");
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  hipLaunchKernelGGL(lvl_synchro_kernel, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dteff, p->smallr);
+  hipLaunchKernelGGL(lvl_synchro_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dteff, p->smallr);
   HCHK(hipGetLastError(), "synchro launch");
   return 0;
 }
@@ -1942,14 +1911,14 @@ int ramses_amd_amrres_synchro(const ramses_amd_hydro_params *p, int ngrid, const
 // set_uold with poisson: add_gravity_source_terms on unew, then the scalar fix and uold = unew
 int ramses_amd_amrres_set_uold_grav(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold_grav")) return rc_;
-  if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
-  if (!g_ar.grav) return failf(RAMSES_AMD_EINVAL, "set_uold: no acceleration on the device (ramses_amd_amrres_load_f)");
+  if (!g_ar.grav) return fail(RAMSES_AMD_EINVAL, "set_uold: no acceleration on the device (ramses_amd_amrres_load_f)");
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  hipLaunchKernelGGL(lvl_gravity_source_kernel, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dt, p->smallr);
-  hipLaunchKernelGGL(lvl_set_uold_kernel, dim3(grid_for((long)ngrid * 8)), dim3(256), 0, nullptr, A, p->smallr);
+  hipLaunchKernelGGL(lvl_gravity_source_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dt, p->smallr);
+  hipLaunchKernelGGL(lvl_set_uold_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, p->smallr);
   HCHK(hipGetLastError(), "set_uold launch");
   return 0;
 }
@@ -1958,7 +1927,7 @@ int ramses_amd_amrres_set_uold_grav(const ramses_amd_hydro_params *p, int ngrid,
 // ---- pressure_fix: divu / enew live on the device only (they are scratch of one hydro step)
 int ramses_amd_amrres_enable_pfix(void) {
   AmrRes &R = g_ar;
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state");
   if (R.pfix) return 0;
   HCHK(R.divu.ensure(sizeof(double) * (size_t)R.ncell), "hipMalloc divu"); HCHK(R.enew.ensure(sizeof(double) * (size_t)R.ncell), "hipMalloc enew");
   HCHK(hipMemsetAsync(R.divu.p, 0, sizeof(double) * (size_t)R.ncell, nullptr), "memset"); HCHK(hipMemsetAsync(R.enew.p, 0, sizeof(double) * (size_t)R.ncell, nullptr), "memset");
@@ -1968,13 +1937,13 @@ int ramses_amd_amrres_enable_pfix(void) {
 // set_unew with pressure_fix: unew = uold, divu = 0, enew = internal energy
 int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_unew_pfix")) return rc_;
-  if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
-  if (!g_ar.pfix) return failf(RAMSES_AMD_EINVAL, "set_unew: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
+  if (!g_ar.pfix) return fail(RAMSES_AMD_EINVAL, "set_unew: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  const dim3 g(grid_for((long)ngrid * 8)), b(256);
+  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
   hipLaunchKernelGGL(lvl_copy_kernel, g, b, 0, nullptr, A, A.unew, A.uold);
   hipLaunchKernelGGL(lvl_pfix_init_kernel, g, b, 0, nullptr, A, g_ar.divu.as<double>(), g_ar.enew.as<double>(), p->smallr);
   HCHK(hipGetLastError(), "set_unew launch");
@@ -1984,14 +1953,14 @@ int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid,
 int ramses_amd_amrres_set_uold_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt, double dx_loc, double beta_fix,
                                     double hexp) {
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold_pfix")) return rc_;
-  if (!p) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   AmrRes &R = g_ar;
-  if (!R.pfix) return failf(RAMSES_AMD_EINVAL, "set_uold: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
+  if (!R.pfix) return fail(RAMSES_AMD_EINVAL, "set_uold: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  const dim3 g(grid_for((long)ngrid * 8)), b(256);
+  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
   if (R.grav) hipLaunchKernelGGL(lvl_gravity_source_kernel, g, b, 0, nullptr, A, R.f.as<double>(), dt, p->smallr);
   hipLaunchKernelGGL(lvl_pdv_kernel, g, b, 0, nullptr, A, R.enew.as<double>(), dx_loc, dt, p->gamma, p->smallr);
   hipLaunchKernelGGL(lvl_set_uold_kernel, g, b, 0, nullptr, A, p->smallr);
@@ -2002,9 +1971,9 @@ int ramses_amd_amrres_set_uold_pfix(const ramses_amd_hydro_params *p, int ngrid,
 // divu / enew of the listed octs' cells into the host vectors (1:ncell): what a test or a user debugging a pressure_fix run reads
 int ramses_amd_amrres_sync_pfix(int ngrid, const int *igrid, double *divu, double *enew) {
   AmrRes &R = g_ar;
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "sync_pfix: no resident AMR state");
-  if (!R.pfix) return failf(RAMSES_AMD_EINVAL, "sync_pfix: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
-  if (!divu || !enew) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "sync_pfix: no resident AMR state");
+  if (!R.pfix) return fail(RAMSES_AMD_EINVAL, "sync_pfix: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
+  if (!divu || !enew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
@@ -2036,19 +2005,19 @@ int ramses_amd_amrres_comm_epoch(int ilevel) {
 // the communicators of a level after build_comm: em_n / rc_n [ncpu] octs per peer, em_ig / rc_ig the concatenated lists
 int ramses_amd_amrres_comm_set(int ilevel, int epoch, int ncpu, const int *em_n, const int *em_ig, const int *rc_n, const int *rc_ig) {
   AmrRes &R = g_ar;
-  if (ilevel < 1 || ilevel > 64 || ncpu < 1 || !em_n || !rc_n || epoch < 0) return failf(RAMSES_AMD_EINVAL, "comm_set: bad argument");
+  if (ilevel < 1 || ilevel > 64 || ncpu < 1 || !em_n || !rc_n || epoch < 0) return fail(RAMSES_AMD_EINVAL, "comm_set: bad argument");
   if ((size_t)ilevel >= R.comm.size()) R.comm.resize((size_t)ilevel + 1);
   CommLevel &L = R.comm[ilevel];
   L.epoch = -1;
   L.ncpu = ncpu;
   L.em_first.assign((size_t)ncpu + 1, 0); L.rc_first.assign((size_t)ncpu + 1, 0);
   for (int c = 0; c < ncpu; c++) {
-    if (em_n[c] < 0 || rc_n[c] < 0) return failf(RAMSES_AMD_EINVAL, "comm_set: negative list length");
+    if (em_n[c] < 0 || rc_n[c] < 0) return fail(RAMSES_AMD_EINVAL, "comm_set: negative list length");
     L.em_first[c + 1] = L.em_first[c] + em_n[c];
     L.rc_first[c + 1] = L.rc_first[c] + rc_n[c];
   }
   const int nem = L.em_first[ncpu], nrc = L.rc_first[ncpu];
-  if ((nem > 0 && !em_ig) || (nrc > 0 && !rc_ig)) return failf(RAMSES_AMD_EINVAL, "comm_set: NULL list");
+  if ((nem > 0 && !em_ig) || (nrc > 0 && !rc_ig)) return fail(RAMSES_AMD_EINVAL, "comm_set: NULL list");
   HCHK(L.em_ig.ensure(sizeof(int) * (size_t)(nem > 0 ? nem : 1)), "hipMalloc"); HCHK(L.rc_ig.ensure(sizeof(int) * (size_t)(nrc > 0 ? nrc : 1)), "hipMalloc");
   HCHK(L.em_raw.ensure(sizeof(int) * (size_t)(nem > 0 ? nem : 1)), "hipMalloc"); HCHK(L.rc_raw.ensure(sizeof(int) * (size_t)(nrc > 0 ? nrc : 1)), "hipMalloc");
   if (nem > 0) HCHK(hipMemcpy(L.em_raw.p, em_ig, sizeof(int) * (size_t)nem, hipMemcpyHostToDevice), "H2D emission list");
@@ -2060,9 +2029,9 @@ int ramses_amd_amrres_comm_set(int ilevel, int epoch, int ncpu, const int *em_n,
 
 namespace {
 int comm_of(AmrRes &R, int ilevel, CommLevel *&L) {
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
   if (ilevel < 1 || (size_t)ilevel >= R.comm.size() || R.comm[ilevel].epoch < 0)
-    return failf(RAMSES_AMD_EINVAL, "level %d: no communicators on the device (ramses_amd_amrres_comm_set)", ilevel);
+    return fail(RAMSES_AMD_EINVAL, "level %d: no communicators on the device (ramses_amd_amrres_comm_set)", ilevel);
   L = &R.comm[ilevel];
   if (L->serial != R.map.serial) {
     // the lists in the numbers of the layout in force (a regrid of OTHER levels renumbers nothing here, but costs nothing either)
@@ -2090,18 +2059,18 @@ int halo_spec(AmrRes &R, int dir, HaloSpec &S) {
     case 0: S = {R.uold.as<double>(), R.nvar, false}; return 0;
     case 1: S = {R.unew.as<double>(), R.nvar, true}; return 0;
     case 2: case 3:
-      if (!R.pfix) return failf(RAMSES_AMD_EINVAL, "halo on enew/divu: pressure_fix is not enabled");
+      if (!R.pfix) return fail(RAMSES_AMD_EINVAL, "halo on enew/divu: pressure_fix is not enabled");
       S = {dir == 2 ? R.enew.as<double>() : R.divu.as<double>(), 1, true}; return 0;
     case 7:
-      if (!R.grav) return failf(RAMSES_AMD_EINVAL, "halo on f: no acceleration on the device");
+      if (!R.grav) return fail(RAMSES_AMD_EINVAL, "halo on f: no acceleration on the device");
       S = {R.f.as<double>(), 3, false}; return 0;
     case 4: case 5: case 6:
-      if (!R.rho.p || !R.mp.p) return failf(RAMSES_AMD_EINVAL, "halo on rho / the multipoles: rho_fine has not run on the device");
+      if (!R.rho.p || !R.mp.p) return fail(RAMSES_AMD_EINVAL, "halo on rho / the multipoles: rho_fine has not run on the device");
       if (dir == 6) S = {R.mp.as<double>(), 4, false};
       else S = {R.rho.as<double>(), 1, dir == 4};
       return 0;
   }
-  return failf(RAMSES_AMD_EINVAL, "halo: bad direction %d", dir);
+  return fail(RAMSES_AMD_EINVAL, "halo: bad direction %d", dir);
 }
 // gather every peer's message into sendbuf; fills the [ncpu+1] offset tables (in doubles)
 int halo_pack(AmrRes &R, CommLevel &L, const HaloSpec &S) {
@@ -2115,7 +2084,7 @@ int halo_pack(AmrRes &R, CommLevel &L, const HaloSpec &S) {
   for (int c = 0; c < L.ncpu; c++) {
     const int n = sf[c + 1] - sf[c];
     if (n <= 0) continue;
-    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8)), dim3(256), 0, nullptr, S.vec, R.sendbuf.as<double>() + per * sf[c],
+    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.sendbuf.as<double>() + per * sf[c],
                        sig + sf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
   }
   HCHK(hipGetLastError(), "halo pack launch");
@@ -2129,9 +2098,9 @@ int halo_unpack(AmrRes &R, CommLevel &L, const HaloSpec &S) {
   for (int c = 0; c < L.ncpu; c++) {
     const int n = rf[c + 1] - rf[c];
     if (n <= 0) continue;
-    if (S.reverse) hipLaunchKernelGGL(lvl_acc_comp_kernel, dim3(grid_for((long)n * 8)), dim3(256), 0, nullptr, S.vec, R.recvbuf.as<double>() + per * rf[c],
+    if (S.reverse) hipLaunchKernelGGL(lvl_acc_comp_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.recvbuf.as<double>() + per * rf[c],
                                       rig + rf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
-    else hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8)), dim3(256), 0, nullptr, S.vec, R.recvbuf.as<double>() + per * rf[c],
+    else hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.recvbuf.as<double>() + per * rf[c],
                             rig + rf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
   }
   HCHK(hipGetLastError(), "halo unpack launch");
@@ -2147,22 +2116,22 @@ int halo_unpack(AmrRes &R, CommLevel &L, const HaloSpec &S) {
 int ramses_amd_amrres_boundary_hydro(int nregion, const int *btype, const int *ngrid, const int *igrid, int no_inflow, double smallr,
                                      int nvector, const double *imposed) {
   AmrRes &R = g_ar;
-  if (!R.valid) return failf(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
-  if (nregion < 0 || (nregion > 0 && (!btype || !ngrid))) return failf(RAMSES_AMD_EINVAL, "bad boundary description");
-  if (R.nvar > 8) return failf(RAMSES_AMD_EUNSUPPORTED, "make_boundary_hydro on the device: nvar <= 8 (got %d)", R.nvar);
-  if (nvector < 1) return failf(RAMSES_AMD_EINVAL, "nvector must be >= 1");
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
+  if (nregion < 0 || (nregion > 0 && (!btype || !ngrid))) return fail(RAMSES_AMD_EINVAL, "bad boundary description");
+  if (R.nvar > 8) return fail(RAMSES_AMD_EUNSUPPORTED, "make_boundary_hydro on the device: nvar <= 8 (got %d)", R.nvar);
+  if (nvector < 1) return fail(RAMSES_AMD_EINVAL, "nvector must be >= 1");
   long ntot = 0;
   int nmax = 0;
   for (int r = 0; r < nregion; r++) {
     const int k = btype[r] / 10, d = btype[r] % 10;
-    if (k < 0 || k > 2 || d < 1 || d > 6) return failf(RAMSES_AMD_EINVAL, "make_boundary_hydro: bad boundary_type %d", btype[r]);
-    if (k == 2 && !imposed) return failf(RAMSES_AMD_EINVAL, "make_boundary_hydro: an imposed boundary needs its states (boundana's output)");
-    if (ngrid[r] < 0) return failf(RAMSES_AMD_EINVAL, "bad boundary oct count");
+    if (k < 0 || k > 2 || d < 1 || d > 6) return fail(RAMSES_AMD_EINVAL, "make_boundary_hydro: bad boundary_type %d", btype[r]);
+    if (k == 2 && !imposed) return fail(RAMSES_AMD_EINVAL, "make_boundary_hydro: an imposed boundary needs its states (boundana's output)");
+    if (ngrid[r] < 0) return fail(RAMSES_AMD_EINVAL, "bad boundary oct count");
     ntot += ngrid[r];
     if (ngrid[r] > nmax) nmax = ngrid[r];
   }
   if (ntot == 0) return 0;
-  if (!igrid) return failf(RAMSES_AMD_EINVAL, "NULL oct list");
+  if (!igrid) return fail(RAMSES_AMD_EINVAL, "NULL oct list");
   HCHK(R.bnd_list.ensure(sizeof(int) * (size_t)ntot), "hipMalloc boundary octs");
   HCHK(R.bnd_tmp.ensure(sizeof(double) * (size_t)nmax * 8 * (size_t)R.nvar), "hipMalloc boundary states");
   if (!R.bnd_pos.p || R.bnd_pos.cap < sizeof(int) * (size_t)R.ngridmax) R.bnd_pos_clean = false;
@@ -2171,7 +2140,7 @@ int ramses_amd_amrres_boundary_hydro(int nregion, const int *btype, const int *n
   // (the marks of a region are set and cleared around its kernels: an error return in between leaves marks behind, so the
   //  table counts as clean again only after the last region's clear has been queued)
   R.bnd_pos_clean = false;
-  if (R.nvar < 5) return failf(RAMSES_AMD_EUNSUPPORTED, "make_boundary_hydro on the device: the 3-D hydro layout (rho, rho u, rho v, rho w, E first)");
+  if (R.nvar < 5) return fail(RAMSES_AMD_EUNSUPPORTED, "make_boundary_hydro on the device: the 3-D hydro layout (rho, rho u, rho v, rho w, E first)");
   if (int rc = upload_list(R, R.bnd_list, igrid, (int)ntot)) return rc;
   BndArgs A;
   A.uold = R.uold.as<double>(); A.tmp = R.bnd_tmp.as<double>();
@@ -2187,12 +2156,12 @@ int ramses_amd_amrres_boundary_hydro(int nregion, const int *btype, const int *n
         const size_t cnt = (size_t)n * 8 * (size_t)R.nvar;
         HCHK(hipMemcpyAsync(A.tmp, imposed + imp_off, sizeof(double) * cnt, hipMemcpyHostToDevice, nullptr), "H2D imposed states");
         imp_off += (long)cnt;
-        hipLaunchKernelGGL(bnd_store_kernel, dim3(grid_for((long)n * 8)), dim3(256), 0, nullptr, A);
+        hipLaunchKernelGGL(bnd_store_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, A);
       } else {
-        hipLaunchKernelGGL(bnd_mark_kernel, dim3(grid_for(n)), dim3(256), 0, nullptr, A, 0);
-        hipLaunchKernelGGL(bnd_compute_kernel, dim3(grid_for((long)n * 8)), dim3(256), 0, nullptr, A);
-        hipLaunchKernelGGL(bnd_store_kernel, dim3(grid_for((long)n * 8)), dim3(256), 0, nullptr, A);
-        hipLaunchKernelGGL(bnd_mark_kernel, dim3(grid_for(n)), dim3(256), 0, nullptr, A, 1);
+        hipLaunchKernelGGL(bnd_mark_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, nullptr, A, 0);
+        hipLaunchKernelGGL(bnd_compute_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, A);
+        hipLaunchKernelGGL(bnd_store_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, A);
+        hipLaunchKernelGGL(bnd_mark_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, nullptr, A, 1);
       }
     }
     off += n;
@@ -2211,7 +2180,7 @@ int ramses_amd_amrres_zero_unew_virtual(int ilevel) {
   if (int rc = comm_of(R, ilevel, L)) return rc;
   const int n = L->rc_first[L->ncpu];
   if (n <= 0) return 0;
-  const dim3 g(grid_for((long)n * 8)), b(256);
+  const dim3 g(grid_for((long)n * 8, GRID_CAP)), b(256);
   hipLaunchKernelGGL(lvl_zero_comp_kernel, g, b, 0, nullptr, R.unew.as<double>(), L->rc_ig.as<int>(), n, R.nvar, R.ncell, R.ncoarse, R.ngridmax);
   if (R.pfix) {
     hipLaunchKernelGGL(lvl_zero_comp_kernel, g, b, 0, nullptr, R.divu.as<double>(), L->rc_ig.as<int>(), n, 1, R.ncell, R.ncoarse, R.ngridmax);
@@ -2253,9 +2222,9 @@ int ramses_amd_amrres_halo_stage_out(int ilevel, int dir, int ncpu, int64_t *h_s
   AmrRes &R = g_ar;
   CommLevel *L;
   HaloSpec S;
-  if (!h_send_addr || !h_recv_addr || !send_off || !recv_off) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!h_send_addr || !h_recv_addr || !send_off || !recv_off) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = comm_of(R, ilevel, L)) return rc;
-  if (ncpu != L->ncpu) return failf(RAMSES_AMD_EINVAL, "ncpu mismatch");
+  if (ncpu != L->ncpu) return fail(RAMSES_AMD_EINVAL, "ncpu mismatch");
   if (int rc = halo_spec(R, dir, S)) return rc;
   if (int rc = halo_pack(R, *L, S)) return rc;
   const size_t ns = (size_t)R.f_send_off[ncpu], nr = (size_t)R.f_recv_off[ncpu];
@@ -2274,7 +2243,7 @@ int ramses_amd_amrres_halo_stage_in(int ilevel, int dir) {
   if (int rc = comm_of(R, ilevel, L)) return rc;
   if (int rc = halo_spec(R, dir, S)) return rc;
   if (R.halo_level != ilevel || R.halo_dir != dir || R.f_recv_off.size() != (size_t)L->ncpu + 1)
-    return failf(RAMSES_AMD_EINVAL, "halo_stage_in(level %d, dir %d) does not close the exchange halo_stage_out opened (level %d, dir %d)",
+    return fail(RAMSES_AMD_EINVAL, "halo_stage_in(level %d, dir %d) does not close the exchange halo_stage_out opened (level %d, dir %d)",
                  ilevel, dir, R.halo_level, R.halo_dir);
   R.halo_level = 0; R.halo_dir = -1;
   const size_t nr = (size_t)R.f_recv_off[L->ncpu];

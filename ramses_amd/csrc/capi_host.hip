@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -83,7 +82,6 @@ int ramses_amd_godunov_fine_host(const ramses_amd_hydro_params *p, int ilevel, i
   if (int rc = resident_release("godunov_fine (staged brick sweep)")) return rc;   // the bricks are reused
   hipStream_t s = nullptr;
   HostCtx &H = g_host;
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(e_, what); } while (0)
   HCHK(H.uold.ensure(sizeof(double) * nvar * ncell), "hipMalloc uold");
   HCHK(H.unew.ensure(sizeof(double) * nvar * ncell), "hipMalloc unew");
   HCHK(H.igrid.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
@@ -129,7 +127,6 @@ int ramses_amd_godunov_fine_host(const ramses_amd_hydro_params *p, int ilevel, i
   HCHK(launch_oct_copy(A, false, s), "scatter launch");
   HCHK(hipMemcpyAsync(unew, H.unew.p, sizeof(double) * nvar * ncell, hipMemcpyDeviceToHost, s), "D2H unew");
   HCHK(hipStreamSynchronize(s), "sync");
-#undef HCHK
   return 0;
 }
 
@@ -223,7 +220,6 @@ int ramses_amd_godunov_fine_amr_host(const ramses_amd_hydro_params *p, int ileve
   hipStream_t s = nullptr;
   HostCtx &H = g_host;
   static DevBuf dson, dnbor, dfather, dwork, ddivu, denew;
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(e_, what); } while (0)
   const int nvar = p->nvar;
   HCHK(H.uold.ensure(sizeof(double) * nvar * ncell), "hipMalloc uold");
   HCHK(H.unew.ensure(sizeof(double) * nvar * ncell), "hipMalloc unew");
@@ -266,7 +262,6 @@ int ramses_amd_godunov_fine_amr_host(const ramses_amd_hydro_params *p, int ileve
     HCHK(hipMemcpyAsync(enew, denew.p, sizeof(double) * ncell, hipMemcpyDeviceToHost, s), "D2H enew");
   }
   HCHK(hipStreamSynchronize(s), "sync");
-#undef HCHK
   if (bad) return fail(RAMSES_AMD_EINVAL, "level %d: %d of the 3^3 father cells of an oct do not exist (tree inconsistent)", ilevel, bad);
   return 0;
 }
@@ -400,7 +395,6 @@ int ramses_amd_godunov_fine_lowdim_f90(const ramses_amd_hydro_params *p, int ile
   if (int rc = resident_release("godunov_fine (NDIM<3 brick sweep)")) return rc;
   hipStream_t s = nullptr;
   HostCtx &H = g_host;
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(e_, what); } while (0)
   const size_t bytes = sizeof(double) * 5 * (size_t)b.pitch_var;
   HCHK(H.bold.ensure(bytes), "hipMalloc brick"); HCHK(H.bnew.ensure(bytes), "hipMalloc brick");
   HCHK(hipMemcpyAsync(H.bold.p, hb.data(), bytes, hipMemcpyHostToDevice, s), "H2D brick");
@@ -413,7 +407,6 @@ int ramses_amd_godunov_fine_lowdim_f90(const ramses_amd_hydro_params *p, int ile
   if (int rc = ramses_amd_godunov_brick(&q, &b, H.bold.as<double>(), nullptr, H.bnew.as<double>(), dx, dt, s)) return rc;
   HCHK(hipMemcpyAsync(hb.data(), H.bnew.p, bytes, hipMemcpyDeviceToHost, s), "D2H brick");
   HCHK(hipStreamSynchronize(s), "sync");
-#undef HCHK
   // unew(active cells) = uold + flux differences, as after the reference's set_unew + godunov_fine
   for (int i = 0; i < ngrid; i++) {
     const int g = igrid[i];
@@ -460,7 +453,6 @@ int ramses_amd_multigrid_fine_f90(int ilevel, int ngrid, const int *igrid, const
   if (H.res_valid && !(H.res_level == ilevel && H.res_ngrid == ngrid && H.res_ncell == ncell))
     if (int rc = resident_release("multigrid_fine")) return rc;
   static DevBuf rhovec, phivec, brho, bphi, bf1, bf2, work;
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(e_, what); } while (0)
   const int64_t nwork = ramses_amd_mg_workspace_doubles(ilevel);
   HCHK(rhovec.ensure(sizeof(double) * ncell), "hipMalloc");
   HCHK(phivec.ensure(sizeof(double) * ncell), "hipMalloc");
@@ -498,7 +490,6 @@ int ramses_amd_multigrid_fine_f90(int ilevel, int ngrid, const int *igrid, const
   HCHK(launch_oct_copy(A, false, s), "scatter launch");
   HCHK(hipMemcpyAsync(phi, phivec.p, sizeof(double) * ncell, hipMemcpyDeviceToHost, s), "D2H phi");
   HCHK(hipStreamSynchronize(s), "sync");
-#undef HCHK
   return 0;
 }
 
@@ -519,7 +510,6 @@ int ramses_amd_force_fine_f90(int ilevel, int ngrid, const int *igrid, const dou
   hipStream_t s = nullptr;
   HostCtx &H = g_host;
   static DevBuf phivec, fvec3, bphi, bf;
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(e_, what); } while (0)
   HCHK(phivec.ensure(sizeof(double) * ncell), "hipMalloc");
   HCHK(fvec3.ensure(sizeof(double) * 3 * ncell), "hipMalloc");
   HCHK(bphi.ensure(sizeof(double) * N), "hipMalloc");
@@ -586,7 +576,6 @@ int ramses_amd_force_fine_f90(int ilevel, int ngrid, const int *igrid, const dou
     HCHK(hipMemcpyAsync(diag2, scratch + FORCE_DIAG_SCRATCH, sizeof(double) * 2, hipMemcpyDeviceToHost, s), "D2H diag");
   }
   HCHK(hipStreamSynchronize(s), "sync");
-#undef HCHK
   return 0;
 }
 
@@ -599,7 +588,6 @@ int ramses_amd_force_fine_f90(int ilevel, int ngrid, const int *igrid, const dou
 // ramses_amd_resident()); the host array is refreshed on demand
 // (ramses_amd_resident_sync_host_f90, called by the backup_hydro shim).
 // ---------------------------------------------------------------------------
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(e_, what); } while (0)
 static int resident_ensure(const ramses_amd_hydro_params *p, int ilevel, int ngrid, const int *igrid,
                            const double *xg, int64_t ngridmax, int64_t ncoarse, int nx_loc,
                            const double *uold) {
@@ -1003,7 +991,6 @@ int ramses_amd_resident_invalidate(void) {
   H.res_valid = false;
   return 0;
 }
-#undef HCHK
 
 }  // extern "C"
 

@@ -18,7 +18,6 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,22 +25,11 @@
 
 #include "../../include/ramses_amd.h"
 #include "halo_plan.hpp"
+#include "host_util.hpp"
 #include "misc_args.hpp"
 #include "pack_args.hpp"
 
 using namespace ramses_amd;
-
-extern "C" int ramses_amd_set_error(int code, const char *msg);   // capi.hip: fills ramses_amd_last_error()
-
-static int failf(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return ramses_amd_set_error(code, buf);
-}
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failf(RAMSES_AMD_EHIP, "%s: %s", what, hipGetErrorString(e_)); } while (0)
 
 // ---------------------------------------------------------------------------
 // RCCL, loaded on demand
@@ -72,10 +60,10 @@ int rccl_load() {
     R.h = dlopen(n, RTLD_NOW | RTLD_LOCAL);
     if (R.h) break;
   }
-  if (!R.h) return failf(RAMSES_AMD_EUNSUPPORTED, "librccl.so cannot be loaded: %s", dlerror());
+  if (!R.h) return fail(RAMSES_AMD_EUNSUPPORTED, "librccl.so cannot be loaded: %s", dlerror());
 #define SYM(field, name) \
   *reinterpret_cast<void **>(&R.field) = dlsym(R.h, name); \
-  if (!R.field) return failf(RAMSES_AMD_EUNSUPPORTED, "librccl.so lacks %s", name)
+  if (!R.field) return fail(RAMSES_AMD_EUNSUPPORTED, "librccl.so lacks %s", name)
   SYM(GetUniqueId, "ncclGetUniqueId");
   SYM(CommInitRank, "ncclCommInitRank");
   SYM(CommDestroy, "ncclCommDestroy");
@@ -89,9 +77,9 @@ int rccl_load() {
 #undef SYM
   return 0;
 }
-#define NCHK(call, what) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) return failf(RAMSES_AMD_EHIP, "%s: %s", what, g_rccl.GetErrorString(r_)); } while (0)
+#define NCHK(call, what) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) return fail(RAMSES_AMD_EHIP, "%s: %s", what, g_rccl.GetErrorString(r_)); } while (0)
 // inside ncclGroupStart ... ncclGroupEnd: close the group before reporting, so that the next exchange does not nest into it
-#define NCHK_GROUP(call, what) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) { g_rccl.GroupEnd(); return failf(RAMSES_AMD_EHIP, "%s: %s", what, g_rccl.GetErrorString(r_)); } } while (0)
+#define NCHK_GROUP(call, what) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) { g_rccl.GroupEnd(); return fail(RAMSES_AMD_EHIP, "%s: %s", what, g_rccl.GetErrorString(r_)); } } while (0)
 }  // namespace
 
 extern "C" {
@@ -100,7 +88,7 @@ extern "C" {
 // (hash of the host name and the PCI bus id of the current device): RCCL refuses communicators with two
 // ranks on one device, so the shim checks before it tries.
 int ramses_amd_device_uid(int64_t *uid) {
-  if (!uid) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!uid) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   int dev = 0;
   HCHK(hipGetDevice(&dev), "hipGetDevice");
   char bus[64] = "";
@@ -126,7 +114,7 @@ int ramses_amd_rccl_probe(void) {
 }
 
 int ramses_amd_rccl_unique_id(char *id128) {
-  if (!id128) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!id128) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = rccl_load()) return rc;
   ncclUniqueId id;
   NCHK(g_rccl.GetUniqueId(&id), "ncclGetUniqueId");
@@ -136,7 +124,7 @@ int ramses_amd_rccl_unique_id(char *id128) {
 }
 
 int ramses_amd_rccl_init(const char *id128, int nranks, int rank) {
-  if (!id128 || nranks < 1 || rank < 0 || rank >= nranks) return failf(RAMSES_AMD_EINVAL, "bad argument");
+  if (!id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(RAMSES_AMD_EINVAL, "bad argument");
   if (int rc = rccl_load()) return rc;
   Rccl &R = g_rccl;
   if (R.comm) { R.CommDestroy(R.comm); R.comm = nullptr; }
@@ -162,15 +150,15 @@ int ramses_amd_rccl_exchange(int npeer, const int *peer, const double *d_send, c
                              const int64_t *send_cnt, double *d_recv, const int64_t *recv_off,
                              const int64_t *recv_cnt, void *stream) {
   Rccl &R = g_rccl;
-  if (!R.comm) return failf(RAMSES_AMD_EINVAL, "RCCL communicator not initialised (ramses_amd_rccl_init)");
+  if (!R.comm) return fail(RAMSES_AMD_EINVAL, "RCCL communicator not initialised (ramses_amd_rccl_init)");
   if (npeer < 0 || (npeer > 0 && (!peer || !send_off || !send_cnt || !recv_off || !recv_cnt)))
-    return failf(RAMSES_AMD_EINVAL, "bad argument");
+    return fail(RAMSES_AMD_EINVAL, "bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   NCHK(R.GroupStart(), "ncclGroupStart");
   for (int i = 0; i < npeer; i++) {
     // peer[i] == own rank is legal: RCCL matches a send to self with the receive from self of the same group
-    if (peer[i] < 0 || peer[i] >= R.nranks) { R.GroupEnd(); return failf(RAMSES_AMD_EINVAL, "bad peer rank %d", peer[i]); }
-    if (peer[i] == R.rank && send_cnt[i] != recv_cnt[i]) { R.GroupEnd(); return failf(RAMSES_AMD_EINVAL, "message to self: %lld doubles sent, %lld expected", (long long)send_cnt[i], (long long)recv_cnt[i]); }
+    if (peer[i] < 0 || peer[i] >= R.nranks) { R.GroupEnd(); return fail(RAMSES_AMD_EINVAL, "bad peer rank %d", peer[i]); }
+    if (peer[i] == R.rank && send_cnt[i] != recv_cnt[i]) { R.GroupEnd(); return fail(RAMSES_AMD_EINVAL, "message to self: %lld doubles sent, %lld expected", (long long)send_cnt[i], (long long)recv_cnt[i]); }
     if (recv_cnt[i] > 0) NCHK_GROUP(R.Recv(d_recv + recv_off[i], (size_t)recv_cnt[i], ncclDouble, peer[i], R.comm, s), "ncclRecv");
     if (send_cnt[i] > 0) NCHK_GROUP(R.Send(d_send + send_off[i], (size_t)send_cnt[i], ncclDouble, peer[i], R.comm, s), "ncclSend");
   }
@@ -183,17 +171,17 @@ int ramses_amd_rccl_exchange(int npeer, const int *peer, const double *d_send, c
 int ramses_amd_rccl_sendrecv(int nsend, const double *const *send_ptr, const int64_t *send_cnt, const int *send_peer,
                              int nrecv, double *const *recv_ptr, const int64_t *recv_cnt, const int *recv_peer, void *stream) {
   Rccl &R = g_rccl;
-  if (!R.comm) return failf(RAMSES_AMD_EINVAL, "RCCL communicator not initialised (ramses_amd_rccl_init)");
+  if (!R.comm) return fail(RAMSES_AMD_EINVAL, "RCCL communicator not initialised (ramses_amd_rccl_init)");
   if (nsend < 0 || nrecv < 0 || (nsend > 0 && (!send_ptr || !send_cnt || !send_peer)) || (nrecv > 0 && (!recv_ptr || !recv_cnt || !recv_peer)))
-    return failf(RAMSES_AMD_EINVAL, "bad argument");
+    return fail(RAMSES_AMD_EINVAL, "bad argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   NCHK(R.GroupStart(), "ncclGroupStart");
   for (int i = 0; i < nrecv; i++) {
-    if (recv_peer[i] < 0 || recv_peer[i] >= R.nranks) { R.GroupEnd(); return failf(RAMSES_AMD_EINVAL, "bad peer rank %d", recv_peer[i]); }
+    if (recv_peer[i] < 0 || recv_peer[i] >= R.nranks) { R.GroupEnd(); return fail(RAMSES_AMD_EINVAL, "bad peer rank %d", recv_peer[i]); }
     NCHK_GROUP(R.Recv(recv_ptr[i], (size_t)recv_cnt[i], ncclDouble, recv_peer[i], R.comm, s), "ncclRecv");
   }
   for (int i = 0; i < nsend; i++) {
-    if (send_peer[i] < 0 || send_peer[i] >= R.nranks) { R.GroupEnd(); return failf(RAMSES_AMD_EINVAL, "bad peer rank %d", send_peer[i]); }
+    if (send_peer[i] < 0 || send_peer[i] >= R.nranks) { R.GroupEnd(); return fail(RAMSES_AMD_EINVAL, "bad peer rank %d", send_peer[i]); }
     NCHK_GROUP(R.Send(send_ptr[i], (size_t)send_cnt[i], ncclDouble, send_peer[i], R.comm, s), "ncclSend");
   }
   NCHK(R.GroupEnd(), "ncclGroupEnd");
@@ -204,8 +192,8 @@ int ramses_amd_rccl_sendrecv(int nsend, const double *const *send_ptr, const int
 // courant_fine hydro/courant_fine.f90:133-140, of the multigrid norms and of the CG dot products)
 int ramses_amd_rccl_allreduce(double *d_buf, int n, int op, void *stream) {
   Rccl &R = g_rccl;
-  if (!R.comm) return failf(RAMSES_AMD_EINVAL, "RCCL communicator not initialised (ramses_amd_rccl_init)");
-  if (!d_buf || n < 1 || op < 0 || op > 2) return failf(RAMSES_AMD_EINVAL, "bad argument");
+  if (!R.comm) return fail(RAMSES_AMD_EINVAL, "RCCL communicator not initialised (ramses_amd_rccl_init)");
+  if (!d_buf || n < 1 || op < 0 || op > 2) return fail(RAMSES_AMD_EINVAL, "bad argument");
   const ncclRedOp_t o = op == 0 ? ncclSum : (op == 1 ? ncclMin : ncclMax);
   NCHK(R.AllReduce(d_buf, d_buf, (size_t)n, ncclDouble, o, R.comm, reinterpret_cast<hipStream_t>(stream)), "ncclAllReduce");
   return 0;
@@ -214,8 +202,8 @@ int ramses_amd_rccl_allreduce(double *d_buf, int n, int op, void *stream) {
 // d_recv[r*count .. (r+1)*count) = d_send of rank r (the replicated coarse levels of the distributed multigrid)
 int ramses_amd_rccl_allgather(const double *d_send, int64_t count, double *d_recv, void *stream) {
   Rccl &R = g_rccl;
-  if (!R.comm) return failf(RAMSES_AMD_EINVAL, "RCCL communicator not initialised (ramses_amd_rccl_init)");
-  if (!d_send || !d_recv || count < 1) return failf(RAMSES_AMD_EINVAL, "bad argument");
+  if (!R.comm) return fail(RAMSES_AMD_EINVAL, "RCCL communicator not initialised (ramses_amd_rccl_init)");
+  if (!d_send || !d_recv || count < 1) return fail(RAMSES_AMD_EINVAL, "bad argument");
   NCHK(R.AllGather(d_send, d_recv, (size_t)count, ncclDouble, R.comm, reinterpret_cast<hipStream_t>(stream)), "ncclAllGather");
   return 0;
 }
@@ -270,33 +258,6 @@ hipError_t launch_oct_list(const OctListArgs &A, int mode, hipStream_t s) {
   return hipGetLastError();
 }
 
-struct Buf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) { hipFree(p); p = nullptr; cap = 0; }
-    if (bytes == 0) bytes = 8;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
-struct PinBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) { hipHostFree(p); p = nullptr; cap = 0; }
-    if (bytes == 0) bytes = 8;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
-
 struct MpiRes {
   bool valid = false, host_stale = false, new_ready = false;
   int level = 0, ngrid = 0, nvar = 0, ncpu = 0, myid = 0;
@@ -305,7 +266,7 @@ struct MpiRes {
   const double *h_uold = nullptr, *h_unew = nullptr;
   HaloPlan plan;
   ramses_amd_brick brick;
-  Buf bold, bnew, vec, load_igrid, load_org, em_org, rc_src, rc_org, sendbuf, recvbuf, red;
+  DevBuf bold, bnew, vec, load_igrid, load_org, em_org, rc_src, rc_org, sendbuf, recvbuf, red;
   PinBuf h_send, h_recv;
   std::vector<int> peers;                       // ranks (0-based) with a non-empty list
   std::vector<int64_t> send_off, send_cnt, recv_off, recv_cnt;   // per entry of peers, in doubles
@@ -377,17 +338,17 @@ extern "C" {
 int ramses_amd_halo_plan(int ilevel, int ngrid, const int *igrid, const double *xg, int64_t ngridmax, int ncpu,
                          const int *em_ngrid, const int *em_igrid, const int *rc_ngrid, const int *rc_igrid,
                          int *out_box, int64_t *act_org, int64_t *em_org, int *rc_src, int64_t *rc_org, int64_t rc_cap) {
-  if (!igrid || !xg || !em_ngrid || !rc_ngrid || !out_box || ncpu < 1) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!igrid || !xg || !em_ngrid || !rc_ngrid || !out_box || ncpu < 1) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   HaloPlan P;
   if (!build_halo_plan(ilevel, ngrid, igrid, xg, ngridmax, ncpu, em_ngrid, em_igrid, rc_ngrid, rc_igrid, P))
-    return failf(RAMSES_AMD_EUNSUPPORTED, "%s", P.error.c_str());
+    return fail(RAMSES_AMD_EUNSUPPORTED, "%s", P.error.c_str());
   for (int d = 0; d < 3; d++) { out_box[d] = P.olo[d]; out_box[3 + d] = P.odim[d]; }
   out_box[6] = P.self_axes;
   out_box[7] = (int)P.rc_src.size();
   if (act_org) std::memcpy(act_org, P.act_org.data(), sizeof(int64_t) * P.act_org.size());
   if (em_org) std::memcpy(em_org, P.em_org.data(), sizeof(int64_t) * P.em_org.size());
   if (rc_src && rc_org) {
-    if ((int64_t)P.rc_src.size() > rc_cap) return failf(RAMSES_AMD_EINVAL, "rc_cap too small");
+    if ((int64_t)P.rc_src.size() > rc_cap) return fail(RAMSES_AMD_EINVAL, "rc_cap too small");
     std::memcpy(rc_src, P.rc_src.data(), sizeof(int) * P.rc_src.size());
     std::memcpy(rc_org, P.rc_org.data(), sizeof(int64_t) * P.rc_org.size());
   }
@@ -402,19 +363,19 @@ int ramses_amd_mpires_setup(const ramses_amd_hydro_params *p, int ilevel, int ng
                             int64_t ngridmax, int64_t ncoarse, int nx_loc, const double *uold, const double *unew,
                             int ncpu, int myid, const int *em_ngrid, const int *em_igrid, const int *rc_ngrid,
                             const int *rc_igrid) {
-  if (!p || !igrid || !xg || !uold || !unew || !em_ngrid || !rc_ngrid) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (p->ndim != 3) return failf(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3");
+  if (!p || !igrid || !xg || !uold || !unew || !em_ngrid || !rc_ngrid) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (p->ndim != 3) return fail(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3");
   if (p->nvar < 5 || p->nvar > RAMSES_AMD_MAX_NVAR)
-    return failf(RAMSES_AMD_EUNSUPPORTED, "ramses_amd_mpires_setup: NVAR=%d: the device path implements 5+NENER <= NVAR <= %d", p->nvar, RAMSES_AMD_MAX_NVAR);
+    return fail(RAMSES_AMD_EUNSUPPORTED, "ramses_amd_mpires_setup: NVAR=%d: the device path implements 5+NENER <= NVAR <= %d", p->nvar, RAMSES_AMD_MAX_NVAR);
   if (p->nener < 0 || p->nener > RAMSES_AMD_MAX_NENER || p->nvar < 5 + p->nener)
-    return failf(RAMSES_AMD_EUNSUPPORTED, "NENER=%d with NVAR=%d: the device path implements NENER=0, 1, 2 with NVAR >= 5+NENER", p->nener, p->nvar);
-  if (nx_loc != 1) return failf(RAMSES_AMD_EUNSUPPORTED, "device path needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
-  if (ncpu < 1 || myid < 1 || myid > ncpu) return failf(RAMSES_AMD_EINVAL, "bad ncpu/myid");
+    return fail(RAMSES_AMD_EUNSUPPORTED, "NENER=%d with NVAR=%d: the device path implements NENER=0, 1, 2 with NVAR >= 5+NENER", p->nener, p->nvar);
+  if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "device path needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
+  if (ncpu < 1 || myid < 1 || myid > ncpu) return fail(RAMSES_AMD_EINVAL, "bad ncpu/myid");
   MpiRes &M = g_mr;
-  if (M.valid && M.host_stale) return failf(RAMSES_AMD_EINVAL, "mpires_setup: the host array is stale; sync first");
+  if (M.valid && M.host_stale) return fail(RAMSES_AMD_EINVAL, "mpires_setup: the host array is stale; sync first");
   M.valid = false;
   if (!build_halo_plan(ilevel, ngrid, igrid, xg, ngridmax, ncpu, em_ngrid, em_igrid, rc_ngrid, rc_igrid, M.plan))
-    return failf(RAMSES_AMD_EUNSUPPORTED, "%s", M.plan.error.c_str());
+    return fail(RAMSES_AMD_EUNSUPPORTED, "%s", M.plan.error.c_str());
   HaloPlan &P = M.plan;
   M.level = ilevel; M.ngrid = ngrid; M.nvar = p->nvar; M.ncpu = ncpu; M.myid = myid; M.nener = p->nener;
   M.ncoarse = ncoarse; M.ngridmax = ngridmax; M.ncell = ncoarse + 8 * ngridmax;
@@ -453,7 +414,7 @@ int ramses_amd_mpires_setup(const ramses_amd_hydro_params *p, int ilevel, int ng
     M.f_send_off[c + 1] = (int64_t)P.em_first[c + 1] * per;
     M.f_recv_off[c + 1] = (int64_t)P.rc_first[c + 1] * per;
     if (em_ngrid[c] > 0 || rc_ngrid[c] > 0) {
-      if (c == myid - 1) return failf(RAMSES_AMD_EINVAL, "a rank cannot be its own peer");
+      if (c == myid - 1) return fail(RAMSES_AMD_EINVAL, "a rank cannot be its own peer");
       M.peers.push_back(c);
       M.send_off.push_back((int64_t)P.em_first[c] * per); M.send_cnt.push_back((int64_t)em_ngrid[c] * per);
       M.recv_off.push_back((int64_t)P.rc_first[c] * per); M.recv_cnt.push_back((int64_t)rc_ngrid[c] * per);
@@ -508,13 +469,13 @@ int ramses_amd_mpires_which(const double *xx) {
   return 0;
 }
 
-#define NEED_VALID(who) do { if (!g_mr.valid) return failf(RAMSES_AMD_EINVAL, "%s: no resident level (ramses_amd_mpires_setup)", who); } while (0)
+#define NEED_VALID(who) do { if (!g_mr.valid) return fail(RAMSES_AMD_EINVAL, "%s: no resident level (ramses_amd_mpires_setup)", who); } while (0)
 
 // courant_fine on the rank's brick: out4 = {dt_loc (min with dt_in), mass_loc, sum(E*vol), eint_loc};
 // the shim reduces over the ranks as the reference does (hydro/courant_fine.f90:133-140)
 int ramses_amd_mpires_courant(const ramses_amd_hydro_params *p, double dx, double dt_in, double *out4) {
   NEED_VALID("courant_fine");
-  if (!p || !out4) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!p || !out4) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   MpiRes &M = g_mr;
   hipStream_t s = M.s_comp;
   if (int rc = join_comm(M)) return rc;
@@ -575,7 +536,7 @@ int ramses_amd_mpires_godunov(const ramses_amd_hydro_params *p, double dx, doubl
 int ramses_amd_mpires_reverse_unew(void) {
   NEED_VALID("make_virtual_reverse_dp");
   MpiRes &M = g_mr;
-  if (!M.new_ready) return failf(RAMSES_AMD_EINVAL, "make_virtual_reverse_dp(unew): no godunov_fine result pending");
+  if (!M.new_ready) return fail(RAMSES_AMD_EINVAL, "make_virtual_reverse_dp(unew): no godunov_fine result pending");
   if (M.prefetched) return 0;     // done on the communication stream before the pack (ramses_amd_mpires_godunov)
   OctListArgs A = list_args(M, M.bnew.as<double>(), nullptr, M.em_org.as<int64_t>(), nullptr, M.plan.em_first[M.ncpu]);
   HCHK(launch_oct_list(A, OL_ADDZERO, M.s_comp), "reverse launch");
@@ -583,8 +544,8 @@ int ramses_amd_mpires_reverse_unew(void) {
 }
 
 static int mpires_swap(MpiRes &M) {
-  if (!M.new_ready) return failf(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending");
-  Buf t = M.bold; M.bold = M.bnew; M.bnew = t;
+  if (!M.new_ready) return fail(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending");
+  DevBuf t = M.bold; M.bold = M.bnew; M.bnew = t;
   M.new_ready = false; M.host_stale = true;
   return 0;
 }
@@ -592,7 +553,7 @@ int ramses_amd_mpires_set_uold(void) {
   NEED_VALID("set_uold");
   MpiRes &M = g_mr;
   if (M.nener > 0)
-    return failf(RAMSES_AMD_EINVAL, "set_uold: the level carries NENER=%d non-thermal energies: their pdV term is "
+    return fail(RAMSES_AMD_EINVAL, "set_uold: the level carries NENER=%d non-thermal energies: their pdV term is "
                  "ramses_amd_mpires_set_uold_pdv's", M.nener);
   return mpires_swap(M);
 }
@@ -602,9 +563,9 @@ int ramses_amd_mpires_set_uold(void) {
 int ramses_amd_mpires_set_uold_pdv(const ramses_amd_hydro_params *p, double dx, double dt) {
   NEED_VALID("set_uold");
   MpiRes &M = g_mr;
-  if (!M.new_ready) return failf(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending");
+  if (!M.new_ready) return fail(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending");
   if (int rc = join_comm(M)) return rc;
-  if (M.prefetched) return failf(RAMSES_AMD_EINVAL, "set_uold with pdV: the new state's halo already left (overlap with NENER > 0)");
+  if (M.prefetched) return fail(RAMSES_AMD_EINVAL, "set_uold with pdV: the new state's halo already left (overlap with NENER > 0)");
   if (int rc = ramses_amd_pdv_brick(p, &M.brick, M.bold.as<double>(), M.bnew.as<double>(), dx, dt, M.s_comp)) return rc;
   return mpires_swap(M);
 }
@@ -639,7 +600,7 @@ int ramses_amd_mpires_halo_forward(void) {
 // length send_off[icpu]-send_off[icpu-1] doubles, likewise h_recv/recv_off -- stage_in unpacks what arrived.
 int ramses_amd_mpires_halo_stage_out(double **h_send, const int64_t **send_off, double **h_recv, const int64_t **recv_off) {
   NEED_VALID("make_virtual_fine_dp");
-  if (!h_send || !send_off || !h_recv || !recv_off) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!h_send || !send_off || !h_recv || !recv_off) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   MpiRes &M = g_mr;
   hipStream_t s = M.s_comp;
   const int nem = M.plan.em_first[M.ncpu];
@@ -675,8 +636,8 @@ int ramses_amd_mpires_halo_stage_in(void) {
 int ramses_amd_mpires_halo_stage_out_f90(int64_t *h_send_addr, int64_t *h_recv_addr, int64_t *send_off, int64_t *recv_off, int ncpu) {
   double *hs, *hr;
   const int64_t *so, *ro;
-  if (!h_send_addr || !h_recv_addr || !send_off || !recv_off) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (ncpu != g_mr.ncpu) return failf(RAMSES_AMD_EINVAL, "ncpu mismatch");
+  if (!h_send_addr || !h_recv_addr || !send_off || !recv_off) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (ncpu != g_mr.ncpu) return fail(RAMSES_AMD_EINVAL, "ncpu mismatch");
   if (int rc = ramses_amd_mpires_halo_stage_out(&hs, &so, &hr, &ro)) return rc;
   *h_send_addr = (int64_t)(intptr_t)hs; *h_recv_addr = (int64_t)(intptr_t)hr;
   for (int c = 0; c <= ncpu; c++) { send_off[c] = so[c]; recv_off[c] = ro[c]; }
@@ -687,7 +648,7 @@ int ramses_amd_mpires_halo_stage_out_f90(int64_t *h_send_addr, int64_t *h_recv_a
 int ramses_amd_mpires_sync_host(double *uold) {
   MpiRes &M = g_mr;
   if (!M.valid || !M.host_stale) return 0;
-  if (uold != M.h_uold) return failf(RAMSES_AMD_EINVAL, "sync_host: not the array the level was loaded from");
+  if (uold != M.h_uold) return fail(RAMSES_AMD_EINVAL, "sync_host: not the array the level was loaded from");
   hipStream_t s = M.s_comp;
   HCHK(hipStreamSynchronize(M.s_comm), "sync");
   PackArgs A;
@@ -709,7 +670,7 @@ int ramses_amd_mpires_sync_host(double *uold) {
 
 int ramses_amd_mpires_invalidate(void) {
   MpiRes &M = g_mr;
-  if (M.valid && M.host_stale) return failf(RAMSES_AMD_EINVAL, "invalidate: the host array is stale; sync first");
+  if (M.valid && M.host_stale) return fail(RAMSES_AMD_EINVAL, "invalidate: the host array is stale; sync first");
   M.valid = false;
   return 0;
 }

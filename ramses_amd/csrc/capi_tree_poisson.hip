@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -101,8 +100,6 @@ MgAmrCtx g_mg;
 bool g_mg_force_sync = false;     // several MPI ranks: every routine exchanges its arrays with the host
 }  // namespace
 }  // extern "C++"
-
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hipfail(e_, what); } while (0)
 
 // (re)load the fine level from the host arrays: phi -> u1, f(:,2) -> u2, f(:,3) -> u4, flag2 -> scan
 static void mgamr_count(size_t bytes) {
@@ -929,7 +926,6 @@ int ramses_amd_cgmpi_end(double *phi, double *f) {
   return 0;
 }
 #undef CGM_OPEN
-#undef HCHK
 
 }  // extern "C"
 

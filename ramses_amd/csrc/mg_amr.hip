@@ -18,6 +18,7 @@
 // the sequential loops parallelise without changing a bit.
 #include <hip/hip_runtime.h>
 
+#include "host_util.hpp"
 #include "mg_amr_args.hpp"
 
 namespace ramses_amd {
@@ -250,13 +251,6 @@ __global__ void gather_scan_kernel(const int *flag2, int *out, const int *igrid,
 __global__ void lookup_kernel(const int *igrid, int ngrid, int *lookup) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < ngrid) lookup[igrid[i] - 1] = i + 1;
-}
-
-static inline int grid_for(long work, int cap = 4096) {
-  long g = (work + 255) / 256;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
 }
 
 }  // namespace mgamr

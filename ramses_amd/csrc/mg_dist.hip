@@ -23,19 +23,17 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../../include/ramses_amd.h"
+#include "host_util.hpp"
 #include "mg_args.hpp"
 #include "pack_args.hpp"
 
 using namespace ramses_amd;
-
-extern "C" int ramses_amd_set_error(int code, const char *msg);   // capi.hip
 
 namespace {
 
@@ -44,15 +42,6 @@ constexpr int MIN_FUSED = 64;    // the fused smoother's tile width
 constexpr int MAXITER = 10;      // multigrid_fine_commons.f90:34
 constexpr double SAFE_FACTOR = 0.5;   // :35
 
-int failf(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return ramses_amd_set_error(code, buf);
-}
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failf(RAMSES_AMD_EHIP, "%s: %s", what, hipGetErrorString(e_)); } while (0)
 #define RCHK(call) do { int rc_ = (call); if (rc_) return rc_; } while (0)
 
 struct Seg {
@@ -182,10 +171,10 @@ int plan_regions(const int *pgrid, const int *coords, const int *rank_of_brick, 
     }
     P.total = pos;
   }
-  if (P.segs_s.size() != P.segs_r.size()) return failf(RAMSES_AMD_EINVAL, "halo plan: send and receive peers differ");
+  if (P.segs_s.size() != P.segs_r.size()) return fail(RAMSES_AMD_EINVAL, "halo plan: send and receive peers differ");
   for (size_t i = 0; i < P.segs_s.size(); i++)
     if (P.segs_s[i].peer != P.segs_r[i].peer || P.segs_s[i].cnt != P.segs_r[i].cnt)
-      return failf(RAMSES_AMD_EINVAL, "halo plan: message sizes of peer %d differ", P.segs_s[i].peer);
+      return fail(RAMSES_AMD_EINVAL, "halo plan: message sizes of peer %d differ", P.segs_s[i].peer);
   return 0;
 }
 
@@ -252,9 +241,9 @@ int exchange(ramses_amd_mgdist *M, Level &L, double *t, hipStream_t s) {
       if (P.segs_s[i].peer == M->rank)
         std::memcpy(P.h_recv + P.segs_r[i].off, P.h_send + P.segs_s[i].off, sizeof(double) * P.segs_s[i].cnt);
     if (!peers.empty()) {
-      if (!M->tr.exchange) return failf(RAMSES_AMD_EINVAL, "distributed multigrid: no transport (exchange callback missing)");
+      if (!M->tr.exchange) return fail(RAMSES_AMD_EINVAL, "distributed multigrid: no transport (exchange callback missing)");
       const int rc_ = M->tr.exchange(M->tr.user, (int)peers.size(), peers.data(), P.h_send, so.data(), sc.data(), P.h_recv, ro.data(), rc.data());
-      if (rc_) return failf(RAMSES_AMD_EHIP, "distributed multigrid: the transport's exchange failed (%d)", rc_);
+      if (rc_) return fail(RAMSES_AMD_EHIP, "distributed multigrid: the transport's exchange failed (%d)", rc_);
     }
     HCHK(hipMemcpyAsync(P.d_recv, P.h_recv, sizeof(double) * P.total, hipMemcpyHostToDevice, s), "halo H2D");
   }
@@ -275,9 +264,9 @@ int allreduce_sum(ramses_amd_mgdist *M, double *d_value, double *out, hipStream_
   HCHK(hipMemcpyAsync(out, d_value, sizeof(double), hipMemcpyDeviceToHost, s), "norm copy");
   HCHK(hipStreamSynchronize(s), "stream sync");
   if (!M->use_rccl && M->world > 1) {
-    if (!M->tr.allreduce_sum) return failf(RAMSES_AMD_EINVAL, "distributed multigrid: no transport (allreduce callback missing)");
+    if (!M->tr.allreduce_sum) return fail(RAMSES_AMD_EINVAL, "distributed multigrid: no transport (allreduce callback missing)");
     const int rc_ = M->tr.allreduce_sum(M->tr.user, out);
-    if (rc_) return failf(RAMSES_AMD_EHIP, "distributed multigrid: the transport's allreduce failed (%d)", rc_);
+    if (rc_) return fail(RAMSES_AMD_EHIP, "distributed multigrid: the transport's allreduce failed (%d)", rc_);
   }
   return 0;
 }
@@ -347,9 +336,9 @@ int coarse_cycle(ramses_amd_mgdist *M, int l, int safe, hipStream_t s) {
     } else {
       HCHK(hipMemcpyAsync(M->h_mine, M->rep_mine, sizeof(double) * part, hipMemcpyDeviceToHost, s), "gather D2H");
       HCHK(hipStreamSynchronize(s), "stream sync");
-      if (!M->tr.allgather) return failf(RAMSES_AMD_EINVAL, "distributed multigrid: no transport (allgather callback missing)");
+      if (!M->tr.allgather) return fail(RAMSES_AMD_EINVAL, "distributed multigrid: no transport (allgather callback missing)");
       const int rc_ = M->tr.allgather(M->tr.user, M->h_mine, (int64_t)part, M->h_parts);
-      if (rc_) return failf(RAMSES_AMD_EHIP, "distributed multigrid: the transport's allgather failed (%d)", rc_);
+      if (rc_) return fail(RAMSES_AMD_EHIP, "distributed multigrid: the transport's allgather failed (%d)", rc_);
       HCHK(hipMemcpyAsync(M->rep_parts, M->h_parts, sizeof(double) * part * M->world, hipMemcpyHostToDevice, s), "gather H2D");
     }
     const int N = 1 << l;
@@ -377,15 +366,15 @@ extern "C" {
 
 int ramses_amd_mgdist_create(int level, const int *pgrid, int rank, const int *rank_of_brick,
                              const ramses_amd_mg_transport *transport, ramses_amd_mgdist **out) {
-  if (!pgrid || !out) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!pgrid || !out) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   *out = nullptr;
-  if (level < 1 || level > 11) return failf(RAMSES_AMD_EINVAL, "multigrid level must be in [1,11] (got %d)", level);
+  if (level < 1 || level > 11) return fail(RAMSES_AMD_EINVAL, "multigrid level must be in [1,11] (got %d)", level);
   int world = 1;
   for (int d = 0; d < 3; d++) {
-    if (pgrid[d] < 1 || (pgrid[d] & (pgrid[d] - 1))) return failf(RAMSES_AMD_EINVAL, "distributed multigrid needs a power-of-two rank grid (got %d x %d x %d)", pgrid[0], pgrid[1], pgrid[2]);
+    if (pgrid[d] < 1 || (pgrid[d] & (pgrid[d] - 1))) return fail(RAMSES_AMD_EINVAL, "distributed multigrid needs a power-of-two rank grid (got %d x %d x %d)", pgrid[0], pgrid[1], pgrid[2]);
     world *= pgrid[d];
   }
-  if (rank < 0 || rank >= world) return failf(RAMSES_AMD_EINVAL, "rank %d outside the %d ranks of the grid", rank, world);
+  if (rank < 0 || rank >= world) return fail(RAMSES_AMD_EINVAL, "rank %d outside the %d ranks of the grid", rank, world);
   ramses_amd_mgdist *M = new ramses_amd_mgdist();
   M->level = level; M->rank = rank; M->world = world;
   M->rank_of_brick.resize(world);
@@ -393,7 +382,7 @@ int ramses_amd_mgdist_create(int level, const int *pgrid, int rank, const int *r
   int mine = -1;
   for (int b = 0; b < world; b++) {
     const int r = rank_of_brick ? rank_of_brick[b] : b;
-    if (r < 0 || r >= world || seen[r]) { delete M; return failf(RAMSES_AMD_EINVAL, "rank_of_brick is not a permutation of the ranks"); }
+    if (r < 0 || r >= world || seen[r]) { delete M; return fail(RAMSES_AMD_EINVAL, "rank_of_brick is not a permutation of the ranks"); }
     seen[r] = 1;
     M->rank_of_brick[b] = r;
     if (r == rank) mine = b;
@@ -404,7 +393,7 @@ int ramses_amd_mgdist_create(int level, const int *pgrid, int rank, const int *r
     if (M->dims[d] < MIN_FUSED) {
       const int dd = M->dims[d];
       delete M;
-      return failf(RAMSES_AMD_EINVAL, "per-rank brick of level %d on %d x %d x %d ranks: every extent must be >= %d (got %d)", level, pgrid[0], pgrid[1], pgrid[2], MIN_FUSED, dd);
+      return fail(RAMSES_AMD_EINVAL, "per-rank brick of level %d on %d x %d x %d ranks: every extent must be >= %d (got %d)", level, pgrid[0], pgrid[1], pgrid[2], MIN_FUSED, dd);
     }
   }
   M->coords[0] = mine % pgrid[0]; M->coords[1] = (mine / pgrid[0]) % pgrid[1]; M->coords[2] = mine / (pgrid[0] * pgrid[1]);
@@ -416,7 +405,7 @@ int ramses_amd_mgdist_create(int level, const int *pgrid, int rank, const int *r
   if (transport) M->tr = *transport; else std::memset(&M->tr, 0, sizeof(M->tr));
   if (M->use_rccl && world > 1 && !ramses_amd_rccl_ready()) {
     delete M;
-    return failf(RAMSES_AMD_EINVAL, "distributed multigrid without a transport table needs the RCCL communicator (ramses_amd_rccl_init)");
+    return fail(RAMSES_AMD_EINVAL, "distributed multigrid without a transport table needs the RCCL communicator (ramses_amd_rccl_init)");
   }
   int rc = 0;
   auto bail = [&](int code) { ramses_amd_mgdist_destroy(M); return code; };
@@ -447,7 +436,7 @@ int ramses_amd_mgdist_create(int level, const int *pgrid, int rank, const int *r
   dmalloc(&M->dense, (size_t)M->dims[0] * M->dims[1] * M->dims[2]);
   if (e == hipSuccess) e = hipMalloc(&M->d_rank_of_brick, sizeof(int) * world);
   if (e == hipSuccess) e = hipMemcpy(M->d_rank_of_brick, M->rank_of_brick.data(), sizeof(int) * world, hipMemcpyHostToDevice);
-  if (e != hipSuccess) return bail(failf(RAMSES_AMD_EHIP, "distributed multigrid: device allocation: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return bail(fail(RAMSES_AMD_EHIP, "distributed multigrid: device allocation: %s", hipGetErrorString(e)));
   *out = M;
   return 0;
 }
@@ -470,7 +459,7 @@ int ramses_amd_mgdist_destroy(ramses_amd_mgdist *M) {
 
 int ramses_amd_mgdist_info(const ramses_amd_mgdist *M, int *dims, int *coords, int *n_distributed_levels, int *first_replicated_level,
                            int *safe_mode, int64_t *exchanges) {
-  if (!M) return failf(RAMSES_AMD_EINVAL, "NULL context");
+  if (!M) return fail(RAMSES_AMD_EINVAL, "NULL context");
   for (int d = 0; d < 3; d++) {
     if (dims) dims[d] = M->dims[d];
     if (coords) coords[d] = M->coords[d];
@@ -487,13 +476,13 @@ int ramses_amd_mgdist_info(const ramses_amd_mgdist *M, int *dims, int *coords, i
 // of 0 .. N-1 (host array).  From then on the two norms of every iteration are strictly sequential sums in that order -- the
 // reference's bits, and with them its convergence decision; n = 0 returns to the smoother's own reduction tree.
 int ramses_amd_mgdist_set_order(ramses_amd_mgdist *M, const int *order, int64_t n) {
-  if (!M) return failf(RAMSES_AMD_EINVAL, "NULL context");
+  if (!M) return fail(RAMSES_AMD_EINVAL, "NULL context");
   const long N = (long)M->dims[0] * M->dims[1] * M->dims[2];
   if (n == 0) { M->order_n = 0; return 0; }
-  if (!order || n != N) return failf(RAMSES_AMD_EINVAL, "the order must name each of the brick's %ld cells once (got %ld entries)", N, (long)n);
+  if (!order || n != N) return fail(RAMSES_AMD_EINVAL, "the order must name each of the brick's %ld cells once (got %ld entries)", N, (long)n);
   std::vector<unsigned char> seen((size_t)N, 0);
   for (long k = 0; k < N; k++) {
-    if (order[k] < 0 || order[k] >= N || seen[(size_t)order[k]]) return failf(RAMSES_AMD_EINVAL, "the order is not a permutation of the brick's cells (entry %ld)", k);
+    if (order[k] < 0 || order[k] >= N || seen[(size_t)order[k]]) return fail(RAMSES_AMD_EINVAL, "the order is not a permutation of the brick's cells (entry %ld)", k);
     seen[(size_t)order[k]] = 1;
   }
   if (!M->d_order) HCHK(hipMalloc(&M->d_order, sizeof(int) * (size_t)N), "hipMalloc");
@@ -505,7 +494,7 @@ int ramses_amd_mgdist_set_order(ramses_amd_mgdist *M, const int *order, int64_t 
 }
 
 int ramses_amd_mgdist_set_safe_mode(ramses_amd_mgdist *M, int safe_mode) {
-  if (!M) return failf(RAMSES_AMD_EINVAL, "NULL context");
+  if (!M) return fail(RAMSES_AMD_EINVAL, "NULL context");
   M->safe_mode = safe_mode ? 1 : 0;
   return 0;
 }
@@ -513,7 +502,7 @@ int ramses_amd_mgdist_set_safe_mode(ramses_amd_mgdist *M, int safe_mode) {
 // multigrid_fine from a zero first guess.  d_rho: this rank's dense [nz][ny][nx] brick of the density.
 int ramses_amd_mgdist_solve(ramses_amd_mgdist *M, const double *d_rho, double rho_tot, double fourpi, double epsilon,
                             int *iters_out, double *err_out, void *stream) {
-  if (!M || !d_rho) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!M || !d_rho) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Level &L = M->lev[M->level];
   double *phi = L.u[0], *phi2 = L.u[3], *f1 = L.u[2], *f2 = L.u[1];
@@ -562,14 +551,14 @@ int ramses_amd_mgdist_solve(ramses_amd_mgdist *M, const double *d_rho, double rh
 
 // phi of this rank's brick as a dense [nz][ny][nx] array
 int ramses_amd_mgdist_get_phi(ramses_amd_mgdist *M, double *d_phi, void *stream) {
-  if (!M || !d_phi) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!M || !d_phi) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   Level &L = M->lev[M->level];
   return interior_copy(L, L.u[0], d_phi, 1, reinterpret_cast<hipStream_t>(stream));
 }
 
 // first guess / restart: phi of this rank's brick from a dense array (ghosts are exchanged by the next call)
 int ramses_amd_mgdist_set_phi(ramses_amd_mgdist *M, const double *d_phi, void *stream) {
-  if (!M || !d_phi) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!M || !d_phi) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   Level &L = M->lev[M->level];
   M->phi_fresh = false;
   RCHK(interior_copy(L, L.u[0], const_cast<double *>(d_phi), 0, reinterpret_cast<hipStream_t>(stream)));
@@ -579,7 +568,7 @@ int ramses_amd_mgdist_set_phi(ramses_amd_mgdist *M, const double *d_phi, void *s
 
 // force_fine: halo of phi, then gradient_phi into the dense [3][nz][ny][nx] array d_f
 int ramses_amd_mgdist_force(ramses_amd_mgdist *M, double *d_f, void *stream) {
-  if (!M || !d_f) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!M || !d_f) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   Level &L = M->lev[M->level];
   RCHK(exchange(M, L, L.u[0], s));
@@ -602,17 +591,6 @@ inline bool oct_cell_origin(const double *xg, int64_t ngridmax, int ig, int n, i
   }
   return true;
 }
-struct DevArr {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-};
 }  // namespace
 
 // The deep-halo plan of one rank, host only (no device): what ramses_amd_mgdist_create builds for a level whose bricks have
@@ -626,10 +604,10 @@ int ramses_amd_mgdist_plan(const int *pgrid, int rank, const int *rank_of_brick,
                            int64_t *seg_recv_off, int64_t *seg_recv_cnt, int64_t *total) {
   if (!pgrid || !dims || !send_boxes || !send_offs || !recv_boxes || !recv_offs || !npeer || !seg_peer || !seg_send_off ||
       !seg_send_cnt || !seg_recv_off || !seg_recv_cnt || !total || ng < 1)
-    return failf(RAMSES_AMD_EINVAL, "bad argument");
+    return fail(RAMSES_AMD_EINVAL, "bad argument");
   int world = 1;
   for (int d = 0; d < 3; d++) {
-    if (pgrid[d] < 1 || dims[d] < ng) return failf(RAMSES_AMD_EINVAL, "bad rank grid / brick");
+    if (pgrid[d] < 1 || dims[d] < ng) return fail(RAMSES_AMD_EINVAL, "bad rank grid / brick");
     world *= pgrid[d];
   }
   std::vector<int> rob(world);
@@ -638,7 +616,7 @@ int ramses_amd_mgdist_plan(const int *pgrid, int rank, const int *rank_of_brick,
     rob[b] = rank_of_brick ? rank_of_brick[b] : b;
     if (rob[b] == rank) mine = b;
   }
-  if (mine < 0) return failf(RAMSES_AMD_EINVAL, "rank %d owns no brick", rank);
+  if (mine < 0) return fail(RAMSES_AMD_EINVAL, "rank %d owns no brick", rank);
   const int coords[3] = {mine % pgrid[0], (mine / pgrid[0]) % pgrid[1], mine / (pgrid[0] * pgrid[1])};
   HaloPlan P;
   RCHK(plan_regions(pgrid, coords, rob.data(), dims, ng, P));
@@ -657,17 +635,17 @@ int ramses_amd_mgdist_plan(const int *pgrid, int rank, const int *rank_of_brick,
 // The box the rank's octs of the level fill: lo[3] (first cell) and dims[3] (cells), host only.  RAMSES_AMD_EUNSUPPORTED
 // when they do not fill a box (the caller then keeps the multigrid of AMR levels).
 int ramses_amd_mgdist_oct_box(int ilevel, int ngrid, const int *igrid, const double *xg, int64_t ngridmax, int *lo, int *dims) {
-  if (!igrid || !xg || !lo || !dims || ilevel < 1 || ilevel > 11 || ngrid < 1) return failf(RAMSES_AMD_EINVAL, "bad argument");
+  if (!igrid || !xg || !lo || !dims || ilevel < 1 || ilevel > 11 || ngrid < 1) return fail(RAMSES_AMD_EINVAL, "bad argument");
   const int n = 1 << ilevel;
   int mn[3] = {n, n, n}, mx[3] = {-1, -1, -1};
   for (int g = 0; g < ngrid; g++) {
     int o[3];
-    if (!oct_cell_origin(xg, ngridmax, igrid[g], n, o)) return failf(RAMSES_AMD_EINVAL, "oct %d of level %d does not sit on the level lattice", igrid[g], ilevel);
+    if (!oct_cell_origin(xg, ngridmax, igrid[g], n, o)) return fail(RAMSES_AMD_EINVAL, "oct %d of level %d does not sit on the level lattice", igrid[g], ilevel);
     for (int d = 0; d < 3; d++) { mn[d] = std::min(mn[d], o[d]); mx[d] = std::max(mx[d], o[d] + 2); }
   }
   long vol = 1;
   for (int d = 0; d < 3; d++) { lo[d] = mn[d]; dims[d] = mx[d] - mn[d]; vol *= dims[d]; }
-  if (vol != (long)ngrid * 8) return failf(RAMSES_AMD_EUNSUPPORTED, "the rank's %d octs of level %d do not fill their bounding box (%d x %d x %d cells)", ngrid, ilevel, dims[0], dims[1], dims[2]);
+  if (vol != (long)ngrid * 8) return fail(RAMSES_AMD_EUNSUPPORTED, "the rank's %d octs of level %d do not fill their bounding box (%d x %d x %d cells)", ngrid, ilevel, dims[0], dims[1], dims[2]);
   return 0;
 }
 
@@ -678,24 +656,24 @@ int ramses_amd_mgdist_oct_box(int ilevel, int ngrid, const int *igrid, const dou
 int ramses_amd_mgdist_multigrid_f90(ramses_amd_mgdist *M, int ilevel, int ngrid, const int *igrid, const double *xg,
                                     int64_t ngridmax, int64_t ncoarse, const int *lo, const double *rho, double *phi,
                                     double rho_tot, double fourpi, double epsilon, int *safe_mode, int *iters, double *err) {
-  if (!M || !igrid || !xg || !lo || !rho || !phi || !safe_mode) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (ilevel != M->level) return failf(RAMSES_AMD_EINVAL, "context built for level %d, called for level %d", M->level, ilevel);
+  if (!M || !igrid || !xg || !lo || !rho || !phi || !safe_mode) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (ilevel != M->level) return fail(RAMSES_AMD_EINVAL, "context built for level %d, called for level %d", M->level, ilevel);
   const int n = 1 << ilevel;
   const long N = (long)M->dims[0] * M->dims[1] * M->dims[2];
-  if ((long)ngrid * 8 != N) return failf(RAMSES_AMD_EINVAL, "the rank holds %d octs, its brick %ld cells", ngrid, N);
+  if ((long)ngrid * 8 != N) return fail(RAMSES_AMD_EINVAL, "the rank holds %d octs, its brick %ld cells", ngrid, N);
   for (int d = 0; d < 3; d++)
-    if (lo[d] != M->coords[d] * M->dims[d]) return failf(RAMSES_AMD_EINVAL, "the rank's box does not start where its brick does");
+    if (lo[d] != M->coords[d] * M->dims[d]) return fail(RAMSES_AMD_EINVAL, "the rank's box does not start where its brick does");
   const long ncell = ncoarse + 8 * ngridmax;
   hipStream_t s = nullptr;
-  static DevArr d_rho, d_phi;
+  static DevBuf d_rho, d_phi;
   static std::vector<long> org;
   org.resize(ngrid);
   for (int g = 0; g < ngrid; g++) {
     int o[3];
-    if (!oct_cell_origin(xg, ngridmax, igrid[g], n, o)) return failf(RAMSES_AMD_EINVAL, "oct %d of level %d does not sit on the level lattice", igrid[g], ilevel);
+    if (!oct_cell_origin(xg, ngridmax, igrid[g], n, o)) return fail(RAMSES_AMD_EINVAL, "oct %d of level %d does not sit on the level lattice", igrid[g], ilevel);
     for (int d = 0; d < 3; d++) {
       o[d] -= lo[d];
-      if (o[d] < 0 || o[d] + 2 > M->dims[d]) return failf(RAMSES_AMD_EINVAL, "oct %d lies outside the rank's box", igrid[g]);
+      if (o[d] < 0 || o[d] + 2 > M->dims[d]) return fail(RAMSES_AMD_EINVAL, "oct %d lies outside the rank's box", igrid[g]);
     }
     org[g] = o[0] + (long)M->dims[0] * (o[1] + (long)M->dims[1] * o[2]);
   }
@@ -746,19 +724,19 @@ int ramses_amd_mgdist_multigrid_f90(ramses_amd_mgdist *M, int ilevel, int ngrid,
 int ramses_amd_mgdist_force_f90(ramses_amd_mgdist *M, int ilevel, int ngrid, const int *igrid, const double *xg,
                                 int64_t ngridmax, int64_t ncoarse, const int *lo, double *f, const double *rho, const int *son,
                                 int nvector, double fact, double *diag) {
-  if (!M || !igrid || !xg || !lo || !f || !rho || !son || !diag || nvector < 1) return failf(RAMSES_AMD_EINVAL, "bad argument");
-  if (ilevel != M->level) return failf(RAMSES_AMD_EINVAL, "context built for level %d, called for level %d", M->level, ilevel);
-  if (!M->phi_fresh) return failf(RAMSES_AMD_EINVAL, "force_fine: the context holds no potential (ramses_amd_mgdist_multigrid_f90 first)");
+  if (!M || !igrid || !xg || !lo || !f || !rho || !son || !diag || nvector < 1) return fail(RAMSES_AMD_EINVAL, "bad argument");
+  if (ilevel != M->level) return fail(RAMSES_AMD_EINVAL, "context built for level %d, called for level %d", M->level, ilevel);
+  if (!M->phi_fresh) return fail(RAMSES_AMD_EINVAL, "force_fine: the context holds no potential (ramses_amd_mgdist_multigrid_f90 first)");
   for (int d = 0; d < 3; d++)
     if (lo[d] != M->coords[d] * M->dims[d])
-      return failf(RAMSES_AMD_EINVAL, "force_fine: lo = (%d,%d,%d) is not the origin of this rank's brick (%d,%d,%d)", lo[0], lo[1], lo[2],
+      return fail(RAMSES_AMD_EINVAL, "force_fine: lo = (%d,%d,%d) is not the origin of this rank's brick (%d,%d,%d)", lo[0], lo[1], lo[2],
                    M->coords[0] * M->dims[0], M->coords[1] * M->dims[1], M->coords[2] * M->dims[2]);
   const int n = 1 << ilevel;
   const long N = (long)M->dims[0] * M->dims[1] * M->dims[2];
-  if ((long)ngrid * 8 != N) return failf(RAMSES_AMD_EINVAL, "the rank holds %d octs, its brick %ld cells", ngrid, N);
+  if ((long)ngrid * 8 != N) return fail(RAMSES_AMD_EINVAL, "the rank holds %d octs, its brick %ld cells", ngrid, N);
   const long ncell = ncoarse + 8 * ngridmax;
   hipStream_t s = nullptr;
-  static DevArr d_f;
+  static DevBuf d_f;
   static std::vector<double> h_f;
   HCHK(d_f.ensure(sizeof(double) * 3 * N), "hipMalloc");
   h_f.resize(3 * (size_t)N);
@@ -768,10 +746,10 @@ int ramses_amd_mgdist_force_f90(ramses_amd_mgdist *M, int ilevel, int ngrid, con
   const long py = M->dims[0], pz = (long)M->dims[0] * M->dims[1];
   for (int g = 0; g < ngrid; g++) {
     int o[3];
-    if (!oct_cell_origin(xg, ngridmax, igrid[g], n, o)) return failf(RAMSES_AMD_EINVAL, "oct %d of level %d does not sit on the level lattice", igrid[g], ilevel);
+    if (!oct_cell_origin(xg, ngridmax, igrid[g], n, o)) return fail(RAMSES_AMD_EINVAL, "oct %d of level %d does not sit on the level lattice", igrid[g], ilevel);
     for (int d = 0; d < 3; d++) {
       o[d] -= lo[d];
-      if (o[d] < 0 || o[d] + 2 > M->dims[d]) return failf(RAMSES_AMD_EINVAL, "oct %d lies outside the rank's box", igrid[g]);
+      if (o[d] < 0 || o[d] + 2 > M->dims[d]) return fail(RAMSES_AMD_EINVAL, "oct %d lies outside the rank's box", igrid[g]);
     }
     const long org = o[0] + py * o[1] + pz * o[2];
     for (int ind = 0; ind < 8; ind++) {
@@ -814,10 +792,10 @@ int build_order(ramses_amd_mgdist *M, int ilevel, int ngrid, const int *igrid, c
   order.resize((size_t)N);
   for (int g = 0; g < ngrid; g++) {
     int o[3];
-    if (!oct_cell_origin(xg, ngridmax, igrid[g], n, o)) return failf(RAMSES_AMD_EINVAL, "oct %d of level %d does not sit on the level lattice", igrid[g], ilevel);
+    if (!oct_cell_origin(xg, ngridmax, igrid[g], n, o)) return fail(RAMSES_AMD_EINVAL, "oct %d of level %d does not sit on the level lattice", igrid[g], ilevel);
     for (int d = 0; d < 3; d++) {
       o[d] -= lo[d];
-      if (o[d] < 0 || o[d] + 2 > M->dims[d]) return failf(RAMSES_AMD_EINVAL, "oct %d lies outside the rank's box", igrid[g]);
+      if (o[d] < 0 || o[d] + 2 > M->dims[d]) return fail(RAMSES_AMD_EINVAL, "oct %d lies outside the rank's box", igrid[g]);
     }
     const long org = o[0] + py * o[1] + pz * o[2];
     for (int ind = 0; ind < 8; ind++) order[(size_t)ind * ngrid + g] = (int)(org + (ind & 1) + py * ((ind >> 1) & 1) + pz * ((ind >> 2) & 1));
@@ -830,14 +808,14 @@ int build_order(ramses_amd_mgdist *M, int ilevel, int ngrid, const int *igrid, c
 }  // namespace
 int ramses_amd_mgdist_multigrid_resident_f90(ramses_amd_mgdist *M, int ilevel, int ngrid, const int *igrid, const double *xg, int64_t ngridmax,
                                              const int *lo, double rho_tot, double fourpi, double epsilon, int *safe_mode, int *iters, double *err) {
-  if (!M || !igrid || !xg || !lo || !safe_mode) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (ilevel != M->level) return failf(RAMSES_AMD_EINVAL, "context built for level %d, called for level %d", M->level, ilevel);
+  if (!M || !igrid || !xg || !lo || !safe_mode) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (ilevel != M->level) return fail(RAMSES_AMD_EINVAL, "context built for level %d, called for level %d", M->level, ilevel);
   const long N = (long)M->dims[0] * M->dims[1] * M->dims[2];
-  if ((long)ngrid * 8 != N) return failf(RAMSES_AMD_EINVAL, "the rank holds %d octs, its brick %ld cells", ngrid, N);
+  if ((long)ngrid * 8 != N) return fail(RAMSES_AMD_EINVAL, "the rank holds %d octs, its brick %ld cells", ngrid, N);
   for (int d = 0; d < 3; d++)
-    if (lo[d] != M->coords[d] * M->dims[d]) return failf(RAMSES_AMD_EINVAL, "the rank's box does not start where its brick does");
+    if (lo[d] != M->coords[d] * M->dims[d]) return fail(RAMSES_AMD_EINVAL, "the rank's box does not start where its brick does");
   hipStream_t s = nullptr;
-  static DevArr d_rho;
+  static DevBuf d_rho;
   HCHK(d_rho.ensure(sizeof(double) * N), "hipMalloc");
   if (int rc = build_order(M, ilevel, ngrid, igrid, xg, ngridmax, lo)) return rc;
   RCHK(ramses_amd_amrres_rho_to_brick(ngrid, igrid, M->d_order, reinterpret_cast<double *>(d_rho.p)));
@@ -849,11 +827,11 @@ int ramses_amd_mgdist_multigrid_resident_f90(ramses_amd_mgdist *M, int ilevel, i
 }
 // phi of the rank's own cells from the brick into the host vector (backup_poisson; the caller refreshes the virtual octs)
 int ramses_amd_mgdist_fetch_phi_f90(ramses_amd_mgdist *M, int ngrid, const int *igrid, int64_t ngridmax, int64_t ncoarse, double *phi) {
-  if (!M || !igrid || !phi) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!M || !igrid || !phi) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   const long N = (long)M->dims[0] * M->dims[1] * M->dims[2];
-  if ((long)ngrid * 8 != N || g_h_order.size() != (size_t)N) return failf(RAMSES_AMD_EINVAL, "fetch_phi: not the list of the last solve");
+  if ((long)ngrid * 8 != N || g_h_order.size() != (size_t)N) return fail(RAMSES_AMD_EINVAL, "fetch_phi: not the list of the last solve");
   hipStream_t s = nullptr;
-  static DevArr d_phi;
+  static DevBuf d_phi;
   static std::vector<double> h;
   HCHK(d_phi.ensure(sizeof(double) * N), "hipMalloc");
   h.resize((size_t)N);
@@ -869,7 +847,7 @@ int ramses_amd_mgdist_force_resident_dev_f90(ramses_amd_mgdist *M, int ilevel, i
                                              int nvector, double fact, double *diag);
 // bytes of rho (host -> device) and phi (device -> host) the Fortran entries of the distributed solve moved since the start
 int ramses_amd_mgdist_traffic(int64_t *out2) {
-  if (!out2) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!out2) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   out2[0] = g_rho_up_bytes; out2[1] = g_phi_bytes;
   return 0;
 }
@@ -908,14 +886,14 @@ __global__ __launch_bounds__(256) void mgdist_epot_terms_kernel(const double *__
 int ramses_amd_mgdist_force_resident_f90(ramses_amd_mgdist *M, int ilevel, int ngrid, const int *igrid, int64_t ngridmax, int64_t ncoarse,
                                          const double *rho, int nvector, double fact, double *diag) {
   // (rho = NULL: the deposit lives on the device -- ramses_amd_amrres_rho_keep -- and max |rho| is taken there)
-  if (!M || !igrid || !diag || nvector < 1) return failf(RAMSES_AMD_EINVAL, "bad argument");
-  if (ilevel != M->level) return failf(RAMSES_AMD_EINVAL, "context built for level %d, called for level %d", M->level, ilevel);
-  if (!M->phi_fresh) return failf(RAMSES_AMD_EINVAL, "force_fine: the context holds no potential (ramses_amd_mgdist_multigrid_f90 first)");
+  if (!M || !igrid || !diag || nvector < 1) return fail(RAMSES_AMD_EINVAL, "bad argument");
+  if (ilevel != M->level) return fail(RAMSES_AMD_EINVAL, "context built for level %d, called for level %d", M->level, ilevel);
+  if (!M->phi_fresh) return fail(RAMSES_AMD_EINVAL, "force_fine: the context holds no potential (ramses_amd_mgdist_multigrid_f90 first)");
   const long N = (long)M->dims[0] * M->dims[1] * M->dims[2];
-  if ((long)ngrid * 8 != N) return failf(RAMSES_AMD_EINVAL, "the rank holds %d octs, its brick %ld cells", ngrid, N);
-  if (M->order_n != N || !M->d_order) return failf(RAMSES_AMD_EINVAL, "force_fine (resident): the solve left no oct order (ramses_amd_mgdist_set_order)");
+  if ((long)ngrid * 8 != N) return fail(RAMSES_AMD_EINVAL, "the rank holds %d octs, its brick %ld cells", ngrid, N);
+  if (M->order_n != N || !M->d_order) return fail(RAMSES_AMD_EINVAL, "force_fine (resident): the solve left no oct order (ramses_amd_mgdist_set_order)");
   hipStream_t s = nullptr;
-  static DevArr d_f, d_fp, d_x, d_scr, d_out;
+  static DevBuf d_f, d_fp, d_x, d_scr, d_out;
   HCHK(d_f.ensure(sizeof(double) * 3 * N), "hipMalloc"); HCHK(d_fp.ensure(sizeof(double) * 3 * N), "hipMalloc");
   HCHK(d_x.ensure(sizeof(double) * 3 * N), "hipMalloc"); HCHK(d_scr.ensure(ramses_amd_ordered_sum_scratch(3 * N)), "hipMalloc");
   HCHK(d_out.ensure(sizeof(double)), "hipMalloc");

@@ -15,6 +15,7 @@
 
 #include <cstdlib>
 
+#include "host_util.hpp"
 #include "mg_args.hpp"
 
 namespace ramses_amd {
@@ -397,13 +398,6 @@ __global__ __launch_bounds__(256) void mg_gradient_ghost_kernel(const double *__
 // ---------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------
-static inline int grid_for(long work, int cap = 4096) {
-  long g = (work + 255) / 256;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
-}
-
 hipError_t mg_launch_rhs(const double *rho, double *f2, long N, double fourpi, double rho_tot, hipStream_t s) {
   hipLaunchKernelGGL(mg_rhs_kernel, dim3(grid_for(N)), dim3(256), 0, s, rho, f2, N, fourpi, rho_tot);
   return hipGetLastError();

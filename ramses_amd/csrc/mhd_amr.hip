@@ -24,26 +24,17 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 #include "../../include/ramses_amd.h"
 #include "mhd_assemble.hpp"
+#include "mhd_host.hpp"
 
 using namespace ramses_amd;
 using namespace ramses_amd::mhd;
 
-extern "C" int ramses_amd_set_error(int code, const char *msg);   // capi.hip
-static int failf(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return ramses_amd_set_error(code, buf);
-}
 // RAMSES_AMD_DEBUG_SYNC=1: synchronise and name the stage after every launch (a fault then points at its kernel)
 static int dbg_stage(const char *what) {
   static int on = -1;
@@ -54,7 +45,6 @@ static int dbg_stage(const char *what) {
   fflush(stderr);
   return e == hipSuccess ? 0 : 1;
 }
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failf(RAMSES_AMD_EHIP, "%s: %s", what, hipGetErrorString(e_)); } while (0)
 
 namespace {
 
@@ -604,36 +594,8 @@ __global__ __launch_bounds__(256) void mhd_amr_apply_kernel(double *__restrict__
   unew[k] = x;
 }
 
-struct DBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
-
-int make_const(const ramses_amd_mhd_params *p, MhdConst &P) {
-  if (!p) return failf(RAMSES_AMD_EINVAL, "params is NULL");
-  P.gamma = p->gamma; P.smallr = p->smallr; P.smallc = p->smallc; P.slope_theta = p->slope_theta;
-  P.slope_type = p->slope_type;
-  P.slope_mag_type = p->slope_mag_type == -1 ? p->slope_type : p->slope_mag_type;      // hydro/read_hydro_params.f90:528-530
-  P.riemann = p->riemann; P.riemann2d = p->riemann2d;
-  if (!(p->gamma > 1.0)) return failf(RAMSES_AMD_EINVAL, "gamma must be > 1");
-  if (!slope_type_supported(P.slope_type) || !slope_mag_type_supported(P.slope_mag_type))
-    return failf(RAMSES_AMD_EUNSUPPORTED, "MHD sweep: slope_type 0, 1, 2, 3, 7, 8 and slope_mag_type 0, 1, 2, 7, 8 are on the device (got %d / %d)", P.slope_type, P.slope_mag_type);
-  if (!riemann_supported(P.riemann)) return failf(RAMSES_AMD_EINVAL, "MHD sweep: riemann must be 0 (llf) .. 5 (hydro) (got %d)", P.riemann);
-  if (!riemann2d_supported(P.riemann2d)) return failf(RAMSES_AMD_EINVAL, "MHD sweep: riemann2d must be 0 (llf) .. 5 (hlld) (got %d)", P.riemann2d);
-  return 0;
-}
-
 struct MhdAmrState {
-  DBuf uold, unew, f, son, nbor, father, ig, nfc, rflux, remf, err, cnt, off, okey, tkey, val, okey2, tkey2, val2, perm, perm2, tmp;
+  DevBuf uold, unew, f, son, nbor, father, ig, nfc, rflux, remf, err, cnt, off, okey, tkey, val, okey2, tkey2, val2, perm, perm2, tmp;
   int64_t sweeps = 0, octs = 0, ref_sweeps = 0;
   int ref_levels[64] = {0};
 };
@@ -684,18 +646,18 @@ int ramses_amd_mhd_godfine_amr_device(const ramses_amd_mhd_params *p, int ilevel
   MhdAmrArgs A;
   if (int rc = make_const(p, A.P)) return rc;
   if (ngrid <= 0) return 0;
-  if (!d_igrid || !d_son || !d_nbor || !d_father || !d_uold || !d_unew) return failf(RAMSES_AMD_EINVAL, "NULL device pointer");
-  if (ilevel < 3) return failf(RAMSES_AMD_EUNSUPPORTED, "MHD godfine1 on the device: levels >= 3 (got %d)", ilevel);
-  if (nvector < 1 || nvector > 65536) return failf(RAMSES_AMD_EINVAL, "nvector out of range");
+  if (!d_igrid || !d_son || !d_nbor || !d_father || !d_uold || !d_unew) return fail(RAMSES_AMD_EINVAL, "NULL device pointer");
+  if (ilevel < 3) return fail(RAMSES_AMD_EUNSUPPORTED, "MHD godfine1 on the device: levels >= 3 (got %d)", ilevel);
+  if (nvector < 1 || nvector > 65536) return fail(RAMSES_AMD_EINVAL, "nvector out of range");
   if (interpol_var < 0 || interpol_var > 1 || interpol_type < 0 || interpol_type > 3 || interpol_mag_type < 0 || interpol_mag_type > 3)
-    return failf(RAMSES_AMD_EUNSUPPORTED, "MHD godfine1: interpol_var 0..1, interpol_type 0..3, interpol_mag_type 0..3 (got %d %d %d)", interpol_var, interpol_type, interpol_mag_type);
-  if (!(dx > 0.0) || !(dt >= 0.0)) return failf(RAMSES_AMD_EINVAL, "dx must be > 0 and dt >= 0");
+    return fail(RAMSES_AMD_EUNSUPPORTED, "MHD godfine1: interpol_var 0..1, interpol_type 0..3, interpol_mag_type 0..3 (got %d %d %d)", interpol_var, interpol_type, interpol_mag_type);
+  if (!(dx > 0.0) || !(dt >= 0.0)) return fail(RAMSES_AMD_EINVAL, "dx must be > 0 and dt >= 0");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   MhdAmrState &S = g_ma;
   A.uold = d_uold; A.unew = d_unew; A.grav = d_f;
   A.son = d_son; A.nbor = d_nbor; A.father = d_father; A.igrid = d_igrid; A.ngrid = ngrid;
   A.ncoarse = ncoarse; A.ngridmax = ngridmax; A.ncell = ncoarse + 8 * ngridmax;
-  if ((unsigned long)NF * (unsigned long)A.ncell >= (1ul << 40)) return failf(RAMSES_AMD_EUNSUPPORTED, "cell vectors too long");
+  if ((unsigned long)NF * (unsigned long)A.ncell >= (1ul << 40)) return fail(RAMSES_AMD_EUNSUPPORTED, "cell vectors too long");
   A.dt = dt; A.dx = dx; A.interpol_var = interpol_var; A.interpol_type = interpol_type; A.interpol_mag_type = interpol_mag_type;
   A.coarse = coarse ? 1 : 0;
   HCHK(S.nfc.ensure(sizeof(int) * 27 * (size_t)ngrid), "hipMalloc");
@@ -720,7 +682,7 @@ int ramses_amd_mhd_godfine_amr_device(const ramses_amd_mhd_params *p, int ilevel
   int bad = 0;
   HCHK(hipMemcpyAsync(&bad, A.err, sizeof(int), hipMemcpyDeviceToHost, s), "D2H");
   HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return failf(RAMSES_AMD_EINVAL, "level %d: %d father cells needed by an oct do not exist (tree inconsistent)", ilevel, bad);
+  if (bad) return fail(RAMSES_AMD_EINVAL, "level %d: %d father cells needed by an oct do not exist (tree inconsistent)", ilevel, bad);
   mhd_amr_register();
   S.sweeps++; S.octs += ngrid;
   if (!A.coarse) return 0;
@@ -740,10 +702,10 @@ int ramses_amd_mhd_godfine_amr_device(const ramses_amd_mhd_params *p, int ilevel
   HCHK(hipMemcpyAsync(&total, S.off.as<unsigned>() + ngrid, sizeof(unsigned), hipMemcpyDeviceToHost, s), "D2H");
   HCHK(hipStreamSynchronize(s), "sync");
   if (total == 0) return 0;
-  if ((unsigned long)ngrid * 96ul >= (1ul << 63) / (unsigned long)nvector) return failf(RAMSES_AMD_EUNSUPPORTED, "too many octs for the order key");
-  for (DBuf *b : {&S.okey, &S.tkey, &S.okey2, &S.tkey2}) HCHK(b->ensure(sizeof(unsigned long long) * (size_t)total), "hipMalloc");
-  for (DBuf *b : {&S.val, &S.val2}) HCHK(b->ensure(sizeof(double) * (size_t)total), "hipMalloc");
-  for (DBuf *b : {&S.perm, &S.perm2}) HCHK(b->ensure(sizeof(unsigned) * (size_t)total), "hipMalloc");
+  if ((unsigned long)ngrid * 96ul >= (1ul << 63) / (unsigned long)nvector) return fail(RAMSES_AMD_EUNSUPPORTED, "too many octs for the order key");
+  for (DevBuf *b : {&S.okey, &S.tkey, &S.okey2, &S.tkey2}) HCHK(b->ensure(sizeof(unsigned long long) * (size_t)total), "hipMalloc");
+  for (DevBuf *b : {&S.val, &S.val2}) HCHK(b->ensure(sizeof(double) * (size_t)total), "hipMalloc");
+  for (DevBuf *b : {&S.perm, &S.perm2}) HCHK(b->ensure(sizeof(unsigned) * (size_t)total), "hipMalloc");
   hipLaunchKernelGGL(mhd_amr_emit_kernel<false>, go, bo, 0, s, A, nvector, S.off.as<unsigned>(), (unsigned *)nullptr, S.okey.as<unsigned long long>(),
                      S.tkey.as<unsigned long long>(), S.val.as<double>());
   dbg_stage("emit");
@@ -775,8 +737,8 @@ int ramses_amd_mhd_godunov_fine_amr_f90(const ramses_amd_mhd_params *p, int ilev
                                         int interpol_mag_type) {
   if (ngrid <= 0) return 0;
   if (!use_f) f = nullptr;
-  else if (!f) return failf(RAMSES_AMD_EINVAL, "use_f without f");
-  if (!igrid || !son || !nbor || !father || !uold || !unew) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  else if (!f) return fail(RAMSES_AMD_EINVAL, "use_f without f");
+  if (!igrid || !son || !nbor || !father || !uold || !unew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   MhdAmrState &S = g_ma;
   const size_t ncell = (size_t)(ncoarse + 8 * ngridmax);
   hipStream_t s = nullptr;

@@ -31,7 +31,6 @@
 // ramses_amd_mhd_godunov_brick (and with it the drop-in's staged and resident sweeps) there; the default is the strict build.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <utility>
 #include <cstdlib>
@@ -39,21 +38,11 @@
 
 #include "../../include/ramses_amd.h"
 #include "mhd_assemble.hpp"
+#include "mhd_host.hpp"
 #include "pack_args.hpp"
 
 using namespace ramses_amd;
 using namespace ramses_amd::mhd;
-
-extern "C" int ramses_amd_set_error(int code, const char *msg);   // capi.hip
-static int failf(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return ramses_amd_set_error(code, buf);
-}
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failf(RAMSES_AMD_EHIP, "%s: %s", what, hipGetErrorString(e_)); } while (0)
 
 namespace {
 
@@ -501,30 +490,64 @@ __global__ __launch_bounds__(256) void mhd_courant_final_kernel(const double *__
 
 #endif  // !RAMSES_AMD_MHD_FAST_TU
 
-inline int grid_for(long n, int block) {
-  long g = (n + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > 65536) g = 65536;
-  return (int)g;
-}
+constexpr int MAX_GRID = 65536;   // blocks of the cell-per-thread launches (grid_for)
+constexpr long WORK_DOUBLES_PER_CELL = 8 + 3 + NTR + 15 + 3;
 
-int make_const(const ramses_amd_mhd_params *p, MhdConst &P) {
-  if (!p) return failf(RAMSES_AMD_EINVAL, "params is NULL");
-  P.gamma = p->gamma; P.smallr = p->smallr; P.smallc = p->smallc; P.slope_theta = p->slope_theta;
-  P.slope_type = p->slope_type;
-  P.slope_mag_type = p->slope_mag_type == -1 ? p->slope_type : p->slope_mag_type;      // hydro/read_hydro_params.f90:528-530
-  P.riemann = p->riemann; P.riemann2d = p->riemann2d;
-  if (!(p->gamma > 1.0)) return failf(RAMSES_AMD_EINVAL, "gamma must be > 1");
-  if (!slope_type_supported(P.slope_type) || !slope_mag_type_supported(P.slope_mag_type))
-    return failf(RAMSES_AMD_EUNSUPPORTED, "MHD sweep: slope_type 0, 1, 2, 3, 7, 8 and slope_mag_type 0, 1, 2, 7, 8 are on the device (got %d / %d)", P.slope_type, P.slope_mag_type);
-  if (!riemann_supported(P.riemann))
-    return failf(RAMSES_AMD_EINVAL, "MHD sweep: riemann must be 0 (llf) .. 5 (hydro) (got %d)", P.riemann);
-  if (!riemann2d_supported(P.riemann2d))
-    return failf(RAMSES_AMD_EINVAL, "MHD sweep: riemann2d must be 0 (llf) .. 5 (hlld) (got %d)", P.riemann2d);
+#ifndef RAMSES_AMD_MHD_FAST_TU
+// ---- a fully refined periodic level of the reference's arrays as a brick on the device: what the staged and the resident
+// entry points share.  Its buffers: the host's cell vectors, the level as two bricks, the sweep's workspace, the oct lists and
+// origins of the gather and the scatter ---------------------------------------------------------------------------------
+struct LevelBufs {
+  DevBuf vec, cur, nxt, work, ig, xg, org, flag;
+};
+
+// what both ask of the level (`who` opens the nx_loc message); *n: its cells per direction
+int level_check(const char *who, int ilevel, int ngrid, const int *igrid, const double *xg, int nx_loc, const double *uold, int *n) {
+  if (!igrid || !xg || !uold) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "%s needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", who, nx_loc);
+  if (ilevel < 2 || ilevel > 10) return fail(RAMSES_AMD_EINVAL, "level out of range");
+  *n = 1 << ilevel;
+  if ((long)ngrid * 8 != (long)*n * *n * *n) return fail(RAMSES_AMD_EUNSUPPORTED, "level %d is not fully refined on this rank (ngrid=%d)", ilevel, ngrid);
   return 0;
 }
 
-constexpr long WORK_DOUBLES_PER_CELL = 8 + 3 + NTR + 15 + 3;
+// the copy between B.cur and the cell vectors in B.vec (launch_oct_copy: gather or scatter)
+PackArgs level_pack(const LevelBufs &B, int ngrid, int n, long ncoarse, long ngridmax) {
+  PackArgs PA;
+  PA.igrid = B.ig.as<const int>(); PA.octorg = B.org.as<const long>();
+  PA.ngrid = ngrid; PA.n = n; PA.nvar = NF;
+  PA.ncoarse = ncoarse; PA.ngridmax = ngridmax; PA.ncell = ncoarse + 8 * ngridmax; PA.pitch_var = (long)n * n * n;
+  PA.brick = B.cur.as<double>(); PA.cellvec = B.vec.as<double>();
+  return PA;
+}
+
+// uold(1:ncell,1:nvar+3) goes up into B.vec and the level's cells are gathered into the brick B.cur; B.nxt and B.work are
+// sized for a sweep of it, B.ig / B.org keep the oct lists for the scatter back
+int level_upload(LevelBufs &B, int ilevel, int ngrid, const int *igrid, const double *xg, long ngridmax, long ncoarse, int n,
+                 const double *uold, hipStream_t s) {
+  const long N = (long)n * n * n, ncell = ncoarse + 8 * ngridmax;
+  HCHK(B.vec.ensure(sizeof(double) * NF * ncell), "hipMalloc cell vectors");
+  HCHK(B.cur.ensure(sizeof(double) * NF * N), "hipMalloc brick");
+  HCHK(B.nxt.ensure(sizeof(double) * NF * N), "hipMalloc brick");
+  HCHK(B.work.ensure((size_t)ramses_amd_mhd_workspace_bytes(n, n, n)), "hipMalloc workspace");
+  HCHK(B.org.ensure(sizeof(long) * ngrid), "hipMalloc octorg");
+  HCHK(B.ig.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
+  HCHK(B.xg.ensure(sizeof(double) * 3 * ngridmax), "hipMalloc xg");
+  HCHK(B.flag.ensure(sizeof(int)), "hipMalloc flag");
+  HCHK(hipMemcpyAsync(B.vec.p, uold, sizeof(double) * NF * ncell, hipMemcpyHostToDevice, s), "H2D uold");
+  HCHK(hipMemcpyAsync(B.ig.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
+  HCHK(hipMemcpyAsync(B.xg.p, xg, sizeof(double) * 3 * ngridmax, hipMemcpyHostToDevice, s), "H2D xg");
+  HCHK(hipMemsetAsync(B.flag.p, 0, sizeof(int), s), "memset");
+  const double skip[3] = {0.0, 0.0, 0.0};
+  HCHK(launch_oct_origin(B.ig.as<int>(), B.xg.as<double>(), ngridmax, ngrid, n, skip, B.org.as<long>(), B.flag.as<int>(), s), "oct origin launch");
+  int bad = 0;
+  HCHK(hipMemcpyAsync(&bad, B.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
+  HCHK(hipStreamSynchronize(s), "sync");
+  if (bad) return fail(RAMSES_AMD_EINVAL, "%d octs of level %d do not sit on the level lattice", bad, ilevel);
+  HCHK(launch_oct_copy(level_pack(B, ngrid, n, ncoarse, ngridmax), true, s), "gather launch");
+  return 0;
+}
+#endif  // !RAMSES_AMD_MHD_FAST_TU
 
 }  // namespace
 
@@ -532,7 +555,7 @@ extern "C" {
 
 #ifndef RAMSES_AMD_MHD_FAST_TU
 int64_t ramses_amd_mhd_workspace_bytes(int nx, int ny, int nz) {
-  if (nx < 1 || ny < 1 || nz < 1) return failf(RAMSES_AMD_EINVAL, "bad brick extents");
+  if (nx < 1 || ny < 1 || nz < 1) return fail(RAMSES_AMD_EINVAL, "bad brick extents");
   return (int64_t)sizeof(double) * (WORK_DOUBLES_PER_CELL * nx * ny * nz + NTR * 64) + 256;   // (the trace's last block of 64 cells)
 }
 #define MHD_BRICK_FN ramses_amd_mhd_godunov_brick
@@ -552,11 +575,11 @@ int MHD_BRICK_FN(const ramses_amd_mhd_params *p, int nx, int ny, int nz, const d
 #endif
   MhdArgs A;
   if (int rc = make_const(p, A.P)) return rc;
-  if (nx < 4 || ny < 4 || nz < 4) return failf(RAMSES_AMD_EINVAL, "MHD sweep: the periodic brick needs at least 4 cells per direction (got %d %d %d)", nx, ny, nz);
-  if (!d_uold || !d_unew || !d_work) return failf(RAMSES_AMD_EINVAL, "NULL device pointer");
-  if (d_uold == d_unew) return failf(RAMSES_AMD_EINVAL, "uold and unew must be distinct buffers");
-  if (!(dx > 0.0) || !(dt >= 0.0)) return failf(RAMSES_AMD_EINVAL, "dx must be > 0 and dt >= 0");
-  if (work_bytes < ramses_amd_mhd_workspace_bytes(nx, ny, nz)) return failf(RAMSES_AMD_EINVAL, "MHD sweep: workspace too small (ramses_amd_mhd_workspace_bytes)");
+  if (nx < 4 || ny < 4 || nz < 4) return fail(RAMSES_AMD_EINVAL, "MHD sweep: the periodic brick needs at least 4 cells per direction (got %d %d %d)", nx, ny, nz);
+  if (!d_uold || !d_unew || !d_work) return fail(RAMSES_AMD_EINVAL, "NULL device pointer");
+  if (d_uold == d_unew) return fail(RAMSES_AMD_EINVAL, "uold and unew must be distinct buffers");
+  if (!(dx > 0.0) || !(dt >= 0.0)) return fail(RAMSES_AMD_EINVAL, "dx must be > 0 and dt >= 0");
+  if (work_bytes < ramses_amd_mhd_workspace_bytes(nx, ny, nz)) return fail(RAMSES_AMD_EINVAL, "MHD sweep: workspace too small (ramses_amd_mhd_workspace_bytes)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long N = (long)nx * ny * nz;
   A.uold = d_uold; A.unew = d_unew;
@@ -574,13 +597,13 @@ int MHD_BRICK_FN(const ramses_amd_mhd_params *p, int nx, int ny, int nz, const d
   const char *ef = getenv("RAMSES_AMD_MHD_FUSED");
   const bool fused = !(ef && ef[0] == '0');
   if (!fused) {
-    hipLaunchKernelGGL(mhd_prim_kernel, dim3(grid_for(N, 256)), dim3(256), 0, s, A);
-    hipLaunchKernelGGL(mhd_efield_kernel, dim3(grid_for(N, 256)), dim3(256), 0, s, A);
+    hipLaunchKernelGGL(mhd_prim_kernel, dim3(grid_for(N, MAX_GRID)), dim3(256), 0, s, A);
+    hipLaunchKernelGGL(mhd_efield_kernel, dim3(grid_for(N, MAX_GRID)), dim3(256), 0, s, A);
   }
   // (the stencil kernels: one cell per thread in the XCD-slab order of mhd_cell_of)
   const CellMap cm{nx, ny, nz, (nz + 7) / 8};
   auto remap_grid = [&](int tpb) { return dim3((unsigned)(8 * ((cm.slab_cells(0) + tpb - 1) / tpb))); };
-  if (remap_grid(128).x > 0x7fffffffu / 2) return failf(RAMSES_AMD_EUNSUPPORTED, "MHD sweep: level too large for one launch");
+  if (remap_grid(128).x > 0x7fffffffu / 2) return fail(RAMSES_AMD_EUNSUPPORTED, "MHD sweep: level too large for one launch");
   if (fused) {
     const int ntx = (nx + FT_X - 1) / FT_X, nty = (ny + FT_Y - 1) / FT_Y, ntz = (nz + FT_Z - 1) / FT_Z;
     const dim3 fg((unsigned)((long)ntx * nty * ntz)), fb(FT_X * FT_Y * FT_Z);
@@ -612,7 +635,7 @@ int MHD_BRICK_FN(const ramses_amd_mhd_params *p, int nx, int ny, int nz, const d
   int bad = 0;
   HCHK(hipMemcpyAsync(&bad, A.bad, sizeof(int), hipMemcpyDeviceToHost, s), "D2H");
   HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return failf(RAMSES_AMD_EINVAL, "MHD sweep: %d right-face fields differ from the neighbour's left-face field (uold(:,nvar+1:nvar+3) vs uold(:,6:8))", bad);
+  if (bad) return fail(RAMSES_AMD_EINVAL, "MHD sweep: %d right-face fields differ from the neighbour's left-face field (uold(:,nvar+1:nvar+3) vs uold(:,6:8))", bad);
   return 0;
 }
 
@@ -623,59 +646,20 @@ int MHD_BRICK_FN(const ramses_amd_mhd_params *p, int nx, int ny, int nz, const d
 int ramses_amd_mhd_godunov_fine_f90(const ramses_amd_mhd_params *p, int ilevel, int ngrid, const int *igrid, const double *xg,
                                     int64_t ngridmax, int64_t ncoarse, int nx_loc, const double *uold, double *unew, double dx,
                                     double dt) {
-  if (!igrid || !xg || !uold || !unew) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (nx_loc != 1) return failf(RAMSES_AMD_EUNSUPPORTED, "MHD sweep on the device needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
-  if (ilevel < 2 || ilevel > 10) return failf(RAMSES_AMD_EINVAL, "level out of range");
-  const int n = 1 << ilevel;
-  const long N = (long)n * n * n;
-  if ((long)ngrid * 8 != N) return failf(RAMSES_AMD_EUNSUPPORTED, "level %d is not fully refined on this rank (ngrid=%d)", ilevel, ngrid);
-  const long ncell = ncoarse + 8 * ngridmax;
-  struct DBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-      if (bytes <= cap && p) return hipSuccess;
-      if (p) (void)hipFree(p);
-      p = nullptr; cap = 0;
-      hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-      if (e == hipSuccess) cap = bytes;
-      return e;
-    }
-  };
-  static DBuf b_vec, b_old, b_new, b_work, b_ig, b_xg, b_org, b_flag;
+  if (!unew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  int n = 0;
+  if (int rc = level_check("MHD sweep on the device", ilevel, ngrid, igrid, xg, nx_loc, uold, &n)) return rc;
+  static LevelBufs B;
   hipStream_t s = nullptr;
-  const size_t wb = (size_t)ramses_amd_mhd_workspace_bytes(n, n, n);
-  HCHK(b_vec.ensure(sizeof(double) * NF * ncell), "hipMalloc cell vectors");
-  HCHK(b_old.ensure(sizeof(double) * NF * N), "hipMalloc brick");
-  HCHK(b_new.ensure(sizeof(double) * NF * N), "hipMalloc brick");
-  HCHK(b_work.ensure(wb), "hipMalloc workspace");
-  HCHK(b_org.ensure(sizeof(long) * ngrid), "hipMalloc octorg");
-  HCHK(b_ig.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
-  HCHK(b_xg.ensure(sizeof(double) * 3 * ngridmax), "hipMalloc xg");
-  HCHK(b_flag.ensure(sizeof(int)), "hipMalloc flag");
-  void *d_vec = b_vec.p, *d_old = b_old.p, *d_new = b_new.p, *d_work = b_work.p, *d_ig = b_ig.p, *d_xg = b_xg.p, *d_org = b_org.p, *d_flag = b_flag.p;
-  HCHK(hipMemcpyAsync(d_vec, uold, sizeof(double) * NF * ncell, hipMemcpyHostToDevice, s), "H2D uold");
-  HCHK(hipMemcpyAsync(d_ig, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
-  HCHK(hipMemcpyAsync(d_xg, xg, sizeof(double) * 3 * ngridmax, hipMemcpyHostToDevice, s), "H2D xg");
-  HCHK(hipMemsetAsync(d_flag, 0, sizeof(int), s), "memset");
-  const double skip[3] = {0.0, 0.0, 0.0};
-  HCHK(launch_oct_origin((const int *)d_ig, (const double *)d_xg, ngridmax, ngrid, n, skip, (long *)d_org, (int *)d_flag, s), "oct origin launch");
-  int bad = 0;
-  HCHK(hipMemcpyAsync(&bad, d_flag, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
-  HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return failf(RAMSES_AMD_EINVAL, "%d octs of level %d do not sit on the level lattice", bad, ilevel);
-  PackArgs PA;
-  PA.igrid = (const int *)d_ig; PA.octorg = (const long *)d_org;
-  PA.ngrid = ngrid; PA.n = n; PA.nvar = NF;
-  PA.ncoarse = ncoarse; PA.ngridmax = ngridmax; PA.ncell = ncell; PA.pitch_var = N;
-  PA.brick = (double *)d_old; PA.cellvec = (double *)d_vec;
-  HCHK(launch_oct_copy(PA, true, s), "gather launch");
-  if (int rc = ramses_amd_mhd_godunov_brick(p, n, n, n, (const double *)d_old, (double *)d_new, dx, dt, d_work, (int64_t)wb, s)) return rc;
+  if (int rc = level_upload(B, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, n, uold, s)) return rc;
+  if (int rc = ramses_amd_mhd_godunov_brick(p, n, n, n, B.cur.as<double>(), B.nxt.as<double>(), dx, dt, B.work.p, (int64_t)B.work.cap, s)) return rc;
   // unew of the level's cells: the other cells of the host array keep their values (H2D of unew first)
-  HCHK(hipMemcpyAsync(d_vec, unew, sizeof(double) * NF * ncell, hipMemcpyHostToDevice, s), "H2D unew");
-  PA.brick = (double *)d_new;
+  const size_t vec_bytes = sizeof(double) * NF * (ncoarse + 8 * ngridmax);
+  HCHK(hipMemcpyAsync(B.vec.p, unew, vec_bytes, hipMemcpyHostToDevice, s), "H2D unew");
+  PackArgs PA = level_pack(B, ngrid, n, ncoarse, ngridmax);
+  PA.brick = B.nxt.as<double>();
   HCHK(launch_oct_copy(PA, false, s), "scatter launch");
-  HCHK(hipMemcpyAsync(unew, d_vec, sizeof(double) * NF * ncell, hipMemcpyDeviceToHost, s), "D2H unew");
+  HCHK(hipMemcpyAsync(unew, B.vec.p, vec_bytes, hipMemcpyDeviceToHost, s), "D2H unew");
   HCHK(hipStreamSynchronize(s), "sync");
   return 0;
 }
@@ -686,67 +670,27 @@ int ramses_amd_mhd_godunov_fine_f90(const ramses_amd_mhd_params *p, int ilevel, 
 // host array uold is stale from the first set_uold until ramses_amd_mhd_resident_sync_host_f90 (backup_hydro).  Mirrors
 // ramses_amd_resident_* of the hydro solver (capi_host.hip). ---------------------------------------------------------
 namespace {
-struct MhdBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-};
-struct MhdResident {
+struct MhdResident : LevelBufs {
   bool valid = false, host_stale = false, new_ready = false;
   int level = 0, ngrid = 0, n = 0;
   long ncell = 0, ncoarse = 0, ngridmax = 0;
   const double *h_uold = nullptr;
-  MhdBuf vec, cur, nxt, work, ig, xg, org, flag, red;
+  DevBuf red;
 };
 MhdResident g_mres;
 
 int mres_ensure(int ilevel, int ngrid, const int *igrid, const double *xg, int64_t ngridmax, int64_t ncoarse, int nx_loc,
                 const double *uold) {
   MhdResident &R = g_mres;
-  if (!igrid || !xg || !uold) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (nx_loc != 1) return failf(RAMSES_AMD_EUNSUPPORTED, "MHD residency needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
-  if (ilevel < 2 || ilevel > 10) return failf(RAMSES_AMD_EINVAL, "level out of range");
-  const int n = 1 << ilevel;
-  const long N = (long)n * n * n;
-  if ((long)ngrid * 8 != N) return failf(RAMSES_AMD_EUNSUPPORTED, "level %d is not fully refined on this rank (ngrid=%d)", ilevel, ngrid);
+  int n = 0;
+  if (int rc = level_check("MHD residency", ilevel, ngrid, igrid, xg, nx_loc, uold, &n)) return rc;
   const long ncell = ncoarse + 8 * ngridmax;
   if (R.valid && R.level == ilevel && R.ngrid == ngrid && R.h_uold == uold && R.ncell == ncell) return 0;
   if (R.valid && R.host_stale)
-    return failf(RAMSES_AMD_EINVAL, "MHD residency: level %d is resident and the host array is stale; ramses_amd_mhd_resident_sync_host_f90 first", R.level);
+    return fail(RAMSES_AMD_EINVAL, "MHD residency: level %d is resident and the host array is stale; ramses_amd_mhd_resident_sync_host_f90 first", R.level);
   R.valid = false;
-  hipStream_t s = nullptr;
-  HCHK(R.vec.ensure(sizeof(double) * NF * ncell), "hipMalloc cell vectors");
-  HCHK(R.cur.ensure(sizeof(double) * NF * N), "hipMalloc brick");
-  HCHK(R.nxt.ensure(sizeof(double) * NF * N), "hipMalloc brick");
-  HCHK(R.work.ensure((size_t)ramses_amd_mhd_workspace_bytes(n, n, n)), "hipMalloc workspace");
-  HCHK(R.org.ensure(sizeof(long) * ngrid), "hipMalloc octorg");
-  HCHK(R.ig.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
-  HCHK(R.xg.ensure(sizeof(double) * 3 * ngridmax), "hipMalloc xg");
-  HCHK(R.flag.ensure(sizeof(int)), "hipMalloc flag");
   HCHK(R.red.ensure(sizeof(double) * (COUR_BLOCKS * 5 + 8)), "hipMalloc reduction");
-  HCHK(hipMemcpyAsync(R.vec.p, uold, sizeof(double) * NF * ncell, hipMemcpyHostToDevice, s), "H2D uold");
-  HCHK(hipMemcpyAsync(R.ig.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
-  HCHK(hipMemcpyAsync(R.xg.p, xg, sizeof(double) * 3 * ngridmax, hipMemcpyHostToDevice, s), "H2D xg");
-  HCHK(hipMemsetAsync(R.flag.p, 0, sizeof(int), s), "memset");
-  const double skip[3] = {0.0, 0.0, 0.0};
-  HCHK(launch_oct_origin((const int *)R.ig.p, (const double *)R.xg.p, ngridmax, ngrid, n, skip, (long *)R.org.p, (int *)R.flag.p, s), "oct origin launch");
-  int bad = 0;
-  HCHK(hipMemcpyAsync(&bad, R.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
-  HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return failf(RAMSES_AMD_EINVAL, "%d octs of level %d do not sit on the level lattice", bad, ilevel);
-  PackArgs PA;
-  PA.igrid = (const int *)R.ig.p; PA.octorg = (const long *)R.org.p;
-  PA.ngrid = ngrid; PA.n = n; PA.nvar = NF;
-  PA.ncoarse = ncoarse; PA.ngridmax = ngridmax; PA.ncell = ncell; PA.pitch_var = N;
-  PA.brick = (double *)R.cur.p; PA.cellvec = (double *)R.vec.p;
-  HCHK(launch_oct_copy(PA, true, s), "gather launch");
+  if (int rc = level_upload(R, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, n, uold, nullptr)) return rc;
   R.valid = true; R.host_stale = false; R.new_ready = false;
   R.level = ilevel; R.ngrid = ngrid; R.n = n; R.ncell = ncell; R.ncoarse = ncoarse; R.ngridmax = ngridmax; R.h_uold = uold;
   return 0;
@@ -760,13 +704,13 @@ int ramses_amd_mhd_resident_active(void) { return g_mres.valid ? 1 : 0; }
 int ramses_amd_mhd_resident_courant_f90(const ramses_amd_mhd_params *p, int ilevel, int ngrid, const int *igrid, const double *xg,
                                         int64_t ngridmax, int64_t ncoarse, int nx_loc, const double *uold, double dx, double dt_in,
                                         double courant_factor, double *out5) {
-  if (!out5) return failf(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!out5) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   MhdArgs A;
   if (int rc = make_const(p, A.P)) return rc;
   if (int rc = mres_ensure(ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold)) return rc;
   MhdResident &R = g_mres;
-  if (R.new_ready) return failf(RAMSES_AMD_EINVAL, "courant_fine between godunov_fine and set_uold");
-  if (!(dx > 0.0) || !(courant_factor > 0.0)) return failf(RAMSES_AMD_EINVAL, "dx and courant_factor must be > 0");
+  if (R.new_ready) return fail(RAMSES_AMD_EINVAL, "courant_fine between godunov_fine and set_uold");
+  if (!(dx > 0.0) || !(courant_factor > 0.0)) return fail(RAMSES_AMD_EINVAL, "dx and courant_factor must be > 0");
   const long N = (long)R.n * R.n * R.n;
   A.uold = (const double *)R.cur.p; A.unew = nullptr;
   A.nx = A.ny = A.nz = R.n; A.ncell = N; A.dx = dx; A.dt = 0.0;
@@ -798,8 +742,8 @@ int ramses_amd_mhd_resident_godunov_f90(const ramses_amd_mhd_params *p, int ilev
 // set_uold(ilevel) (mhd/godunov_fine.f90:185-281 without gravity / pressure_fix / passive scalars): the bricks swap roles
 int ramses_amd_mhd_resident_set_uold_f90(int ilevel) {
   MhdResident &R = g_mres;
-  if (!R.valid || R.level != ilevel) return failf(RAMSES_AMD_EINVAL, "set_uold: level %d is not resident", ilevel);
-  if (!R.new_ready) return failf(RAMSES_AMD_EINVAL, "set_uold without a godunov_fine before it");
+  if (!R.valid || R.level != ilevel) return fail(RAMSES_AMD_EINVAL, "set_uold: level %d is not resident", ilevel);
+  if (!R.new_ready) return fail(RAMSES_AMD_EINVAL, "set_uold without a godunov_fine before it");
   std::swap(R.cur, R.nxt);
   R.new_ready = false;
   R.host_stale = true;
@@ -811,15 +755,9 @@ int ramses_amd_mhd_resident_set_uold_f90(int ilevel) {
 int ramses_amd_mhd_resident_sync_host_f90(double *uold) {
   MhdResident &R = g_mres;
   if (!R.valid || !R.host_stale) return 0;
-  if (uold != R.h_uold) return failf(RAMSES_AMD_EINVAL, "sync: not the array the level was loaded from");
-  if (R.new_ready) return failf(RAMSES_AMD_EINVAL, "sync between godunov_fine and set_uold");
-  const long N = (long)R.n * R.n * R.n;
-  PackArgs PA;
-  PA.igrid = (const int *)R.ig.p; PA.octorg = (const long *)R.org.p;
-  PA.ngrid = R.ngrid; PA.n = R.n; PA.nvar = NF;
-  PA.ncoarse = R.ncoarse; PA.ngridmax = R.ngridmax; PA.ncell = R.ncell; PA.pitch_var = N;
-  PA.brick = (double *)R.cur.p; PA.cellvec = (double *)R.vec.p;
-  HCHK(launch_oct_copy(PA, false, nullptr), "scatter launch");
+  if (uold != R.h_uold) return fail(RAMSES_AMD_EINVAL, "sync: not the array the level was loaded from");
+  if (R.new_ready) return fail(RAMSES_AMD_EINVAL, "sync between godunov_fine and set_uold");
+  HCHK(launch_oct_copy(level_pack(R, R.ngrid, R.n, R.ncoarse, R.ngridmax), false, nullptr), "scatter launch");
   HCHK(hipMemcpy(uold, R.vec.p, sizeof(double) * NF * R.ncell, hipMemcpyDeviceToHost), "D2H uold");
   R.host_stale = false;
   return 0;
@@ -827,7 +765,7 @@ int ramses_amd_mhd_resident_sync_host_f90(double *uold) {
 
 int ramses_amd_mhd_resident_invalidate(void) {
   MhdResident &R = g_mres;
-  if (R.valid && R.host_stale) return failf(RAMSES_AMD_EINVAL, "invalidate: the host array is stale; sync first");
+  if (R.valid && R.host_stale) return fail(RAMSES_AMD_EINVAL, "invalidate: the host array is stale; sync first");
   R.valid = false;
   return 0;
 }

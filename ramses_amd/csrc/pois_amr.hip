@@ -23,57 +23,19 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../../include/ramses_amd.h"
+#include "host_util.hpp"
 #include "mg_amr_args.hpp"
 #include "misc_args.hpp"
 
 using namespace ramses_amd;
 
-extern "C" int ramses_amd_set_error(int code, const char *msg);
-static int failf(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return ramses_amd_set_error(code, buf);
-}
-#define HCHK(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failf(RAMSES_AMD_EHIP, "%s: %s", what, hipGetErrorString(e_)); } while (0)
-
 namespace {
-
-struct Buf {
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    if (bytes == 0) bytes = 8;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
-struct PinBuf {     // page-locked staging area
-  void *p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-    if (bytes == 0) bytes = 8;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
 
 // same-level neighbour of cell c (1-based AMR index) in direction dir (-x,+x,-y,+y,-z,+z); 0 if its oct does
 // not exist.  The single coarse cell of a periodic box is its own neighbour.
@@ -334,16 +296,9 @@ __global__ void vec_scatter_kernel(double *vec, const double *in, const int *igr
     vec[ncoarse + (long)(c / ngrid) * ngridmax + igrid[c % ngrid] - 1] = in[c];
 }
 
-inline int grid_for(long work, int cap = 4096) {
-  long g = (work + 255) / 256;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
-}
-
 struct Level {
   int ngrid = 0;
-  Buf igrid, u1, u2, u3, u4, scan;
+  DevBuf igrid, u1, u2, u3, u4, scan;
   MgAmrLevel view() {
     MgAmrLevel L;
     L.ngrid = ngrid; L.nact = ngrid; L.igrid = igrid.as<int>();
@@ -367,17 +322,17 @@ struct PoisAmr {
   bool tree_valid = false;
   int epoch = -1;
   long ncoarse = 0, ngridmax = 0, ncell = 0;
-  Buf son, nbor, father, lookup;
+  DevBuf son, nbor, father, lookup;
   // the reference's cell vectors (AMR layout)
-  Buf phi, phi_old, rho, f;
+  DevBuf phi, phi_old, rho, f;
   // what the device copies hold: phi and rho of level `have_level` (ngrid `have_ngrid`), and, if have_above, phi and
   // phi_old of the level above it -- left there by the last multigrid solve for force_fine
   int have_level = 0, have_ngrid = 0, have_epoch = -1;
   bool have_above = false;
-  Buf fpack, leaf, diag;
-  Buf igrid_c;                      // octs of the level above (whose phi feeds the interpolation)
+  DevBuf fpack, leaf, diag;
+  DevBuf igrid_c;                      // octs of the level above (whose phi feeds the interpolation)
   Level lev[32];
-  Buf count, any, partial, norm, pack;
+  DevBuf count, any, partial, norm, pack;
   PinBuf stage;
   int levelmin_mg = 1;
   MgAmrTree tree() {
@@ -427,8 +382,8 @@ extern "C" {
 // the tree arrays son(1:ncell), nbor(1:ngridmax,1:6), father(1:ngridmax); sent only when `epoch` (a counter the
 // caller advances whenever refine_fine / load_balance may have changed the tree) differs from the cached one
 int ramses_amd_poisamr_tree(int epoch, int64_t ngridmax, int64_t ncoarse, const int *son, const int *nbor, const int *father) {
-  if (!son || !nbor || !father) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (ngridmax < 1 || ncoarse != 1) return failf(RAMSES_AMD_EUNSUPPORTED, "the device AMR multigrid driver covers a box of one coarse cell (nx=ny=nz=1)");
+  if (!son || !nbor || !father) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (ngridmax < 1 || ncoarse != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "the device AMR multigrid driver covers a box of one coarse cell (nx=ny=nz=1)");
   PoisAmr &P = g_pa;
   if (P.tree_valid && P.epoch == epoch && P.ngridmax == ngridmax && P.ncoarse == ncoarse) return 0;
   P.tree_valid = false;
@@ -458,10 +413,10 @@ int ramses_amd_poisamr_multigrid(int ilevel, int ngrid, const int *igrid, int ng
                                  int interp, double epsilon, int ngs_fine, int ngs_coarse, int ncycles_coarse_safe, int *safe_mode,
                                  int *iters, double *err_out) {
   PoisAmr &P = g_pa;
-  if (!P.tree_valid) return failf(RAMSES_AMD_EINVAL, "poisamr_multigrid: no tree (ramses_amd_poisamr_tree)");
-  if (!igrid || !phi || !phi_old || !rho || !flag2 || !safe_mode || !iters || !err_out) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (ilevel < 2 || ilevel > 30 || ngrid < 1 || ngrid > P.ngridmax) return failf(RAMSES_AMD_EINVAL, "bad level %d / ngrid %d", ilevel, ngrid);
-  if (interp && (!igrid_c || ngrid_c < 1)) return failf(RAMSES_AMD_EINVAL, "the level above is empty");
+  if (!P.tree_valid) return fail(RAMSES_AMD_EINVAL, "poisamr_multigrid: no tree (ramses_amd_poisamr_tree)");
+  if (!igrid || !phi || !phi_old || !rho || !flag2 || !safe_mode || !iters || !err_out) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (ilevel < 2 || ilevel > 30 || ngrid < 1 || ngrid > P.ngridmax) return fail(RAMSES_AMD_EINVAL, "bad level %d / ngrid %d", ilevel, ngrid);
+  if (interp && (!igrid_c || ngrid_c < 1)) return fail(RAMSES_AMD_EINVAL, "the level above is empty");
   const int MAXITER = 10;
   const double SAFE_FACTOR = 0.5;
   hipStream_t s = nullptr;
@@ -518,7 +473,7 @@ int ramses_amd_poisamr_multigrid(int ilevel, int ngrid, const int *igrid, int ng
     int n = 0;
     HCHK(hipMemcpyAsync(&n, P.count.as<int>() + l, sizeof(int), hipMemcpyDeviceToHost, s), "D2H count");
     HCHK(hipStreamSynchronize(s), "sync");
-    if (n < 1 || n > cap) return failf(RAMSES_AMD_EINVAL, "multigrid level %d: %d octs found (capacity %ld): tree inconsistent", l, n, cap);
+    if (n < 1 || n > cap) return fail(RAMSES_AMD_EINVAL, "multigrid level %d: %d octs found (capacity %ld): tree inconsistent", l, n, cap);
     C.ngrid = n;
     HCHK(C.ensure(n), "hipMalloc level");
     hipLaunchKernelGGL(set_lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, s, C.igrid.as<int>(), n, P.lookup.as<int>(), -1);
@@ -662,7 +617,7 @@ int ramses_amd_poisamr_force(int ilevel, int ngrid, const int *igrid, int ngrid_
 int ramses_amd_poisamr_force_mpi(int ilevel, int ngrid_own, int ngrid_all, const int *igrid_all, int ngrid_c_all, const int *igrid_c_all,
                                  const double *phi, const double *phi_old, const double *rho, double *f, double tfrac, int interp,
                                  double fact, double *diag) {
-  if (ngrid_own < 0 || ngrid_own > ngrid_all) return failf(RAMSES_AMD_EINVAL, "poisamr_force_mpi: bad own / total oct counts");
+  if (ngrid_own < 0 || ngrid_own > ngrid_all) return fail(RAMSES_AMD_EINVAL, "poisamr_force_mpi: bad own / total oct counts");
   if (ngrid_own == 0) { if (diag) { diag[0] = 0.0; diag[1] = 0.0; } return 0; }
   return poisamr_force_impl(ilevel, ngrid_own, ngrid_all, igrid_all, ngrid_c_all, igrid_c_all, phi, phi_old, rho, f, tfrac, interp, 0, fact, diag);
 }
@@ -675,7 +630,7 @@ static bool g_force_to_resident = false;
 int ramses_amd_poisamr_force_mpi_resident(int ilevel, int ngrid_own, int ngrid_all, const int *igrid_all, int ngrid_c_all, const int *igrid_c_all,
                                           const double *phi, const double *phi_old, const double *rho, double tfrac, int interp, double fact,
                                           double *diag) {
-  if (ngrid_own < 0 || ngrid_own > ngrid_all) return failf(RAMSES_AMD_EINVAL, "poisamr_force_mpi: bad own / total oct counts");
+  if (ngrid_own < 0 || ngrid_own > ngrid_all) return fail(RAMSES_AMD_EINVAL, "poisamr_force_mpi: bad own / total oct counts");
   if (ngrid_own == 0) { if (diag) { diag[0] = 0.0; diag[1] = 0.0; } return 0; }
   g_force_to_resident = true;
   double dummy = 0.0;
@@ -687,10 +642,10 @@ static int poisamr_force_impl(int ilevel, int ngrid_own, int ngrid, const int *i
                               const double *phi_old, const double *rho, double *f, double tfrac, int interp, int fresh, double fact,
                               double *diag) {
   PoisAmr &P = g_pa;
-  if (!P.tree_valid) return failf(RAMSES_AMD_EINVAL, "poisamr_force: no tree (ramses_amd_poisamr_tree)");
-  if (!igrid || !phi || !phi_old || !rho || !f || !diag) return failf(RAMSES_AMD_EINVAL, "NULL argument");
-  if (ilevel < 2 || ilevel > 30 || ngrid < 1 || ngrid > P.ngridmax) return failf(RAMSES_AMD_EINVAL, "bad level %d / ngrid %d", ilevel, ngrid);
-  if (interp && (!igrid_c || ngrid_c < 1)) return failf(RAMSES_AMD_EINVAL, "the level above is empty");
+  if (!P.tree_valid) return fail(RAMSES_AMD_EINVAL, "poisamr_force: no tree (ramses_amd_poisamr_tree)");
+  if (!igrid || !phi || !phi_old || !rho || !f || !diag) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (ilevel < 2 || ilevel > 30 || ngrid < 1 || ngrid > P.ngridmax) return fail(RAMSES_AMD_EINVAL, "bad level %d / ngrid %d", ilevel, ngrid);
+  if (interp && (!igrid_c || ngrid_c < 1)) return fail(RAMSES_AMD_EINVAL, "the level above is empty");
   hipStream_t s = nullptr;
   const long ncoarse = P.ncoarse, ngridmax = P.ngridmax;
   const long nf = 8L * ngrid, nc = interp ? 8L * ngrid_c : 0;
