@@ -34,6 +34,7 @@
 #include "rho_args.hpp"
 #include "sweep_args.hpp"
 #include "capi_shared.hpp"
+#include "peer_exchange.hpp"
 
 using namespace ramses_amd;
 
@@ -780,10 +781,7 @@ struct LevelPlan {
 
 struct AmrRes {
   std::vector<CommLevel> comm;                 // by level
-  Buf sendbuf, recvbuf;
-  PinBuf h_send, h_recv;
-  std::vector<int64_t> f_send_off, f_recv_off; // [ncpu+1], doubles, of the exchange that is under way
-  int halo_level = 0, halo_dir = -1;           // the exchange halo_stage_out has opened (0: none)
+  PeerExchange halo;                           // the virtual-boundary exchange under way, tagged (level, 0, dir)
   bool valid = false;
   int nvar = 0;
   long ncell = 0, ncoarse = 0, ngridmax = 0;   // of the DEVICE's cell vectors (ngridmax = map.ngd)
@@ -2010,18 +2008,8 @@ int ramses_amd_amrres_comm_set(int ilevel, int epoch, int ncpu, const int *em_n,
   CommLevel &L = R.comm[ilevel];
   L.epoch = -1;
   L.ncpu = ncpu;
-  L.em_first.assign((size_t)ncpu + 1, 0); L.rc_first.assign((size_t)ncpu + 1, 0);
-  for (int c = 0; c < ncpu; c++) {
-    if (em_n[c] < 0 || rc_n[c] < 0) return fail(RAMSES_AMD_EINVAL, "comm_set: negative list length");
-    L.em_first[c + 1] = L.em_first[c] + em_n[c];
-    L.rc_first[c + 1] = L.rc_first[c] + rc_n[c];
-  }
-  const int nem = L.em_first[ncpu], nrc = L.rc_first[ncpu];
-  if ((nem > 0 && !em_ig) || (nrc > 0 && !rc_ig)) return fail(RAMSES_AMD_EINVAL, "comm_set: NULL list");
-  HCHK(L.em_ig.ensure(sizeof(int) * (size_t)(nem > 0 ? nem : 1)), "hipMalloc"); HCHK(L.rc_ig.ensure(sizeof(int) * (size_t)(nrc > 0 ? nrc : 1)), "hipMalloc");
-  HCHK(L.em_raw.ensure(sizeof(int) * (size_t)(nem > 0 ? nem : 1)), "hipMalloc"); HCHK(L.rc_raw.ensure(sizeof(int) * (size_t)(nrc > 0 ? nrc : 1)), "hipMalloc");
-  if (nem > 0) HCHK(hipMemcpy(L.em_raw.p, em_ig, sizeof(int) * (size_t)nem, hipMemcpyHostToDevice), "H2D emission list");
-  if (nrc > 0) HCHK(hipMemcpy(L.rc_raw.p, rc_ig, sizeof(int) * (size_t)nrc, hipMemcpyHostToDevice), "H2D reception list");
+  if (int rc = peer_lists("comm_set", ncpu, em_n, em_ig, rc_n, rc_ig, L.em_first, L.rc_first, L.em_raw, L.rc_raw)) return rc;
+  HCHK(L.em_ig.ensure(L.em_raw.cap), "hipMalloc"); HCHK(L.rc_ig.ensure(L.rc_raw.cap), "hipMalloc");      // the translated twins
   L.serial = -1;             // translated into device indices by the exchange that uses them (comm_of)
   L.epoch = epoch;
   return 0;
@@ -2072,19 +2060,16 @@ int halo_spec(AmrRes &R, int dir, HaloSpec &S) {
   }
   return fail(RAMSES_AMD_EINVAL, "halo: bad direction %d", dir);
 }
-// gather every peer's message into sendbuf; fills the [ncpu+1] offset tables (in doubles)
+// plan the exchange and gather every peer's message into its sendbuf
 int halo_pack(AmrRes &R, CommLevel &L, const HaloSpec &S) {
   const std::vector<int> &sf = S.reverse ? L.rc_first : L.em_first, &rf = S.reverse ? L.em_first : L.rc_first;
   const int *sig = S.reverse ? L.rc_ig.as<int>() : L.em_ig.as<int>();
   const size_t per = (size_t)8 * S.ncomp;
-  R.f_send_off.assign((size_t)L.ncpu + 1, 0); R.f_recv_off.assign((size_t)L.ncpu + 1, 0);
-  for (int c = 0; c <= L.ncpu; c++) { R.f_send_off[c] = (int64_t)(per * sf[c]); R.f_recv_off[c] = (int64_t)(per * rf[c]); }
-  HCHK(R.sendbuf.ensure(sizeof(double) * per * (size_t)(sf[L.ncpu] > 0 ? sf[L.ncpu] : 1)), "hipMalloc sendbuf");
-  HCHK(R.recvbuf.ensure(sizeof(double) * per * (size_t)(rf[L.ncpu] > 0 ? rf[L.ncpu] : 1)), "hipMalloc recvbuf");
+  if (int rc = R.halo.plan(L.ncpu, sf.data(), rf.data(), per)) return rc;
   for (int c = 0; c < L.ncpu; c++) {
     const int n = sf[c + 1] - sf[c];
     if (n <= 0) continue;
-    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.sendbuf.as<double>() + per * sf[c],
+    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.halo.sendbuf.as<double>() + per * sf[c],
                        sig + sf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
   }
   HCHK(hipGetLastError(), "halo pack launch");
@@ -2098,9 +2083,9 @@ int halo_unpack(AmrRes &R, CommLevel &L, const HaloSpec &S) {
   for (int c = 0; c < L.ncpu; c++) {
     const int n = rf[c + 1] - rf[c];
     if (n <= 0) continue;
-    if (S.reverse) hipLaunchKernelGGL(lvl_acc_comp_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.recvbuf.as<double>() + per * rf[c],
+    if (S.reverse) hipLaunchKernelGGL(lvl_acc_comp_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.halo.recvbuf.as<double>() + per * rf[c],
                                       rig + rf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
-    else hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.recvbuf.as<double>() + per * rf[c],
+    else hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.halo.recvbuf.as<double>() + per * rf[c],
                             rig + rf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
   }
   HCHK(hipGetLastError(), "halo unpack launch");
@@ -2191,27 +2176,15 @@ int ramses_amd_amrres_zero_unew_virtual(int ilevel) {
 }
 
 // One exchange over RCCL: pack, one grouped send/recv (a message per peer), unpack / accumulate; asynchronous
-extern "C" int ramses_amd_rccl_exchange(int npeer, const int *peer, const double *d_send, const int64_t *send_off, const int64_t *send_cnt,
-                                        double *d_recv, const int64_t *recv_off, const int64_t *recv_cnt, void *stream);
 int ramses_amd_amrres_halo_rccl(int ilevel, int dir, int myid) {
   AmrRes &R = g_ar;
   CommLevel *L;
   HaloSpec S;
+  (void)myid;      // (the rank may be its own peer: PeerExchange::rccl)
   if (int rc = comm_of(R, ilevel, L)) return rc;
   if (int rc = halo_spec(R, dir, S)) return rc;
   if (int rc = halo_pack(R, *L, S)) return rc;
-  std::vector<int> peer;
-  std::vector<int64_t> so, sc, ro, rcn;
-  for (int c = 0; c < L->ncpu; c++) {
-    const int64_t ns = R.f_send_off[c + 1] - R.f_send_off[c], nr = R.f_recv_off[c + 1] - R.f_recv_off[c];
-    if (ns == 0 && nr == 0) continue;
-    // c == myid - 1 (a communicator of the rank with itself) is legal: the grouped exchange matches the send to self with
-    // the receive from self; build_comm never produces one, the single-rank execution test of the transport does
-    (void)myid;
-    peer.push_back(c); so.push_back(R.f_send_off[c]); sc.push_back(ns); ro.push_back(R.f_recv_off[c]); rcn.push_back(nr);
-  }
-  if (int rc = ramses_amd_rccl_exchange((int)peer.size(), peer.data(), R.sendbuf.as<double>(), so.data(), sc.data(), R.recvbuf.as<double>(),
-                                        ro.data(), rcn.data(), nullptr)) return rc;
+  if (int rc = R.halo.rccl()) return rc;
   return halo_unpack(R, *L, S);
 }
 
@@ -2222,19 +2195,10 @@ int ramses_amd_amrres_halo_stage_out(int ilevel, int dir, int ncpu, int64_t *h_s
   AmrRes &R = g_ar;
   CommLevel *L;
   HaloSpec S;
-  if (!h_send_addr || !h_recv_addr || !send_off || !recv_off) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = comm_of(R, ilevel, L)) return rc;
-  if (ncpu != L->ncpu) return fail(RAMSES_AMD_EINVAL, "ncpu mismatch");
   if (int rc = halo_spec(R, dir, S)) return rc;
   if (int rc = halo_pack(R, *L, S)) return rc;
-  const size_t ns = (size_t)R.f_send_off[ncpu], nr = (size_t)R.f_recv_off[ncpu];
-  HCHK(R.h_send.ensure(sizeof(double) * (ns > 0 ? ns : 1)), "hipHostMalloc"); HCHK(R.h_recv.ensure(sizeof(double) * (nr > 0 ? nr : 1)), "hipHostMalloc");
-  if (ns > 0) HCHK(hipMemcpyAsync(R.h_send.p, R.sendbuf.p, sizeof(double) * ns, hipMemcpyDeviceToHost, nullptr), "D2H halo");
-  HCHK(hipStreamSynchronize(nullptr), "sync");
-  *h_send_addr = (int64_t)(intptr_t)R.h_send.p; *h_recv_addr = (int64_t)(intptr_t)R.h_recv.p;
-  for (int c = 0; c <= ncpu; c++) { send_off[c] = R.f_send_off[c]; recv_off[c] = R.f_recv_off[c]; }
-  R.halo_level = ilevel; R.halo_dir = dir;
-  return 0;
+  return R.halo.stage_out(ilevel, 0, dir, ncpu, h_send_addr, h_recv_addr, send_off, recv_off);
 }
 int ramses_amd_amrres_halo_stage_in(int ilevel, int dir) {
   AmrRes &R = g_ar;
@@ -2242,12 +2206,8 @@ int ramses_amd_amrres_halo_stage_in(int ilevel, int dir) {
   HaloSpec S;
   if (int rc = comm_of(R, ilevel, L)) return rc;
   if (int rc = halo_spec(R, dir, S)) return rc;
-  if (R.halo_level != ilevel || R.halo_dir != dir || R.f_recv_off.size() != (size_t)L->ncpu + 1)
-    return fail(RAMSES_AMD_EINVAL, "halo_stage_in(level %d, dir %d) does not close the exchange halo_stage_out opened (level %d, dir %d)",
-                 ilevel, dir, R.halo_level, R.halo_dir);
-  R.halo_level = 0; R.halo_dir = -1;
-  const size_t nr = (size_t)R.f_recv_off[L->ncpu];
-  if (nr > 0) HCHK(hipMemcpyAsync(R.recvbuf.p, R.h_recv.p, sizeof(double) * nr, hipMemcpyHostToDevice, nullptr), "H2D halo");
+  if (int rc = R.halo.stage_in(ilevel, 0, dir, L->ncpu, "halo_stage_in(level %d, dir %d) does not close the exchange halo_stage_out opened (level %d, dir %d)",
+                               ilevel, dir, R.halo.tag[0], R.halo.tag[2])) return rc;
   return halo_unpack(R, *L, S);
 }
 

@@ -20,6 +20,7 @@
 #include "rho_args.hpp"
 #include "sweep_args.hpp"
 #include "capi_shared.hpp"
+#include "peer_exchange.hpp"
 
 using namespace ramses_amd;
 
@@ -50,11 +51,11 @@ struct MgAmrBlock {
   const int *h_f;             // f(1:ngrid*8, 1)
 };
 // the virtual boundaries of one level of the solve (several ranks): emission = positions in the rank's own part of the
-// layout, per peer; reception = the peer's block of the layout (rc_off octs in, rc_n octs long)
+// layout, per peer; reception = the peer's block of the layout (rc_base + rc_first[icpu-1] octs in)
 struct MgAmrComm {
   bool set = false;
-  int ncpu = 0;
-  std::vector<int> em_first, rc_off, rc_n;
+  int ncpu = 0, rc_base = 0;
+  std::vector<int> em_first, rc_first;        // [ncpu+1]
   DevBuf em_pos;
 };
 struct MgAmrDev {
@@ -75,12 +76,8 @@ struct MgAmrCtx {
   int ilevel = 0;
   long ncoarse = 0, ngridmax = 0, ncell = 0;
   DevBuf son, nbor, father, lookup, vec, ivec, partial, norm;
-  // halo exchanges of the solve: device message buffers, pinned host twins (host-MPI transport), the open exchange
-  DevBuf sendbuf, recvbuf, tmpidx;
-  void *h_send = nullptr, *h_recv = nullptr;
-  size_t h_send_cap = 0, h_recv_cap = 0;
-  std::vector<int64_t> send_off, recv_off;
-  int halo_level = 0, halo_comp = 0, halo_dir = -1;
+  PeerExchange halo;         // the halo exchanges of the solve, tagged (level, component, dir)
+  DevBuf tmpidx;
   // what crossed PCIe: [0] bytes of level arrays moved by the routines AFTER the first one of the solve uploaded them,
   // [1] number of such copies, [2] bytes of halo messages (host-MPI transport), [3] halo exchanges
   long long stats[4] = {0, 0, 0, 0};
@@ -182,7 +179,7 @@ int ramses_amd_mgamr_begin(int ilevel, int64_t ngridmax, int64_t ncoarse, const 
   const char *e = getenv("RAMSES_AMD_MG_SYNC");
   M.sync = (e && e[0] == '1') || g_mg_force_sync;
   M.open = true; M.ilevel = ilevel; M.ncoarse = ncoarse; M.ngridmax = ngridmax; M.ncell = ncoarse + 8 * ngridmax;
-  M.uploaded = false; M.halo_level = 0; M.halo_dir = -1;
+  M.uploaded = false; M.halo.close();
   for (int k = 0; k < 4; k++) M.stats[k] = 0;
   M.h_phi = phi; M.h_f = f; M.h_flag2 = flag2;
   for (int l = 0; l < 32; l++) { M.lev[l].ngrid = 0; M.lev[l].nact = 0; M.lev[l].filled = 0; M.lev[l].level = l; M.lev[l].blocks.clear(); M.lev[l].comm.set = false; }
@@ -405,15 +402,11 @@ int ramses_amd_mgamr_comm_set(int level, int ncpu, int myid, const int *em_n, co
   if (ncpu < 1 || myid < 1 || myid > ncpu || !em_n || !rc_n) return fail(RAMSES_AMD_EINVAL, "mgamr_comm_set: bad argument");
   MgAmrComm &Cm = D->comm;
   Cm.set = false; Cm.ncpu = ncpu;
-  Cm.em_first.assign((size_t)ncpu + 1, 0); Cm.rc_off.assign((size_t)ncpu, 0); Cm.rc_n.assign((size_t)ncpu, 0);
-  int off = D->nact;
-  for (int c = 0; c < ncpu; c++) {
-    if (em_n[c] < 0 || rc_n[c] < 0) return fail(RAMSES_AMD_EINVAL, "mgamr_comm_set: negative list length");
-    Cm.em_first[c + 1] = Cm.em_first[c] + em_n[c];
-    const int n = c == myid - 1 ? 0 : rc_n[c];
-    Cm.rc_off[c] = off; Cm.rc_n[c] = n;
-    off += n;
-  }
+  std::vector<int> rn(rc_n, rc_n + ncpu);
+  if (rn[myid - 1] > 0) rn[myid - 1] = 0;      // (the rank's own octs are the first block of the layout, not a reception block)
+  if (int rc = peer_prefix("mgamr_comm_set", ncpu, em_n, rn.data(), Cm.em_first, Cm.rc_first)) return rc;
+  Cm.rc_base = D->nact;
+  const int off = Cm.rc_base + Cm.rc_first[ncpu];
   if (off != D->ngrid) return fail(RAMSES_AMD_EINVAL, "mgamr_comm_set(level %d): own %d + reception octs = %d, the layout has %d", level, D->nact, off, D->ngrid);
   const int nem = Cm.em_first[ncpu];
   if (nem > 0 && !em_list) return fail(RAMSES_AMD_EINVAL, "mgamr_comm_set: NULL list");
@@ -449,26 +442,19 @@ int mgamr_halo_args(int level, int comp, int dir, MgAmrDev **D, double **vec) {
   *vec = b[comp - 1]->as<double>();
   return 0;
 }
-// messages of every peer into sendbuf; offsets in doubles
+// plan the exchange and gather the messages of every peer into its sendbuf
 int mgamr_halo_pack(MgAmrDev &D, double *vec, int dir) {
   MgAmrCtx &M = g_mg;
   MgAmrComm &Cm = D.comm;
-  M.send_off.assign((size_t)Cm.ncpu + 1, 0); M.recv_off.assign((size_t)Cm.ncpu + 1, 0);
+  const std::vector<int> &sf = dir == 0 ? Cm.em_first : Cm.rc_first, &rf = dir == 0 ? Cm.rc_first : Cm.em_first;
+  if (int rc = M.halo.plan(Cm.ncpu, sf.data(), rf.data(), 8)) return rc;
   for (int c = 0; c < Cm.ncpu; c++) {
-    const int64_t ne = 8 * (int64_t)(Cm.em_first[c + 1] - Cm.em_first[c]), nr = 8 * (int64_t)Cm.rc_n[c];
-    M.send_off[c + 1] = M.send_off[c] + (dir == 0 ? ne : nr);
-    M.recv_off[c + 1] = M.recv_off[c] + (dir == 0 ? nr : ne);
-  }
-  const size_t ns = (size_t)M.send_off[Cm.ncpu], nr = (size_t)M.recv_off[Cm.ncpu];
-  HCHK(M.sendbuf.ensure(sizeof(double) * (ns > 0 ? ns : 1)), "hipMalloc sendbuf");
-  HCHK(M.recvbuf.ensure(sizeof(double) * (nr > 0 ? nr : 1)), "hipMalloc recvbuf");
-  for (int c = 0; c < Cm.ncpu; c++) {
-    const int n = (int)((M.send_off[c + 1] - M.send_off[c]) / 8);
+    const int n = sf[c + 1] - sf[c];
     if (n <= 0) continue;
-    double *buf = M.sendbuf.as<double>() + M.send_off[c];
+    double *buf = M.halo.sendbuf.as<double>() + M.halo.send_off[c];
     const dim3 g((unsigned)((8L * n + 255) / 256)), b(256);
     if (dir == 0) hipLaunchKernelGGL(mgamr_halo_kernel<0>, g, b, 0, nullptr, vec, D.ngrid, Cm.em_pos.as<int>() + Cm.em_first[c], 0, n, buf);
-    else hipLaunchKernelGGL(mgamr_halo_kernel<0>, g, b, 0, nullptr, vec, D.ngrid, (const int *)nullptr, Cm.rc_off[c], n, buf);
+    else hipLaunchKernelGGL(mgamr_halo_kernel<0>, g, b, 0, nullptr, vec, D.ngrid, (const int *)nullptr, Cm.rc_base + Cm.rc_first[c], n, buf);
   }
   HCHK(hipGetLastError(), "mgamr halo pack launch");
   return 0;
@@ -476,23 +462,16 @@ int mgamr_halo_pack(MgAmrDev &D, double *vec, int dir) {
 int mgamr_halo_unpack(MgAmrDev &D, double *vec, int dir) {
   MgAmrCtx &M = g_mg;
   MgAmrComm &Cm = D.comm;
+  const std::vector<int> &rf = dir == 0 ? Cm.rc_first : Cm.em_first;
   for (int c = 0; c < Cm.ncpu; c++) {      // icpu order: the reverse exchange adds peer by peer
-    const int n = (int)((M.recv_off[c + 1] - M.recv_off[c]) / 8);
+    const int n = rf[c + 1] - rf[c];
     if (n <= 0) continue;
-    double *buf = M.recvbuf.as<double>() + M.recv_off[c];
+    double *buf = M.halo.recvbuf.as<double>() + M.halo.recv_off[c];
     const dim3 g((unsigned)((8L * n + 255) / 256)), b(256);
-    if (dir == 0) hipLaunchKernelGGL(mgamr_halo_kernel<1>, g, b, 0, nullptr, vec, D.ngrid, (const int *)nullptr, Cm.rc_off[c], n, buf);
+    if (dir == 0) hipLaunchKernelGGL(mgamr_halo_kernel<1>, g, b, 0, nullptr, vec, D.ngrid, (const int *)nullptr, Cm.rc_base + Cm.rc_first[c], n, buf);
     else hipLaunchKernelGGL(mgamr_halo_kernel<2>, g, b, 0, nullptr, vec, D.ngrid, Cm.em_pos.as<int>() + Cm.em_first[c], 0, n, buf);
   }
   HCHK(hipGetLastError(), "mgamr halo unpack launch");
-  return 0;
-}
-int pin_ensure(void *&p, size_t &cap, size_t bytes) {
-  if (bytes <= cap) return 0;
-  if (p) { hipHostFree(p); p = nullptr; cap = 0; }
-  const size_t want = bytes + bytes / 2;
-  HCHK(hipHostMalloc(&p, want, hipHostMallocDefault), "hipHostMalloc");
-  cap = want;
   return 0;
 }
 }  // namespace
@@ -504,19 +483,10 @@ int ramses_amd_mgamr_halo_stage_out(int level, int comp, int dir, int ncpu, int6
   MgAmrCtx &M = g_mg;
   MgAmrDev *D;
   double *vec;
-  if (!h_send_addr || !h_recv_addr || !send_off || !recv_off) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = mgamr_halo_args(level, comp, dir, &D, &vec)) return rc;
-  if (ncpu != D->comm.ncpu) return fail(RAMSES_AMD_EINVAL, "ncpu mismatch");
   if (int rc = mgamr_halo_pack(*D, vec, dir)) return rc;
-  const size_t ns = (size_t)M.send_off[ncpu], nr = (size_t)M.recv_off[ncpu];
-  if (int rc = pin_ensure(M.h_send, M.h_send_cap, sizeof(double) * (ns > 0 ? ns : 1))) return rc;
-  if (int rc = pin_ensure(M.h_recv, M.h_recv_cap, sizeof(double) * (nr > 0 ? nr : 1))) return rc;
-  if (ns > 0) HCHK(hipMemcpyAsync(M.h_send, M.sendbuf.p, sizeof(double) * ns, hipMemcpyDeviceToHost, nullptr), "D2H halo");
-  HCHK(hipStreamSynchronize(nullptr), "sync");
-  *h_send_addr = (int64_t)(intptr_t)M.h_send; *h_recv_addr = (int64_t)(intptr_t)M.h_recv;
-  for (int c = 0; c <= ncpu; c++) { send_off[c] = M.send_off[c]; recv_off[c] = M.recv_off[c]; }
-  M.halo_level = level; M.halo_comp = comp; M.halo_dir = dir;
-  M.stats[2] += (long long)(sizeof(double) * (ns + nr)); M.stats[3] += 1;
+  if (int rc = M.halo.stage_out(level, comp, dir, ncpu, h_send_addr, h_recv_addr, send_off, recv_off)) return rc;
+  M.stats[2] += (long long)(sizeof(double) * (size_t)(M.halo.send_off[ncpu] + M.halo.recv_off[ncpu])); M.stats[3] += 1;
   return 0;
 }
 int ramses_amd_mgamr_halo_stage_in(int level, int comp, int dir) {
@@ -524,33 +494,18 @@ int ramses_amd_mgamr_halo_stage_in(int level, int comp, int dir) {
   MgAmrDev *D;
   double *vec;
   if (int rc = mgamr_halo_args(level, comp, dir, &D, &vec)) return rc;
-  if (M.halo_level != level || M.halo_comp != comp || M.halo_dir != dir)
-    return fail(RAMSES_AMD_EINVAL, "mgamr_halo_stage_in(level %d, component %d, dir %d) does not close the exchange stage_out opened (%d, %d, %d)",
-                level, comp, dir, M.halo_level, M.halo_comp, M.halo_dir);
-  M.halo_level = 0; M.halo_dir = -1;
-  const size_t nr = (size_t)M.recv_off[D->comm.ncpu];
-  if (nr > 0) HCHK(hipMemcpyAsync(M.recvbuf.p, M.h_recv, sizeof(double) * nr, hipMemcpyHostToDevice, nullptr), "H2D halo");
+  if (int rc = M.halo.stage_in(level, comp, dir, D->comm.ncpu, "mgamr_halo_stage_in(level %d, component %d, dir %d) does not close the exchange stage_out opened (%d, %d, %d)",
+                               level, comp, dir, M.halo.tag[0], M.halo.tag[1], M.halo.tag[2])) return rc;
   return mgamr_halo_unpack(*D, vec, dir);
 }
 // the same exchange over RCCL (every rank on its own GPU): one grouped send/recv, nothing crosses PCIe
-extern "C" int ramses_amd_rccl_exchange(int npeer, const int *peer, const double *d_send, const int64_t *send_off, const int64_t *send_cnt,
-                                        double *d_recv, const int64_t *recv_off, const int64_t *recv_cnt, void *stream);
 int ramses_amd_mgamr_halo_rccl(int level, int comp, int dir) {
-  MgAmrCtx &M = g_mg;
   MgAmrDev *D;
   double *vec;
   if (int rc = mgamr_halo_args(level, comp, dir, &D, &vec)) return rc;
   if (int rc = mgamr_halo_pack(*D, vec, dir)) return rc;
-  std::vector<int> peer;
-  std::vector<int64_t> so, sc, ro, rcn;
-  for (int c = 0; c < D->comm.ncpu; c++) {
-    const int64_t ns = M.send_off[c + 1] - M.send_off[c], nr = M.recv_off[c + 1] - M.recv_off[c];
-    if (ns == 0 && nr == 0) continue;
-    peer.push_back(c); so.push_back(M.send_off[c]); sc.push_back(ns); ro.push_back(M.recv_off[c]); rcn.push_back(nr);
-  }
-  if (int rc = ramses_amd_rccl_exchange((int)peer.size(), peer.data(), M.sendbuf.as<double>(), so.data(), sc.data(), M.recvbuf.as<double>(),
-                                        ro.data(), rcn.data(), nullptr)) return rc;
-  M.stats[3] += 1;
+  if (int rc = g_mg.halo.rccl()) return rc;
+  g_mg.stats[3] += 1;
   return mgamr_halo_unpack(*D, vec, dir);
 }
 
@@ -688,11 +643,10 @@ struct CgMpi {
   bool comm = false;
   int ncpu = 0;
   std::vector<int> em_first, rc_first;
-  DevBuf em_ig, rc_ig, sendbuf, recvbuf;
-  void *h_send = nullptr, *h_recv = nullptr;
-  size_t h_send_cap = 0, h_recv_cap = 0;
-  bool halo_open = false;
+  DevBuf em_ig, rc_ig;
+  PeerExchange halo;         // tagged CG_HALO: there is one exchange, p's
 };
+constexpr int CG_HALO[3] = {1, 0, 0};
 CgMpi g_cgm;
 
 __global__ void cg_cells_kernel(double *vec, double *buf, const int *igrid, int n, long ncoarse, long ngridmax, int gather) {
@@ -828,19 +782,8 @@ int ramses_amd_cgmpi_comm_set(int ncpu, const int *em_n, const int *em_ig, const
   CgMpi &M = g_cgm;
   if (ncpu < 1 || !em_n || !rc_n) return fail(RAMSES_AMD_EINVAL, "cgmpi_comm_set: bad argument");
   M.comm = false; M.ncpu = ncpu;
-  M.em_first.assign((size_t)ncpu + 1, 0); M.rc_first.assign((size_t)ncpu + 1, 0);
-  for (int c = 0; c < ncpu; c++) {
-    if (em_n[c] < 0 || rc_n[c] < 0) return fail(RAMSES_AMD_EINVAL, "cgmpi_comm_set: negative list length");
-    M.em_first[c + 1] = M.em_first[c] + em_n[c];
-    M.rc_first[c + 1] = M.rc_first[c] + rc_n[c];
-  }
-  const int nem = M.em_first[ncpu], nrc = M.rc_first[ncpu];
-  if ((nem > 0 && !em_ig) || (nrc > 0 && !rc_ig)) return fail(RAMSES_AMD_EINVAL, "cgmpi_comm_set: NULL list");
-  HCHK(M.em_ig.ensure(sizeof(int) * (size_t)(nem > 0 ? nem : 1)), "hipMalloc"); HCHK(M.rc_ig.ensure(sizeof(int) * (size_t)(nrc > 0 ? nrc : 1)), "hipMalloc");
-  if (nem > 0) HCHK(hipMemcpy(M.em_ig.p, em_ig, sizeof(int) * (size_t)nem, hipMemcpyHostToDevice), "H2D emission list");
-  if (nrc > 0) HCHK(hipMemcpy(M.rc_ig.p, rc_ig, sizeof(int) * (size_t)nrc, hipMemcpyHostToDevice), "H2D reception list");
-  HCHK(M.sendbuf.ensure(sizeof(double) * 8 * (size_t)(nem > 0 ? nem : 1)), "hipMalloc sendbuf");
-  HCHK(M.recvbuf.ensure(sizeof(double) * 8 * (size_t)(nrc > 0 ? nrc : 1)), "hipMalloc recvbuf");
+  if (int rc = peer_lists("cgmpi_comm_set", ncpu, em_n, em_ig, rc_n, rc_ig, M.em_first, M.rc_first, M.em_ig, M.rc_ig)) return rc;
+  if (int rc = M.halo.plan(ncpu, M.em_first.data(), M.rc_first.data(), 8)) return rc;      // the same exchange every iteration
   M.comm = true;
   return 0;
 }
@@ -851,7 +794,7 @@ int cgmpi_pack(CgMpi &M) {
     if (n <= 0) continue;
     int nb = (int)((8L * n + 255) / 256);
     if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(cg_cells_kernel, dim3(nb), dim3(256), 0, nullptr, M.L.p, M.sendbuf.as<double>() + 8L * M.em_first[c],
+    hipLaunchKernelGGL(cg_cells_kernel, dim3(nb), dim3(256), 0, nullptr, M.L.p, M.halo.sendbuf.as<double>() + 8L * M.em_first[c],
                        M.em_ig.as<int>() + M.em_first[c], n, M.L.ncoarse, M.L.ngridmax, 1);
   }
   HCHK(hipGetLastError(), "cg halo pack launch");
@@ -863,7 +806,7 @@ int cgmpi_unpack(CgMpi &M) {
     if (n <= 0) continue;
     int nb = (int)((8L * n + 255) / 256);
     if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(cg_cells_kernel, dim3(nb), dim3(256), 0, nullptr, M.L.p, M.recvbuf.as<double>() + 8L * M.rc_first[c],
+    hipLaunchKernelGGL(cg_cells_kernel, dim3(nb), dim3(256), 0, nullptr, M.L.p, M.halo.recvbuf.as<double>() + 8L * M.rc_first[c],
                        M.rc_ig.as<int>() + M.rc_first[c], n, M.L.ncoarse, M.L.ngridmax, 0);
   }
   HCHK(hipGetLastError(), "cg halo unpack launch");
@@ -874,25 +817,13 @@ int ramses_amd_cgmpi_p_halo_stage_out(int ncpu, int64_t *h_send_addr, int64_t *h
   CGM_OPEN("cgmpi_p_halo_stage_out");
   CgMpi &M = g_cgm;
   if (!M.comm || ncpu != M.ncpu) return fail(RAMSES_AMD_EINVAL, "cgmpi_p_halo_stage_out: no communicators (ramses_amd_cgmpi_comm_set) / ncpu mismatch");
-  if (!h_send_addr || !h_recv_addr || !send_off || !recv_off) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = cgmpi_pack(M)) return rc;
-  const size_t ns = 8 * (size_t)M.em_first[ncpu], nr = 8 * (size_t)M.rc_first[ncpu];
-  if (int rc = pin_ensure(M.h_send, M.h_send_cap, sizeof(double) * (ns > 0 ? ns : 1))) return rc;
-  if (int rc = pin_ensure(M.h_recv, M.h_recv_cap, sizeof(double) * (nr > 0 ? nr : 1))) return rc;
-  if (ns > 0) HCHK(hipMemcpyAsync(M.h_send, M.sendbuf.p, sizeof(double) * ns, hipMemcpyDeviceToHost, nullptr), "D2H halo");
-  HCHK(hipStreamSynchronize(nullptr), "sync");
-  *h_send_addr = (int64_t)(intptr_t)M.h_send; *h_recv_addr = (int64_t)(intptr_t)M.h_recv;
-  for (int c = 0; c <= ncpu; c++) { send_off[c] = 8 * (int64_t)M.em_first[c]; recv_off[c] = 8 * (int64_t)M.rc_first[c]; }
-  M.halo_open = true;
-  return 0;
+  return M.halo.stage_out(CG_HALO[0], CG_HALO[1], CG_HALO[2], ncpu, h_send_addr, h_recv_addr, send_off, recv_off);
 }
 int ramses_amd_cgmpi_p_halo_stage_in(void) {
   CGM_OPEN("cgmpi_p_halo_stage_in");
   CgMpi &M = g_cgm;
-  if (!M.halo_open) return fail(RAMSES_AMD_EINVAL, "cgmpi_p_halo_stage_in without cgmpi_p_halo_stage_out");
-  M.halo_open = false;
-  const size_t nr = 8 * (size_t)M.rc_first[M.ncpu];
-  if (nr > 0) HCHK(hipMemcpyAsync(M.recvbuf.p, M.h_recv, sizeof(double) * nr, hipMemcpyHostToDevice, nullptr), "H2D halo");
+  if (int rc = M.halo.stage_in(CG_HALO[0], CG_HALO[1], CG_HALO[2], M.ncpu, "%s", "cgmpi_p_halo_stage_in without cgmpi_p_halo_stage_out")) return rc;
   return cgmpi_unpack(M);
 }
 int ramses_amd_cgmpi_p_halo_rccl(void) {
@@ -900,15 +831,7 @@ int ramses_amd_cgmpi_p_halo_rccl(void) {
   CgMpi &M = g_cgm;
   if (!M.comm) return fail(RAMSES_AMD_EINVAL, "cgmpi_p_halo_rccl: no communicators (ramses_amd_cgmpi_comm_set)");
   if (int rc = cgmpi_pack(M)) return rc;
-  std::vector<int> peer;
-  std::vector<int64_t> so, sc, ro, rcn;
-  for (int c = 0; c < M.ncpu; c++) {
-    const int64_t ns = 8 * (int64_t)(M.em_first[c + 1] - M.em_first[c]), nr = 8 * (int64_t)(M.rc_first[c + 1] - M.rc_first[c]);
-    if (ns == 0 && nr == 0) continue;
-    peer.push_back(c); so.push_back(8 * (int64_t)M.em_first[c]); sc.push_back(ns); ro.push_back(8 * (int64_t)M.rc_first[c]); rcn.push_back(nr);
-  }
-  if (int rc = ramses_amd_rccl_exchange((int)peer.size(), peer.data(), M.sendbuf.as<double>(), so.data(), sc.data(), M.recvbuf.as<double>(),
-                                        ro.data(), rcn.data(), nullptr)) return rc;
+  if (int rc = M.halo.rccl()) return rc;
   return cgmpi_unpack(M);
 }
 // phi and f = (r, p, A p) back into the host arrays (what the reference's loop leaves)
@@ -922,7 +845,7 @@ int ramses_amd_cgmpi_end(double *phi, double *f) {
   HCHK(hipMemcpy(f + g_cgm.ncell, G.p.p, vb, hipMemcpyDeviceToHost), "D2H p");
   HCHK(hipMemcpy(f + 2 * g_cgm.ncell, G.z.p, vb, hipMemcpyDeviceToHost), "D2H z");
   g_cgm.open = false;
-  g_cgm.comm = false; g_cgm.halo_open = false;
+  g_cgm.comm = false; g_cgm.halo.close();
   return 0;
 }
 #undef CGM_OPEN
