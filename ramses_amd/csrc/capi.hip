@@ -583,7 +583,7 @@ static hipError_t mg_coarse_cycle(double *w, int level, int l, int safe, hipStre
 
 // ---------------------------------------------------------------------------
 // Distributed multigrid (one rank's brick with ghost layers per level; the
-// V-cycle driver with its halo exchanges is ramses_amd/poisson_parallel.py).
+// V-cycle driver with its halo exchanges is csrc/mg_dist.hip).
 // ---------------------------------------------------------------------------
 static bool brick_extent_ok(int n) { return n >= 2 && !(n & (n - 1)); }
 int ramses_amd_mg_smooth_fused_ghost(const double *d_phi_in, double *d_phi_out, const double *d_rhs,

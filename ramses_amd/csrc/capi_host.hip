@@ -20,6 +20,7 @@
 #include "rho_args.hpp"
 #include "sweep_args.hpp"
 #include "capi_shared.hpp"
+#include "level_brick.hpp"
 
 using namespace ramses_amd;
 
@@ -30,7 +31,8 @@ using namespace ramses_amd;
 // ---------------------------------------------------------------------------
 namespace {
 struct HostCtx {
-  DevBuf uold, unew, fvec, igrid, xg, octorg, bold, bnew, bf, flag, red;
+  DevBuf uold, unew, fvec, bold, bnew, bf, red;
+  LevelOcts octs;   // of the level the staged entries ran on last; of the resident level while res_valid
   // Poisson fields of the resident level (rho_fine -> multigrid_fine -> force_fine without PCIe):
   // rho, phi bricks, the multigrid work arrays, the oct-position -> list-index table of rho_fine
   DevBuf brho, bphi, bf1, bf2, mgwork, octidx, diag, cellvec1;
@@ -60,6 +62,19 @@ int ramses_amd::capi_resident_release(const char *who) {
 }
 static int resident_release(const char *who) { return ramses_amd::capi_resident_release(who); }
 
+// the level as a dense n^3 brick without ghost cells
+static ramses_amd_brick dense_brick(int n) {
+  ramses_amd_brick b;
+  ramses_amd_brick_dense(&b, n, n, n, 0);
+  return b;
+}
+// is (ilevel, ngrid, ncell) the resident level?  The staged Poisson entries share H.octs with it: the same level rewrites
+// them with the same contents, anything else ends the residency
+static bool resident_is_level(int ilevel, int ngrid, long ncell) {
+  const HostCtx &H = g_host;
+  return H.res_valid && H.res_level == ilevel && H.res_ngrid == ngrid && H.res_ncell == ncell;
+}
+
 extern "C" {
 
 int ramses_amd_godunov_fine_host(const ramses_amd_hydro_params *p, int ilevel, int ngrid,
@@ -69,62 +84,38 @@ int ramses_amd_godunov_fine_host(const ramses_amd_hydro_params *p, int ilevel, i
   if (!p || !igrid || !xg || !uold || !unew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (p->ndim != 3) return fail(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3");
   if (int rc = check_nvar(p, "ramses_amd_godunov_fine_host")) return rc;
-  if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "device path needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
-  if (ilevel < 1 || ilevel > 11) return fail(RAMSES_AMD_EINVAL, "level out of range");
-  const int n = 1 << ilevel;
-  const long ncells_level = (long)n * n * n;
-  if ((long)ngrid * 8 != ncells_level)
-    return fail(RAMSES_AMD_EUNSUPPORTED,
-                "level %d is not fully refined on this rank (ngrid=%d, need %ld): AMR / multi-rank levels are not on the device yet",
-                ilevel, ngrid, ncells_level / 8);
-  const long ncell = ncoarse + 8 * ngridmax;
-  const int nvar = p->nvar;
+  LevelShape L;
+  if (int rc = level_shape("device path", ilevel, 1, 11, ngrid, nx_loc, ngridmax, ncoarse, &L)) return rc;
+  const int n = L.n, nvar = p->nvar;
+  const long ncell = L.ncell;
   if (int rc = resident_release("godunov_fine (staged brick sweep)")) return rc;   // the bricks are reused
   hipStream_t s = nullptr;
   HostCtx &H = g_host;
   HCHK(H.uold.ensure(sizeof(double) * nvar * ncell), "hipMalloc uold");
   HCHK(H.unew.ensure(sizeof(double) * nvar * ncell), "hipMalloc unew");
-  HCHK(H.igrid.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
-  HCHK(H.xg.ensure(sizeof(double) * 3 * ngridmax), "hipMalloc xg");
-  HCHK(H.octorg.ensure(sizeof(long) * ngrid), "hipMalloc octorg");
-  HCHK(H.bold.ensure(sizeof(double) * nvar * ncells_level), "hipMalloc brick");
-  HCHK(H.bnew.ensure(sizeof(double) * nvar * ncells_level), "hipMalloc brick");
-  HCHK(H.flag.ensure(sizeof(int)), "hipMalloc flag");
+  HCHK(H.bold.ensure(sizeof(double) * nvar * L.N), "hipMalloc brick");
+  HCHK(H.bnew.ensure(sizeof(double) * nvar * L.N), "hipMalloc brick");
   HCHK(hipMemcpyAsync(H.uold.p, uold, sizeof(double) * nvar * ncell, hipMemcpyHostToDevice, s), "H2D uold");
   HCHK(hipMemcpyAsync(H.unew.p, unew, sizeof(double) * nvar * ncell, hipMemcpyHostToDevice, s), "H2D unew");
-  HCHK(hipMemcpyAsync(H.igrid.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
-  HCHK(hipMemcpyAsync(H.xg.p, xg, sizeof(double) * 3 * ngridmax, hipMemcpyHostToDevice, s), "H2D xg");
-  HCHK(hipMemsetAsync(H.flag.p, 0, sizeof(int), s), "memset");
-  const double skip[3] = {0.0, 0.0, 0.0};   // icoarse_min = 0 for nx = 1
-  HCHK(launch_oct_origin(H.igrid.as<int>(), H.xg.as<double>(), ngridmax, ngrid, n, skip, H.octorg.as<long>(), H.flag.as<int>(), s), "oct origin launch");
-  int bad = 0;
-  HCHK(hipMemcpyAsync(&bad, H.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
-  HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return fail(RAMSES_AMD_EINVAL, "%d octs of level %d do not sit on the level-%d lattice (xg inconsistent)", bad, ilevel, ilevel);
-  PackArgs A;
-  A.igrid = H.igrid.as<int>(); A.octorg = H.octorg.as<long>();
-  A.ngrid = ngrid; A.n = n; A.nvar = nvar;
-  A.ncoarse = ncoarse; A.ngridmax = ngridmax; A.ncell = ncell; A.pitch_var = ncells_level;
-  A.brick = H.bold.as<double>(); A.cellvec = H.uold.as<double>();
-  HCHK(launch_oct_copy(A, true, s), "gather launch");
+  if (int rc = level_octs_upload(H.octs, ilevel, n, ngrid, igrid, xg, ngridmax, s)) return rc;
+  auto pack = [&](int nv, DevBuf &brick, DevBuf &vec) {
+    return level_pack(H.octs, ngrid, n, nv, ncoarse, ngridmax, brick.as<double>(), vec.as<double>());
+  };
+  HCHK(launch_oct_copy(pack(nvar, H.bold, H.uold), true, s), "gather launch");
   const double *d_grav = nullptr;
   if (f) {
     HCHK(H.fvec.ensure(sizeof(double) * 3 * ncell), "hipMalloc f");
-    HCHK(H.bf.ensure(sizeof(double) * 3 * ncells_level), "hipMalloc f brick");
+    HCHK(H.bf.ensure(sizeof(double) * 3 * L.N), "hipMalloc f brick");
     HCHK(hipMemcpyAsync(H.fvec.p, f, sizeof(double) * 3 * ncell, hipMemcpyHostToDevice, s), "H2D f");
-    PackArgs G = A;
-    G.nvar = 3; G.brick = H.bf.as<double>(); G.cellvec = H.fvec.as<double>();
-    HCHK(launch_oct_copy(G, true, s), "gather launch");
+    HCHK(launch_oct_copy(pack(3, H.bf, H.fvec), true, s), "gather launch");
     d_grav = H.bf.as<double>();
   }
-  ramses_amd_brick b;
-  ramses_amd_brick_dense(&b, n, n, n, 0);
+  const ramses_amd_brick b = dense_brick(n);
   if (int rc = ramses_amd_godunov_brick(p, &b, H.bold.as<double>(), d_grav, H.bnew.as<double>(), dx, dt, s)) return rc;
   // The reference adds flux differences to the unew that set_unew prepared
   // (= uold on active cells); the brick kernel returns uold + differences, so
   // scattering it over unew's active cells gives the same array.
-  A.brick = H.bnew.as<double>(); A.cellvec = H.unew.as<double>();
-  HCHK(launch_oct_copy(A, false, s), "scatter launch");
+  HCHK(launch_oct_copy(pack(nvar, H.bnew, H.unew), false, s), "scatter launch");
   HCHK(hipMemcpyAsync(unew, H.unew.p, sizeof(double) * nvar * ncell, hipMemcpyDeviceToHost, s), "D2H unew");
   HCHK(hipStreamSynchronize(s), "sync");
   return 0;
@@ -223,19 +214,19 @@ int ramses_amd_godunov_fine_amr_host(const ramses_amd_hydro_params *p, int ileve
   const int nvar = p->nvar;
   HCHK(H.uold.ensure(sizeof(double) * nvar * ncell), "hipMalloc uold");
   HCHK(H.unew.ensure(sizeof(double) * nvar * ncell), "hipMalloc unew");
-  HCHK(H.igrid.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
+  HCHK(H.octs.igrid.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
   HCHK(dson.ensure(sizeof(int) * ncell), "hipMalloc son");
   HCHK(dnbor.ensure(sizeof(int) * 6 * ngridmax), "hipMalloc nbor");
   HCHK(dfather.ensure(sizeof(int) * ngridmax), "hipMalloc father");
   HCHK(dwork.ensure((size_t)ramses_amd_godunov_fine_amr_workspace(ngrid, ngridmax)), "hipMalloc work");
-  HCHK(H.flag.ensure(sizeof(int)), "hipMalloc flag");
+  HCHK(H.octs.flag.ensure(sizeof(int)), "hipMalloc flag");
   HCHK(hipMemcpyAsync(H.uold.p, uold, sizeof(double) * nvar * ncell, hipMemcpyHostToDevice, s), "H2D uold");
   HCHK(hipMemcpyAsync(H.unew.p, unew, sizeof(double) * nvar * ncell, hipMemcpyHostToDevice, s), "H2D unew");
-  HCHK(hipMemcpyAsync(H.igrid.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
+  HCHK(hipMemcpyAsync(H.octs.igrid.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
   HCHK(hipMemcpyAsync(dson.p, son, sizeof(int) * ncell, hipMemcpyHostToDevice, s), "H2D son");
   HCHK(hipMemcpyAsync(dnbor.p, nbor, sizeof(int) * 6 * ngridmax, hipMemcpyHostToDevice, s), "H2D nbor");
   HCHK(hipMemcpyAsync(dfather.p, father, sizeof(int) * ngridmax, hipMemcpyHostToDevice, s), "H2D father");
-  HCHK(hipMemsetAsync(H.flag.p, 0, sizeof(int), s), "memset");
+  HCHK(hipMemsetAsync(H.octs.flag.p, 0, sizeof(int), s), "memset");
   const double *d_grav = nullptr;
   if (f) {
     HCHK(H.fvec.ensure(sizeof(double) * 3 * ncell), "hipMalloc f");
@@ -250,12 +241,12 @@ int ramses_amd_godunov_fine_amr_host(const ramses_amd_hydro_params *p, int ileve
     HCHK(hipMemcpyAsync(denew.p, enew, sizeof(double) * ncell, hipMemcpyHostToDevice, s), "H2D enew");
     d_divu = ddivu.as<double>(); d_enew = denew.as<double>();
   }
-  if (int rc = ramses_amd_godunov_fine_amr_device(p, ilevel, ngrid, H.igrid.as<int>(), dson.as<int>(), dnbor.as<int>(),
+  if (int rc = ramses_amd_godunov_fine_amr_device(p, ilevel, ngrid, H.octs.igrid.as<int>(), dson.as<int>(), dnbor.as<int>(),
                                                   dfather.as<int>(), ngridmax, ncoarse, H.uold.as<double>(),
                                                   H.unew.as<double>(), d_grav, d_divu, d_enew, dx, dt, nvector, interpol_var, interpol_type,
-                                                  dwork.p, H.flag.as<int>(), s)) return rc;
+                                                  dwork.p, H.octs.flag.as<int>(), s)) return rc;
   int bad = 0;
-  HCHK(hipMemcpyAsync(&bad, H.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
+  HCHK(hipMemcpyAsync(&bad, H.octs.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
   HCHK(hipMemcpyAsync(unew, H.unew.p, sizeof(double) * nvar * ncell, hipMemcpyDeviceToHost, s), "D2H unew");
   if (divu) {
     HCHK(hipMemcpyAsync(divu, ddivu.p, sizeof(double) * ncell, hipMemcpyDeviceToHost, s), "D2H divu");
@@ -440,18 +431,14 @@ int ramses_amd_multigrid_fine_f90(int ilevel, int ngrid, const int *igrid, const
                                   double *phi, double rho_tot, double fourpi, double epsilon,
                                   int *safe_mode, int *iters, double *err) {
   if (!igrid || !xg || !rho || !phi || !safe_mode) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "device multigrid needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
-  if (ilevel < 1 || ilevel > 11) return fail(RAMSES_AMD_EINVAL, "level out of range");
-  const int n = 1 << ilevel;
-  const long N = (long)n * n * n;
-  if ((long)ngrid * 8 != N)
-    return fail(RAMSES_AMD_EUNSUPPORTED, "level %d is not fully refined on this rank (ngrid=%d): masked/AMR multigrid is not on the device yet", ilevel, ngrid);
-  const long ncell = ncoarse + 8 * ngridmax;
+  LevelShape L;
+  if (int rc = level_shape("device multigrid", ilevel, 1, 11, ngrid, nx_loc, ngridmax, ncoarse, &L)) return rc;
+  const long N = L.N, ncell = L.ncell;
   hipStream_t s = nullptr;
   HostCtx &H = g_host;
-  // igrid/xg/octorg are shared with the resident level: the same level rewrites them with the same contents
-  if (H.res_valid && !(H.res_level == ilevel && H.res_ngrid == ngrid && H.res_ncell == ncell))
+  if (!resident_is_level(ilevel, ngrid, ncell))
     if (int rc = resident_release("multigrid_fine")) return rc;
+  // (function-local: a staged solve on the resident level must not overwrite H.brho / H.bphi)
   static DevBuf rhovec, phivec, brho, bphi, bf1, bf2, work;
   const int64_t nwork = ramses_amd_mg_workspace_doubles(ilevel);
   HCHK(rhovec.ensure(sizeof(double) * ncell), "hipMalloc");
@@ -461,33 +448,15 @@ int ramses_amd_multigrid_fine_f90(int ilevel, int ngrid, const int *igrid, const
   HCHK(bf1.ensure(sizeof(double) * N), "hipMalloc");
   HCHK(bf2.ensure(sizeof(double) * N), "hipMalloc");
   HCHK(work.ensure(sizeof(double) * nwork), "hipMalloc");
-  HCHK(H.igrid.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
-  HCHK(H.xg.ensure(sizeof(double) * 3 * ngridmax), "hipMalloc xg");
-  HCHK(H.octorg.ensure(sizeof(long) * ngrid), "hipMalloc octorg");
-  HCHK(H.flag.ensure(sizeof(int)), "hipMalloc flag");
   HCHK(hipMemcpyAsync(rhovec.p, rho, sizeof(double) * ncell, hipMemcpyHostToDevice, s), "H2D rho");
   HCHK(hipMemcpyAsync(phivec.p, phi, sizeof(double) * ncell, hipMemcpyHostToDevice, s), "H2D phi");
-  HCHK(hipMemcpyAsync(H.igrid.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
-  HCHK(hipMemcpyAsync(H.xg.p, xg, sizeof(double) * 3 * ngridmax, hipMemcpyHostToDevice, s), "H2D xg");
-  HCHK(hipMemsetAsync(H.flag.p, 0, sizeof(int), s), "memset");
-  const double skip[3] = {0.0, 0.0, 0.0};
-  HCHK(launch_oct_origin(H.igrid.as<int>(), H.xg.as<double>(), ngridmax, ngrid, n, skip, H.octorg.as<long>(), H.flag.as<int>(), s), "oct origin launch");
-  int bad = 0;
-  HCHK(hipMemcpyAsync(&bad, H.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
-  HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return fail(RAMSES_AMD_EINVAL, "%d octs of level %d do not sit on the level lattice", bad, ilevel);
-  PackArgs A;
-  A.igrid = H.igrid.as<int>(); A.octorg = H.octorg.as<long>();
-  A.ngrid = ngrid; A.n = n; A.nvar = 1;
-  A.ncoarse = ncoarse; A.ngridmax = ngridmax; A.ncell = ncell; A.pitch_var = N;
-  A.brick = brho.as<double>(); A.cellvec = rhovec.as<double>();
-  HCHK(launch_oct_copy(A, true, s), "gather launch");
+  if (int rc = level_octs_upload(H.octs, ilevel, L.n, ngrid, igrid, xg, ngridmax, s)) return rc;
+  HCHK(launch_oct_copy(level_pack(H.octs, ngrid, L.n, 1, ncoarse, ngridmax, brho.as<double>(), rhovec.as<double>()), true, s), "gather launch");
   HCHK(hipMemsetAsync(bphi.p, 0, sizeof(double) * N, s), "memset phi");   // make_multipole_phi, periodic: phi = 0
   if (int rc = ramses_amd_multigrid_fine_brick(ilevel, brho.as<double>(), rho_tot, fourpi, epsilon, safe_mode,
                                                bphi.as<double>(), bf1.as<double>(), bf2.as<double>(),
                                                work.as<double>(), iters, err, s)) return rc;
-  A.brick = bphi.as<double>(); A.cellvec = phivec.as<double>();
-  HCHK(launch_oct_copy(A, false, s), "scatter launch");
+  HCHK(launch_oct_copy(level_pack(H.octs, ngrid, L.n, 1, ncoarse, ngridmax, bphi.as<double>(), phivec.as<double>()), false, s), "scatter launch");
   HCHK(hipMemcpyAsync(phi, phivec.p, sizeof(double) * ncell, hipMemcpyDeviceToHost, s), "D2H phi");
   HCHK(hipStreamSynchronize(s), "sync");
   return 0;
@@ -500,39 +469,23 @@ int ramses_amd_force_fine_f90(int ilevel, int ngrid, const int *igrid, const dou
                               int64_t ngridmax, int64_t ncoarse, int nx_loc, const double *phi, double *f,
                               const double *rho, const int *son_or_dummy, int has_son, double fact, double *diag2) {
   if (!igrid || !xg || !phi || !f || !rho || !diag2 || (has_son && !son_or_dummy)) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "device force_fine needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
-  if (ilevel < 2 || ilevel > 11) return fail(RAMSES_AMD_EINVAL, "level out of range");
-  const int n = 1 << ilevel;
-  const long N = (long)n * n * n;
-  if ((long)ngrid * 8 != N)
-    return fail(RAMSES_AMD_EUNSUPPORTED, "level %d is not fully refined on this rank (ngrid=%d)", ilevel, ngrid);
-  const long ncell = ncoarse + 8 * ngridmax;
+  LevelShape L;
+  if (int rc = level_shape("device force_fine", ilevel, 2, 11, ngrid, nx_loc, ngridmax, ncoarse, &L)) return rc;
+  const long N = L.N, ncell = L.ncell;
   hipStream_t s = nullptr;
   HostCtx &H = g_host;
+  // (function-local: a staged call on the resident level must not overwrite H.bphi)
   static DevBuf phivec, fvec3, bphi, bf;
   HCHK(phivec.ensure(sizeof(double) * ncell), "hipMalloc");
   HCHK(fvec3.ensure(sizeof(double) * 3 * ncell), "hipMalloc");
   HCHK(bphi.ensure(sizeof(double) * N), "hipMalloc");
   HCHK(bf.ensure(sizeof(double) * 3 * N), "hipMalloc");
-  HCHK(H.igrid.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
-  HCHK(H.xg.ensure(sizeof(double) * 3 * ngridmax), "hipMalloc xg");
-  HCHK(H.octorg.ensure(sizeof(long) * ngrid), "hipMalloc octorg");
-  HCHK(H.flag.ensure(sizeof(int)), "hipMalloc flag");
   HCHK(hipMemcpyAsync(phivec.p, phi, sizeof(double) * ncell, hipMemcpyHostToDevice, s), "H2D phi");
   HCHK(hipMemcpyAsync(fvec3.p, f, sizeof(double) * 3 * ncell, hipMemcpyHostToDevice, s), "H2D f");   // cells off the level keep their values
-  HCHK(hipMemcpyAsync(H.igrid.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
-  HCHK(hipMemcpyAsync(H.xg.p, xg, sizeof(double) * 3 * ngridmax, hipMemcpyHostToDevice, s), "H2D xg");
-  HCHK(hipMemsetAsync(H.flag.p, 0, sizeof(int), s), "memset");
-  const double skip[3] = {0.0, 0.0, 0.0};
-  HCHK(launch_oct_origin(H.igrid.as<int>(), H.xg.as<double>(), ngridmax, ngrid, n, skip, H.octorg.as<long>(), H.flag.as<int>(), s), "oct origin launch");
-  int bad = 0;
-  HCHK(hipMemcpyAsync(&bad, H.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
-  HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return fail(RAMSES_AMD_EINVAL, "%d octs of level %d do not sit on the level lattice", bad, ilevel);
-  // igrid/xg/octorg are shared with the resident level: the same level rewrites them with the
-  // same contents, anything else ends the residency
-  const bool resident = H.res_valid && H.res_level == ilevel && H.res_ngrid == ngrid && H.res_ncell == ncell;
+  if (int rc = level_octs_upload(H.octs, ilevel, L.n, ngrid, igrid, xg, ngridmax, s)) return rc;
+  const bool resident = resident_is_level(ilevel, ngrid, ncell);
   if (!resident) if (int rc = resident_release("force_fine")) return rc;
+  auto pack = [&](int nv, double *brick, DevBuf &vec) { return level_pack(H.octs, ngrid, L.n, nv, ncoarse, ngridmax, brick, vec.as<double>()); };
   double *d_f = bf.as<double>();
   if (resident) {
     // the acceleration of the resident level is rewritten in place (synchro_hydro_fine,
@@ -540,17 +493,10 @@ int ramses_amd_force_fine_f90(int ilevel, int ngrid, const int *igrid, const dou
     HCHK(H.bf.ensure(sizeof(double) * 3 * N), "hipMalloc f brick");
     d_f = H.bf.as<double>();
   }
-  PackArgs A;
-  A.igrid = H.igrid.as<int>(); A.octorg = H.octorg.as<long>();
-  A.ngrid = ngrid; A.n = n; A.nvar = 1;
-  A.ncoarse = ncoarse; A.ngridmax = ngridmax; A.ncell = ncell; A.pitch_var = N;
-  A.brick = bphi.as<double>(); A.cellvec = phivec.as<double>();
-  HCHK(launch_oct_copy(A, true, s), "gather launch");
+  HCHK(launch_oct_copy(pack(1, bphi.as<double>(), phivec), true, s), "gather launch");
   if (int rc = ramses_amd_gradient_phi_brick(ilevel, bphi.as<double>(), d_f, s)) return rc;
   if (resident) H.res_grav_valid = true;
-  A.nvar = 3;
-  A.brick = d_f; A.cellvec = fvec3.as<double>();
-  HCHK(launch_oct_copy(A, false, s), "scatter launch");
+  HCHK(launch_oct_copy(pack(3, d_f, fvec3), false, s), "scatter launch");
   HCHK(hipMemcpyAsync(f, fvec3.p, sizeof(double) * 3 * ncell, hipMemcpyDeviceToHost, s), "D2H f");
   // diagnostics (:158-190): potential energy of the leaf cells and maximum density, reduced on the device
   {
@@ -559,7 +505,7 @@ int ramses_amd_force_fine_f90(int ilevel, int ngrid, const int *igrid, const dou
     HCHK(brho.ensure(sizeof(double) * N), "hipMalloc");
     HCHK(H.diag.ensure(sizeof(double) * (FORCE_DIAG_SCRATCH + 2)), "hipMalloc");
     HCHK(hipMemcpyAsync(rhovec.p, rho, sizeof(double) * ncell, hipMemcpyHostToDevice, s), "H2D rho");
-    A.nvar = 1; A.brick = brho.as<double>(); A.cellvec = rhovec.as<double>();
+    const PackArgs A = pack(1, brho.as<double>(), rhovec);
     HCHK(launch_oct_copy(A, true, s), "gather launch");
     const int *d_leaf = nullptr;
     if (has_son) {
@@ -594,44 +540,21 @@ static int resident_ensure(const ramses_amd_hydro_params *p, int ilevel, int ngr
   if (!p || !igrid || !xg || !uold) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (p->ndim != 3) return fail(RAMSES_AMD_EUNSUPPORTED, "device path implements NDIM=3");
   if (int rc = check_nvar(p, "ramses_amd_resident (godunov / courant)")) return rc;
-  if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "device path needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", nx_loc);
-  if (ilevel < 1 || ilevel > 11) return fail(RAMSES_AMD_EINVAL, "level out of range");
-  const int n = 1 << ilevel;
-  const long N = (long)n * n * n;
-  if ((long)ngrid * 8 != N)
-    return fail(RAMSES_AMD_EUNSUPPORTED, "level %d is not fully refined on this rank (ngrid=%d, need %ld)", ilevel, ngrid, N / 8);
+  LevelShape L;
+  if (int rc = level_shape("device path", ilevel, 1, 11, ngrid, nx_loc, ngridmax, ncoarse, &L)) return rc;
   HostCtx &H = g_host;
   H.res_nener = p->nener;
-  const long ncell = ncoarse + 8 * ngridmax;
+  const long ncell = L.ncell;
   const int nvar = p->nvar;
-  if (H.res_valid && H.res_level == ilevel && H.res_ngrid == ngrid && H.res_nvar == nvar && H.res_ncell == ncell &&
-      H.res_host_uold == uold)
-    return 0;
+  if (resident_is_level(ilevel, ngrid, ncell) && H.res_nvar == nvar && H.res_host_uold == uold) return 0;
   hipStream_t s = nullptr;
   HCHK(H.uold.ensure(sizeof(double) * nvar * ncell), "hipMalloc uold");
-  HCHK(H.igrid.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
-  HCHK(H.xg.ensure(sizeof(double) * 3 * ngridmax), "hipMalloc xg");
-  HCHK(H.octorg.ensure(sizeof(long) * ngrid), "hipMalloc octorg");
-  HCHK(H.bold.ensure(sizeof(double) * nvar * N), "hipMalloc brick");
-  HCHK(H.bnew.ensure(sizeof(double) * nvar * N), "hipMalloc brick");
-  HCHK(H.flag.ensure(sizeof(int)), "hipMalloc flag");
+  HCHK(H.bold.ensure(sizeof(double) * nvar * L.N), "hipMalloc brick");
+  HCHK(H.bnew.ensure(sizeof(double) * nvar * L.N), "hipMalloc brick");
   HCHK(H.red.ensure(sizeof(double) * 4), "hipMalloc reduction");
   HCHK(hipMemcpyAsync(H.uold.p, uold, sizeof(double) * nvar * ncell, hipMemcpyHostToDevice, s), "H2D uold");
-  HCHK(hipMemcpyAsync(H.igrid.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
-  HCHK(hipMemcpyAsync(H.xg.p, xg, sizeof(double) * 3 * ngridmax, hipMemcpyHostToDevice, s), "H2D xg");
-  HCHK(hipMemsetAsync(H.flag.p, 0, sizeof(int), s), "memset");
-  const double skip[3] = {0.0, 0.0, 0.0};
-  HCHK(launch_oct_origin(H.igrid.as<int>(), H.xg.as<double>(), ngridmax, ngrid, n, skip, H.octorg.as<long>(), H.flag.as<int>(), s), "oct origin launch");
-  int bad = 0;
-  HCHK(hipMemcpyAsync(&bad, H.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
-  HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return fail(RAMSES_AMD_EINVAL, "%d octs of level %d do not sit on the level lattice (xg inconsistent)", bad, ilevel);
-  PackArgs A;
-  A.igrid = H.igrid.as<int>(); A.octorg = H.octorg.as<long>();
-  A.ngrid = ngrid; A.n = n; A.nvar = nvar;
-  A.ncoarse = ncoarse; A.ngridmax = ngridmax; A.ncell = ncell; A.pitch_var = N;
-  A.brick = H.bold.as<double>(); A.cellvec = H.uold.as<double>();
-  HCHK(launch_oct_copy(A, true, s), "gather launch");
+  if (int rc = level_octs_upload(H.octs, ilevel, L.n, ngrid, igrid, xg, ngridmax, s)) return rc;
+  HCHK(launch_oct_copy(level_pack(H.octs, ngrid, L.n, nvar, ncoarse, ngridmax, H.bold.as<double>(), H.uold.as<double>()), true, s), "gather launch");
   H.res_valid = true; H.res_host_stale = false; H.res_new_ready = false; H.res_grav_valid = false;
   H.res_rho_valid = false; H.res_phi_valid = false; H.res_pois_host_stale = false;
   H.res_level = ilevel; H.res_ngrid = ngrid; H.res_nvar = nvar; H.res_ncell = ncell;
@@ -639,48 +562,102 @@ static int resident_ensure(const ramses_amd_hydro_params *p, int ilevel, int ngr
   return 0;
 }
 
+// cells of the resident level
+static long resident_cells() { const long n = 1L << g_host.res_level; return n * n * n; }
+// the copy between a brick of the resident level and cell vectors (1:ncell,1:nvar) on the device
+static PackArgs resident_pack(int nvar, const DevBuf &brick, const DevBuf &vec) {
+  const HostCtx &H = g_host;
+  return level_pack(H.octs, H.res_ngrid, 1 << H.res_level, nvar, H.res_ncoarse, H.res_ngridmax, brick.as<double>(), vec.as<double>());
+}
+// the level's cells of `brick` into the cell vectors `vec` on the device, and those to the host array (nvar columns of ncell);
+// cells of other levels come back with the values `vec` holds for them.  Synchronises.
+static int resident_to_host(int nvar, const DevBuf &brick, const DevBuf &vec, double *host, const char *what, hipStream_t s) {
+  HCHK(launch_oct_copy(resident_pack(nvar, brick, vec), false, s), "scatter launch");
+  HCHK(hipMemcpyAsync(host, vec.p, sizeof(double) * nvar * g_host.res_ncell, hipMemcpyDeviceToHost, s), what);
+  HCHK(hipStreamSynchronize(s), "sync");
+  return 0;
+}
+
+// ---- gravity on the resident level (SURVEY.md 8f rank 2, first part) -------------------------
+// The acceleration lives in bf next to the hydro state: loaded from the host array on first use,
+// rewritten by ramses_amd_force_fine_f90 every step.
+static int resident_ensure_grav(const double *f) {
+  HostCtx &H = g_host;
+  if (H.res_grav_valid) return 0;
+  if (!f) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  hipStream_t s = nullptr;
+  HCHK(H.fvec.ensure(sizeof(double) * 3 * H.res_ncell), "hipMalloc f");
+  HCHK(H.bf.ensure(sizeof(double) * 3 * resident_cells()), "hipMalloc f brick");
+  HCHK(hipMemcpyAsync(H.fvec.p, f, sizeof(double) * 3 * H.res_ncell, hipMemcpyHostToDevice, s), "H2D f");
+  HCHK(launch_oct_copy(resident_pack(3, H.bf, H.fvec), true, s), "gather launch");
+  H.res_grav_valid = true;
+  return 0;
+}
+
 // courant_fine (hydro/courant_fine.f90:1-159) on the resident level:
 // out4 = {dt_loc, mass_loc, sum(E*vol) ("ekin_loc"), eint_loc}.  dt is
 // bit-identical (min is order independent); the three sums are accumulated in
 // a different order than the reference's serial loop (diagnostics only).
-int ramses_amd_resident_courant_f90(const ramses_amd_hydro_params *p, int ilevel, int ngrid,
-                                    const int *igrid, const double *xg, int64_t ngridmax,
-                                    int64_t ncoarse, int nx_loc, const double *uold, double dx,
-                                    double dt_in, double *out4) {
+// grav: with the gravity term of cmpdt (:77-85), the acceleration loaded from f unless the device holds it already
+static int resident_courant(const ramses_amd_hydro_params *p, int ilevel, int ngrid, const int *igrid, const double *xg,
+                            int64_t ngridmax, int64_t ncoarse, int nx_loc, const double *uold, bool grav, const double *f,
+                            double dx, double dt_in, double *out4) {
   if (!out4) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (int rc = resident_ensure(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold)) return rc;
+  if (grav) if (int rc = resident_ensure_grav(f)) return rc;
   HostCtx &H = g_host;
-  const int n = 1 << ilevel;
   hipStream_t s = nullptr;
-  ramses_amd_brick b;
-  ramses_amd_brick_dense(&b, n, n, n, 0);
+  const ramses_amd_brick b = dense_brick(1 << ilevel);
   if (int rc = ramses_amd_courant_init(p, dx, H.red.as<double>(), s)) return rc;
-  if (int rc = ramses_amd_courant_brick(p, &b, H.bold.as<double>(), nullptr, dx, H.red.as<double>(), s)) return rc;
+  if (int rc = ramses_amd_courant_brick(p, &b, H.bold.as<double>(), grav ? H.bf.as<double>() : nullptr, dx, H.red.as<double>(), s)) return rc;
   HCHK(hipMemcpyAsync(out4, H.red.p, sizeof(double) * 4, hipMemcpyDeviceToHost, s), "D2H courant");
   HCHK(hipStreamSynchronize(s), "sync");
   if (dt_in < out4[0]) out4[0] = dt_in;   // dt_loc starts from dtnew(ilevel)
   return 0;
 }
+int ramses_amd_resident_courant_f90(const ramses_amd_hydro_params *p, int ilevel, int ngrid,
+                                    const int *igrid, const double *xg, int64_t ngridmax,
+                                    int64_t ncoarse, int nx_loc, const double *uold, double dx,
+                                    double dt_in, double *out4) {
+  return resident_courant(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold, false, nullptr, dx, dt_in, out4);
+}
 
 // set_unew + godunov_fine on the resident level: bold -> bnew (= uold + flux differences)
+// grav: with the gravity predictor (godfine1 :637-647, ctoprim)
+static int resident_godunov(const ramses_amd_hydro_params *p, int ilevel, int ngrid, const int *igrid, const double *xg,
+                            int64_t ngridmax, int64_t ncoarse, int nx_loc, const double *uold, bool grav, const double *f,
+                            double dx, double dt) {
+  if (int rc = resident_ensure(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold)) return rc;
+  if (grav) if (int rc = resident_ensure_grav(f)) return rc;
+  HostCtx &H = g_host;
+  const ramses_amd_brick b = dense_brick(1 << ilevel);
+  if (int rc = ramses_amd_godunov_brick(p, &b, H.bold.as<double>(), grav ? H.bf.as<double>() : nullptr, H.bnew.as<double>(), dx, dt, nullptr)) return rc;
+  H.res_new_ready = true;
+  return 0;
+}
 int ramses_amd_resident_godunov_f90(const ramses_amd_hydro_params *p, int ilevel, int ngrid,
                                     const int *igrid, const double *xg, int64_t ngridmax,
                                     int64_t ncoarse, int nx_loc, const double *uold, double dx, double dt) {
-  if (int rc = resident_ensure(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold)) return rc;
-  HostCtx &H = g_host;
-  const int n = 1 << ilevel;
-  ramses_amd_brick b;
-  ramses_amd_brick_dense(&b, n, n, n, 0);
-  if (int rc = ramses_amd_godunov_brick(p, &b, H.bold.as<double>(), nullptr, H.bnew.as<double>(), dx, dt, nullptr)) return rc;
-  H.res_new_ready = true;
+  return resident_godunov(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold, false, nullptr, dx, dt);
+}
+
+// the entry points that work on what a resident level holds: `what` opens the message
+static int resident_level_is(int ilevel, const char *what) {
+  const HostCtx &H = g_host;
+  if (!H.res_valid || H.res_level != ilevel) return fail(RAMSES_AMD_EINVAL, "%s: level %d is not resident", what, ilevel);
+  return 0;
+}
+// ... and on the result of a godunov_fine that set_uold has not taken yet
+static int resident_pending(int ilevel, const char *what) {
+  if (int rc = resident_level_is(ilevel, what)) return rc;
+  if (!g_host.res_new_ready) return fail(RAMSES_AMD_EINVAL, "%s: no godunov_fine result pending on level %d", what, ilevel);
   return 0;
 }
 
 // set_uold on the resident level: the new state becomes the current one
 static int resident_swap(int ilevel) {
   HostCtx &H = g_host;
-  if (!H.res_valid || H.res_level != ilevel) return fail(RAMSES_AMD_EINVAL, "set_uold: level %d is not resident", ilevel);
-  if (!H.res_new_ready) return fail(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending on level %d", ilevel);
+  if (int rc = resident_pending(ilevel, "set_uold")) return rc;
   DevBuf t = H.bold; H.bold = H.bnew; H.bnew = t;
   H.res_new_ready = false;
   H.res_host_stale = true;
@@ -697,11 +674,8 @@ int ramses_amd_resident_set_uold_f90(int ilevel) {
 // hydro/godunov_fine.f90:166) on the pending result, from the state it was swept from; then the swap
 int ramses_amd_resident_set_uold_pdv_f90(const ramses_amd_hydro_params *p, int ilevel, double dx, double dt) {
   HostCtx &H = g_host;
-  if (!H.res_valid || H.res_level != ilevel) return fail(RAMSES_AMD_EINVAL, "set_uold: level %d is not resident", ilevel);
-  if (!H.res_new_ready) return fail(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending on level %d", ilevel);
-  const int n = 1 << ilevel;
-  ramses_amd_brick b;
-  ramses_amd_brick_dense(&b, n, n, n, 0);
+  if (int rc = resident_pending(ilevel, "set_uold")) return rc;
+  const ramses_amd_brick b = dense_brick(1 << ilevel);
   if (int rc = ramses_amd_pdv_brick(p, &b, H.bold.as<double>(), H.bnew.as<double>(), dx, dt, nullptr)) return rc;
   return resident_swap(ilevel);
 }
@@ -711,42 +685,9 @@ int ramses_amd_resident_sync_host_f90(double *uold) {
   HostCtx &H = g_host;
   if (!H.res_valid || !H.res_host_stale) return 0;
   if (uold != H.res_host_uold) return fail(RAMSES_AMD_EINVAL, "sync_host: not the array the level was loaded from");
-  const int n = 1 << H.res_level;
-  const long N = (long)n * n * n;
-  hipStream_t s = nullptr;
-  PackArgs A;
-  A.igrid = H.igrid.as<int>(); A.octorg = H.octorg.as<long>();
-  A.ngrid = H.res_ngrid; A.n = n; A.nvar = H.res_nvar;
-  A.ncoarse = H.res_ncoarse; A.ngridmax = H.res_ngridmax; A.ncell = H.res_ncell; A.pitch_var = N;
-  A.brick = H.bold.as<double>(); A.cellvec = H.uold.as<double>();
-  HCHK(launch_oct_copy(A, false, s), "scatter launch");
   // cells of other levels come back with the values they were loaded with
-  HCHK(hipMemcpyAsync(uold, H.uold.p, sizeof(double) * H.res_nvar * H.res_ncell, hipMemcpyDeviceToHost, s), "D2H uold");
-  HCHK(hipStreamSynchronize(s), "sync");
+  if (int rc = resident_to_host(H.res_nvar, H.bold, H.uold, uold, "D2H uold", nullptr)) return rc;
   H.res_host_stale = false;
-  return 0;
-}
-
-// ---- gravity on the resident level (SURVEY.md 8f rank 2, first part) -------------------------
-// The acceleration lives in bf next to the hydro state: loaded from the host array on first use,
-// rewritten by ramses_amd_force_fine_f90 every step.
-static int resident_ensure_grav(const double *f) {
-  HostCtx &H = g_host;
-  if (H.res_grav_valid) return 0;
-  if (!f) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  const int n = 1 << H.res_level;
-  const long N = (long)n * n * n;
-  hipStream_t s = nullptr;
-  HCHK(H.fvec.ensure(sizeof(double) * 3 * H.res_ncell), "hipMalloc f");
-  HCHK(H.bf.ensure(sizeof(double) * 3 * N), "hipMalloc f brick");
-  HCHK(hipMemcpyAsync(H.fvec.p, f, sizeof(double) * 3 * H.res_ncell, hipMemcpyHostToDevice, s), "H2D f");
-  PackArgs G;
-  G.igrid = H.igrid.as<int>(); G.octorg = H.octorg.as<long>();
-  G.ngrid = H.res_ngrid; G.n = n; G.nvar = 3;
-  G.ncoarse = H.res_ncoarse; G.ngridmax = H.res_ngridmax; G.ncell = H.res_ncell; G.pitch_var = N;
-  G.brick = H.bf.as<double>(); G.cellvec = H.fvec.as<double>();
-  HCHK(launch_oct_copy(G, true, s), "gather launch");
-  H.res_grav_valid = true;
   return 0;
 }
 
@@ -757,10 +698,8 @@ int ramses_amd_resident_synchro_f90(const ramses_amd_hydro_params *p, int ilevel
   if (int rc = resident_ensure(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold)) return rc;
   if (int rc = resident_ensure_grav(f)) return rc;
   HostCtx &H = g_host;
-  const int n = 1 << ilevel;
-  const long N = (long)n * n * n;
   if (H.res_new_ready) return fail(RAMSES_AMD_EINVAL, "synchro_hydro_fine between godunov_fine and set_uold");
-  hipError_t e = launch_synchro_hydro(H.bold.as<double>(), H.bf.as<double>(), N, dteff, p->smallr, nullptr);
+  hipError_t e = launch_synchro_hydro(H.bold.as<double>(), H.bf.as<double>(), resident_cells(), dteff, p->smallr, nullptr);
   if (e != hipSuccess) return hipfail(e, "synchro_hydro launch");
   H.res_host_stale = true;
   return 0;
@@ -771,20 +710,7 @@ int ramses_amd_resident_courant_grav_f90(const ramses_amd_hydro_params *p, int i
                                          const int *igrid, const double *xg, int64_t ngridmax,
                                          int64_t ncoarse, int nx_loc, const double *uold, const double *f,
                                          double dx, double dt_in, double *out4) {
-  if (!out4) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (int rc = resident_ensure(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold)) return rc;
-  if (int rc = resident_ensure_grav(f)) return rc;
-  HostCtx &H = g_host;
-  const int n = 1 << ilevel;
-  hipStream_t s = nullptr;
-  ramses_amd_brick b;
-  ramses_amd_brick_dense(&b, n, n, n, 0);
-  if (int rc = ramses_amd_courant_init(p, dx, H.red.as<double>(), s)) return rc;
-  if (int rc = ramses_amd_courant_brick(p, &b, H.bold.as<double>(), H.bf.as<double>(), dx, H.red.as<double>(), s)) return rc;
-  HCHK(hipMemcpyAsync(out4, H.red.p, sizeof(double) * 4, hipMemcpyDeviceToHost, s), "D2H courant");
-  HCHK(hipStreamSynchronize(s), "sync");
-  if (dt_in < out4[0]) out4[0] = dt_in;
-  return 0;
+  return resident_courant(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold, true, f, dx, dt_in, out4);
 }
 
 // set_unew + godunov_fine with the gravity predictor (godfine1 :637-647, ctoprim)
@@ -792,27 +718,16 @@ int ramses_amd_resident_godunov_grav_f90(const ramses_amd_hydro_params *p, int i
                                          const int *igrid, const double *xg, int64_t ngridmax,
                                          int64_t ncoarse, int nx_loc, const double *uold, const double *f,
                                          double dx, double dt) {
-  if (int rc = resident_ensure(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold)) return rc;
-  if (int rc = resident_ensure_grav(f)) return rc;
-  HostCtx &H = g_host;
-  const int n = 1 << ilevel;
-  ramses_amd_brick b;
-  ramses_amd_brick_dense(&b, n, n, n, 0);
-  if (int rc = ramses_amd_godunov_brick(p, &b, H.bold.as<double>(), H.bf.as<double>(), H.bnew.as<double>(), dx, dt, nullptr)) return rc;
-  H.res_new_ready = true;
-  return 0;
+  return resident_godunov(p, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, nx_loc, uold, true, f, dx, dt);
 }
 
 // set_uold with add_gravity_source_terms (hydro/godunov_fine.f90:160-162,237-289) before the swap
 int ramses_amd_resident_set_uold_grav_f90(const ramses_amd_hydro_params *p, int ilevel, double dt) {
   HostCtx &H = g_host;
   if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (!H.res_valid || H.res_level != ilevel) return fail(RAMSES_AMD_EINVAL, "set_uold: level %d is not resident", ilevel);
-  if (!H.res_new_ready) return fail(RAMSES_AMD_EINVAL, "set_uold: no godunov_fine result pending on level %d", ilevel);
+  if (int rc = resident_pending(ilevel, "set_uold")) return rc;
   if (!H.res_grav_valid) return fail(RAMSES_AMD_EINVAL, "set_uold: no acceleration on the device for level %d", ilevel);
-  const int n = 1 << ilevel;
-  const long N = (long)n * n * n;
-  hipError_t e = launch_add_gravity_source(H.bnew.as<double>(), H.bold.as<double>(), H.bf.as<double>(), N, dt, p->smallr, nullptr);
+  hipError_t e = launch_add_gravity_source(H.bnew.as<double>(), H.bold.as<double>(), H.bf.as<double>(), resident_cells(), dt, p->smallr, nullptr);
   if (e != hipSuccess) return hipfail(e, "add_gravity_source launch");
   return ramses_amd_resident_set_uold_f90(ilevel);
 }
@@ -822,18 +737,7 @@ int ramses_amd_resident_sync_density_f90(double *uold) {
   HostCtx &H = g_host;
   if (!H.res_valid || !H.res_host_stale) return 0;
   if (uold != H.res_host_uold) return fail(RAMSES_AMD_EINVAL, "sync_density: not the array the level was loaded from");
-  const int n = 1 << H.res_level;
-  const long N = (long)n * n * n;
-  hipStream_t s = nullptr;
-  PackArgs A;
-  A.igrid = H.igrid.as<int>(); A.octorg = H.octorg.as<long>();
-  A.ngrid = H.res_ngrid; A.n = n; A.nvar = 1;
-  A.ncoarse = H.res_ncoarse; A.ngridmax = H.res_ngridmax; A.ncell = H.res_ncell; A.pitch_var = N;
-  A.brick = H.bold.as<double>(); A.cellvec = H.uold.as<double>();
-  HCHK(launch_oct_copy(A, false, s), "scatter launch");
-  HCHK(hipMemcpyAsync(uold, H.uold.p, sizeof(double) * H.res_ncell, hipMemcpyDeviceToHost, s), "D2H density");
-  HCHK(hipStreamSynchronize(s), "sync");
-  return 0;   // the other variables of the host array stay stale
+  return resident_to_host(1, H.bold, H.uold, uold, "D2H density", nullptr);   // the other variables of the host array stay stale
 }
 
 // ---- the Poisson branch of amr_step on the resident level (second part) ----------
@@ -858,11 +762,11 @@ int ramses_amd_resident_rho_fine_f90(const ramses_amd_hydro_params *p, int ileve
   HCHK(H.brho.ensure(sizeof(double) * N), "hipMalloc rho brick");
   HCHK(H.octidx.ensure(sizeof(int) * (size_t)(N / 8)), "hipMalloc oct index");
   HCHK(H.diag.ensure(sizeof(double) * (FORCE_DIAG_SCRATCH + 8)), "hipMalloc");
-  HCHK(launch_oct_index(H.octorg.as<long>(), ngrid, n, H.octidx.as<int>(), s), "oct index launch");
+  HCHK(launch_oct_index(H.octs.octorg.as<long>(), ngrid, n, H.octidx.as<int>(), s), "oct index launch");
   RhoArgs A;
   A.dens = H.bold.as<double>();          // variable 1 of the resident state
   A.rho = H.brho.as<double>();
-  A.octorg = H.octorg.as<long>(); A.octidx = H.octidx.as<int>();
+  A.octorg = H.octs.octorg.as<long>(); A.octidx = H.octidx.as<int>();
   A.n = n; A.ngrid = ngrid; A.nvector = nvector;
   A.dx = std::ldexp(1.0, -ilevel);
   A.scale = boxlen / (double)nx_loc;
@@ -886,7 +790,7 @@ int ramses_amd_resident_multigrid_f90(int ilevel, double rho_tot, double fourpi,
                                       int *iters, double *err) {
   HostCtx &H = g_host;
   if (!safe_mode) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (!H.res_valid || H.res_level != ilevel) return fail(RAMSES_AMD_EINVAL, "multigrid_fine: level %d is not resident", ilevel);
+  if (int rc = resident_level_is(ilevel, "multigrid_fine")) return rc;
   if (!H.res_rho_valid) return fail(RAMSES_AMD_EINVAL, "multigrid_fine: no density deposit on the device (rho_fine)");
   const int n = 1 << ilevel;
   const long N = (long)n * n * n;
@@ -909,7 +813,7 @@ int ramses_amd_resident_multigrid_f90(int ilevel, double rho_tot, double fourpi,
 int ramses_amd_resident_force_fine_f90(int ilevel, double fact, double *diag2) {
   HostCtx &H = g_host;
   if (!diag2) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (!H.res_valid || H.res_level != ilevel) return fail(RAMSES_AMD_EINVAL, "force_fine: level %d is not resident", ilevel);
+  if (int rc = resident_level_is(ilevel, "force_fine")) return rc;
   if (!H.res_phi_valid || !H.res_rho_valid) return fail(RAMSES_AMD_EINVAL, "force_fine: no potential on the device (multigrid_fine)");
   const int n = 1 << ilevel;
   const long N = (long)n * n * n;
@@ -931,25 +835,16 @@ int ramses_amd_resident_sync_poisson_f90(double *phi, double *f, double *rho) {
   HostCtx &H = g_host;
   if (!H.res_valid || !H.res_pois_host_stale) return 0;
   if (!phi || !f || !rho) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  const int n = 1 << H.res_level;
-  const long N = (long)n * n * n;
   const long ncell = H.res_ncell;
   hipStream_t s = nullptr;
   HCHK(H.cellvec1.ensure(sizeof(double) * 3 * ncell), "hipMalloc");
-  PackArgs A;
-  A.igrid = H.igrid.as<int>(); A.octorg = H.octorg.as<long>();
-  A.ngrid = H.res_ngrid; A.n = n;
-  A.ncoarse = H.res_ncoarse; A.ngridmax = H.res_ngridmax; A.ncell = ncell; A.pitch_var = N;
-  struct { bool ok; double *host; double *brick; int nvar; } col[3] = {
-      {H.res_phi_valid, phi, H.bphi.as<double>(), 1}, {H.res_grav_valid, f, H.bf.as<double>(), 3}, {H.res_rho_valid, rho, H.brho.as<double>(), 1}};
+  struct { bool ok; double *host; const DevBuf *brick; int nvar; } col[3] = {
+      {H.res_phi_valid, phi, &H.bphi, 1}, {H.res_grav_valid, f, &H.bf, 3}, {H.res_rho_valid, rho, &H.brho, 1}};
   for (auto &c : col) {
     if (!c.ok) continue;
     // cells of other levels keep their host values: scatter into a device copy of the host vector
     HCHK(hipMemcpyAsync(H.cellvec1.p, c.host, sizeof(double) * c.nvar * ncell, hipMemcpyHostToDevice, s), "H2D");
-    A.nvar = c.nvar; A.brick = c.brick; A.cellvec = H.cellvec1.as<double>();
-    HCHK(launch_oct_copy(A, false, s), "scatter launch");
-    HCHK(hipMemcpyAsync(c.host, H.cellvec1.p, sizeof(double) * c.nvar * ncell, hipMemcpyDeviceToHost, s), "D2H");
-    HCHK(hipStreamSynchronize(s), "sync");
+    if (int rc = resident_to_host(c.nvar, *c.brick, H.cellvec1, c.host, "D2H", s)) return rc;
   }
   H.res_pois_host_stale = false;
   return 0;

@@ -39,7 +39,7 @@
 #include "../../include/ramses_amd.h"
 #include "mhd_assemble.hpp"
 #include "mhd_host.hpp"
-#include "pack_args.hpp"
+#include "level_brick.hpp"
 
 using namespace ramses_amd;
 using namespace ramses_amd::mhd;
@@ -495,56 +495,25 @@ constexpr long WORK_DOUBLES_PER_CELL = 8 + 3 + NTR + 15 + 3;
 
 #ifndef RAMSES_AMD_MHD_FAST_TU
 // ---- a fully refined periodic level of the reference's arrays as a brick on the device: what the staged and the resident
-// entry points share.  Its buffers: the host's cell vectors, the level as two bricks, the sweep's workspace, the oct lists and
-// origins of the gather and the scatter ---------------------------------------------------------------------------------
+// entry points share on top of level_brick.hpp.  MHD's own buffers: the host's cell vectors, the level as two bricks, the
+// sweep's workspace ------------------------------------------------------------------------------------------------------
 struct LevelBufs {
-  DevBuf vec, cur, nxt, work, ig, xg, org, flag;
+  DevBuf vec, cur, nxt, work;
 };
 
-// what both ask of the level (`who` opens the nx_loc message); *n: its cells per direction
-int level_check(const char *who, int ilevel, int ngrid, const int *igrid, const double *xg, int nx_loc, const double *uold, int *n) {
-  if (!igrid || !xg || !uold) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  if (nx_loc != 1) return fail(RAMSES_AMD_EUNSUPPORTED, "%s needs a periodic box with nx=ny=nz=1 (got nx_loc=%d)", who, nx_loc);
-  if (ilevel < 2 || ilevel > 10) return fail(RAMSES_AMD_EINVAL, "level out of range");
-  *n = 1 << ilevel;
-  if ((long)ngrid * 8 != (long)*n * *n * *n) return fail(RAMSES_AMD_EUNSUPPORTED, "level %d is not fully refined on this rank (ngrid=%d)", ilevel, ngrid);
-  return 0;
-}
+constexpr int MHD_LEVEL_MIN = 2, MHD_LEVEL_MAX = 10;   // of level_shape
 
-// the copy between B.cur and the cell vectors in B.vec (launch_oct_copy: gather or scatter)
-PackArgs level_pack(const LevelBufs &B, int ngrid, int n, long ncoarse, long ngridmax) {
-  PackArgs PA;
-  PA.igrid = B.ig.as<const int>(); PA.octorg = B.org.as<const long>();
-  PA.ngrid = ngrid; PA.n = n; PA.nvar = NF;
-  PA.ncoarse = ncoarse; PA.ngridmax = ngridmax; PA.ncell = ncoarse + 8 * ngridmax; PA.pitch_var = (long)n * n * n;
-  PA.brick = B.cur.as<double>(); PA.cellvec = B.vec.as<double>();
-  return PA;
-}
-
-// uold(1:ncell,1:nvar+3) goes up into B.vec and the level's cells are gathered into the brick B.cur; B.nxt and B.work are
-// sized for a sweep of it, B.ig / B.org keep the oct lists for the scatter back
-int level_upload(LevelBufs &B, int ilevel, int ngrid, const int *igrid, const double *xg, long ngridmax, long ncoarse, int n,
-                 const double *uold, hipStream_t s) {
-  const long N = (long)n * n * n, ncell = ncoarse + 8 * ngridmax;
-  HCHK(B.vec.ensure(sizeof(double) * NF * ncell), "hipMalloc cell vectors");
-  HCHK(B.cur.ensure(sizeof(double) * NF * N), "hipMalloc brick");
-  HCHK(B.nxt.ensure(sizeof(double) * NF * N), "hipMalloc brick");
-  HCHK(B.work.ensure((size_t)ramses_amd_mhd_workspace_bytes(n, n, n)), "hipMalloc workspace");
-  HCHK(B.org.ensure(sizeof(long) * ngrid), "hipMalloc octorg");
-  HCHK(B.ig.ensure(sizeof(int) * ngrid), "hipMalloc igrid");
-  HCHK(B.xg.ensure(sizeof(double) * 3 * ngridmax), "hipMalloc xg");
-  HCHK(B.flag.ensure(sizeof(int)), "hipMalloc flag");
-  HCHK(hipMemcpyAsync(B.vec.p, uold, sizeof(double) * NF * ncell, hipMemcpyHostToDevice, s), "H2D uold");
-  HCHK(hipMemcpyAsync(B.ig.p, igrid, sizeof(int) * ngrid, hipMemcpyHostToDevice, s), "H2D igrid");
-  HCHK(hipMemcpyAsync(B.xg.p, xg, sizeof(double) * 3 * ngridmax, hipMemcpyHostToDevice, s), "H2D xg");
-  HCHK(hipMemsetAsync(B.flag.p, 0, sizeof(int), s), "memset");
-  const double skip[3] = {0.0, 0.0, 0.0};
-  HCHK(launch_oct_origin(B.ig.as<int>(), B.xg.as<double>(), ngridmax, ngrid, n, skip, B.org.as<long>(), B.flag.as<int>(), s), "oct origin launch");
-  int bad = 0;
-  HCHK(hipMemcpyAsync(&bad, B.flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "D2H flag");
-  HCHK(hipStreamSynchronize(s), "sync");
-  if (bad) return fail(RAMSES_AMD_EINVAL, "%d octs of level %d do not sit on the level lattice", bad, ilevel);
-  HCHK(launch_oct_copy(level_pack(B, ngrid, n, ncoarse, ngridmax), true, s), "gather launch");
+// uold(1:ncell,1:nvar+3) goes up into B.vec and the level's cells are gathered into the brick B.cur; B.nxt and B.work are sized
+// for a sweep of it, O keeps the oct lists for the scatter back
+int mhd_level_upload(LevelBufs &B, LevelOcts &O, const LevelShape &L, int ilevel, int ngrid, const int *igrid, const double *xg,
+                     long ngridmax, long ncoarse, const double *uold, hipStream_t s) {
+  HCHK(B.vec.ensure(sizeof(double) * NF * L.ncell), "hipMalloc cell vectors");
+  HCHK(B.cur.ensure(sizeof(double) * NF * L.N), "hipMalloc brick");
+  HCHK(B.nxt.ensure(sizeof(double) * NF * L.N), "hipMalloc brick");
+  HCHK(B.work.ensure((size_t)ramses_amd_mhd_workspace_bytes(L.n, L.n, L.n)), "hipMalloc workspace");
+  HCHK(hipMemcpyAsync(B.vec.p, uold, sizeof(double) * NF * L.ncell, hipMemcpyHostToDevice, s), "H2D uold");
+  if (int rc = level_octs_upload(O, ilevel, L.n, ngrid, igrid, xg, ngridmax, s)) return rc;
+  HCHK(launch_oct_copy(level_pack(O, ngrid, L.n, NF, ncoarse, ngridmax, B.cur.as<double>(), B.vec.as<double>()), true, s), "gather launch");
   return 0;
 }
 #endif  // !RAMSES_AMD_MHD_FAST_TU
@@ -646,19 +615,19 @@ int MHD_BRICK_FN(const ramses_amd_mhd_params *p, int nx, int ny, int nz, const d
 int ramses_amd_mhd_godunov_fine_f90(const ramses_amd_mhd_params *p, int ilevel, int ngrid, const int *igrid, const double *xg,
                                     int64_t ngridmax, int64_t ncoarse, int nx_loc, const double *uold, double *unew, double dx,
                                     double dt) {
-  if (!unew) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  int n = 0;
-  if (int rc = level_check("MHD sweep on the device", ilevel, ngrid, igrid, xg, nx_loc, uold, &n)) return rc;
+  if (!unew || !igrid || !xg || !uold) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  LevelShape L;
+  if (int rc = level_shape("MHD sweep on the device", ilevel, MHD_LEVEL_MIN, MHD_LEVEL_MAX, ngrid, nx_loc, ngridmax, ncoarse, &L)) return rc;
+  const int n = L.n;
   static LevelBufs B;
+  static LevelOcts O;
   hipStream_t s = nullptr;
-  if (int rc = level_upload(B, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, n, uold, s)) return rc;
+  if (int rc = mhd_level_upload(B, O, L, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, uold, s)) return rc;
   if (int rc = ramses_amd_mhd_godunov_brick(p, n, n, n, B.cur.as<double>(), B.nxt.as<double>(), dx, dt, B.work.p, (int64_t)B.work.cap, s)) return rc;
   // unew of the level's cells: the other cells of the host array keep their values (H2D of unew first)
-  const size_t vec_bytes = sizeof(double) * NF * (ncoarse + 8 * ngridmax);
+  const size_t vec_bytes = sizeof(double) * NF * L.ncell;
   HCHK(hipMemcpyAsync(B.vec.p, unew, vec_bytes, hipMemcpyHostToDevice, s), "H2D unew");
-  PackArgs PA = level_pack(B, ngrid, n, ncoarse, ngridmax);
-  PA.brick = B.nxt.as<double>();
-  HCHK(launch_oct_copy(PA, false, s), "scatter launch");
+  HCHK(launch_oct_copy(level_pack(O, ngrid, n, NF, ncoarse, ngridmax, B.nxt.as<double>(), B.vec.as<double>()), false, s), "scatter launch");
   HCHK(hipMemcpyAsync(unew, B.vec.p, vec_bytes, hipMemcpyDeviceToHost, s), "D2H unew");
   HCHK(hipStreamSynchronize(s), "sync");
   return 0;
@@ -671,6 +640,7 @@ int ramses_amd_mhd_godunov_fine_f90(const ramses_amd_mhd_params *p, int ilevel, 
 // ramses_amd_resident_* of the hydro solver (capi_host.hip). ---------------------------------------------------------
 namespace {
 struct MhdResident : LevelBufs {
+  LevelOcts octs;
   bool valid = false, host_stale = false, new_ready = false;
   int level = 0, ngrid = 0, n = 0;
   long ncell = 0, ncoarse = 0, ngridmax = 0;
@@ -682,17 +652,18 @@ MhdResident g_mres;
 int mres_ensure(int ilevel, int ngrid, const int *igrid, const double *xg, int64_t ngridmax, int64_t ncoarse, int nx_loc,
                 const double *uold) {
   MhdResident &R = g_mres;
-  int n = 0;
-  if (int rc = level_check("MHD residency", ilevel, ngrid, igrid, xg, nx_loc, uold, &n)) return rc;
-  const long ncell = ncoarse + 8 * ngridmax;
+  if (!igrid || !xg || !uold) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  LevelShape L;
+  if (int rc = level_shape("MHD residency", ilevel, MHD_LEVEL_MIN, MHD_LEVEL_MAX, ngrid, nx_loc, ngridmax, ncoarse, &L)) return rc;
+  const long ncell = L.ncell;
   if (R.valid && R.level == ilevel && R.ngrid == ngrid && R.h_uold == uold && R.ncell == ncell) return 0;
   if (R.valid && R.host_stale)
     return fail(RAMSES_AMD_EINVAL, "MHD residency: level %d is resident and the host array is stale; ramses_amd_mhd_resident_sync_host_f90 first", R.level);
   R.valid = false;
   HCHK(R.red.ensure(sizeof(double) * (COUR_BLOCKS * 5 + 8)), "hipMalloc reduction");
-  if (int rc = level_upload(R, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, n, uold, nullptr)) return rc;
+  if (int rc = mhd_level_upload(R, R.octs, L, ilevel, ngrid, igrid, xg, ngridmax, ncoarse, uold, nullptr)) return rc;
   R.valid = true; R.host_stale = false; R.new_ready = false;
-  R.level = ilevel; R.ngrid = ngrid; R.n = n; R.ncell = ncell; R.ncoarse = ncoarse; R.ngridmax = ngridmax; R.h_uold = uold;
+  R.level = ilevel; R.ngrid = ngrid; R.n = L.n; R.ncell = ncell; R.ncoarse = ncoarse; R.ngridmax = ngridmax; R.h_uold = uold;
   return 0;
 }
 }  // namespace
@@ -757,7 +728,7 @@ int ramses_amd_mhd_resident_sync_host_f90(double *uold) {
   if (!R.valid || !R.host_stale) return 0;
   if (uold != R.h_uold) return fail(RAMSES_AMD_EINVAL, "sync: not the array the level was loaded from");
   if (R.new_ready) return fail(RAMSES_AMD_EINVAL, "sync between godunov_fine and set_uold");
-  HCHK(launch_oct_copy(level_pack(R, R.ngrid, R.n, R.ncoarse, R.ngridmax), false, nullptr), "scatter launch");
+  HCHK(launch_oct_copy(level_pack(R.octs, R.ngrid, R.n, NF, R.ncoarse, R.ngridmax, R.cur.as<double>(), R.vec.as<double>()), false, nullptr), "scatter launch");
   HCHK(hipMemcpy(uold, R.vec.p, sizeof(double) * NF * R.ncell, hipMemcpyDeviceToHost), "D2H uold");
   R.host_stale = false;
   return 0;

@@ -26,6 +26,29 @@ def random_brick(nx, ny, nz, seed, gamma=1.4, contrast=True, nvar=5):
     return u
 
 
+def _octree_layout(u, level, rng, ngridmax, ncoarse=1):
+    """Scatter brick u[nvar,n,n,n] into RAMSES cell vectors with octs of the
+    level placed in random slots; returns (cellvec[nvar,ncell], igrid, xg, (ox, oy, oz))."""
+    nvar, n = u.shape[0], u.shape[1]
+    no = n // 2
+    ngrid = no ** 3
+    ncell = ncoarse + 8 * ngridmax
+    slots = rng.permutation(ngridmax)[:ngrid] + 1            # 1-based oct slots
+    igrid = rng.permutation(slots).astype(np.int32)          # active list order
+    xg = np.zeros((3, ngridmax))
+    vec = rng.normal(size=(nvar, ncell))                     # garbage elsewhere
+    # oct g of the active list sits at a random oct position
+    pos = rng.permutation(ngrid)
+    oz, oy, ox = np.unravel_index(pos, (no, no, no))
+    for d, o in enumerate((ox, oy, oz)):
+        xg[d, igrid - 1] = (2 * o + 1) / n
+    for ind in range(8):
+        ix, iy, iz = ind & 1, (ind >> 1) & 1, (ind >> 2) & 1
+        icell = ncoarse + ind * ngridmax + (igrid - 1)
+        vec[:, icell] = u[:, 2 * oz + iz, 2 * oy + iy, 2 * ox + ix]
+    return vec, igrid, xg, (ox, oy, oz)
+
+
 def rel_linf(a, b):
     """max |a-b| / max |b| per variable, maximised over variables."""
     worst = 0.0
