@@ -948,6 +948,35 @@ int ramses_amd_amrres_rho_mpi_deposit(int ilevel, int nvector, double boxlen_ove
 int ramses_amd_amrres_rho_mpi_finish(int ilevel, int levelmin, int nvector, const int *igrid_all, double *rho, double *multipole4);
 int ramses_amd_amrres_hydro_flag(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double err_grad_d, double err_grad_p,
                                  double err_grad_u, double floor_d, double floor_p, double floor_u, int *cells, int *ncells);
+/* Every local physical refinement criterion of a level in one pass over the resident state.  A field that is negative or zero
+ * switches its criterion off (err_grad_*: negative only, as the reference tests err_grad_* >= 0). */
+typedef struct ramses_amd_refine_crit {
+  double err_grad_d, err_grad_p, err_grad_u; /* &REFINE_PARAMS gradient thresholds (hydro_refine, hydro/godunov_utils.f90:125-263) */
+  double floor_d, floor_p, floor_u;          /* their floors */
+  double n_jeans;        /* jeans_refine(ilevel): cells per Jeans length (jeans_length_refine, hydro/hydro_flag.f90:209-255) */
+  double tail_pix;       /* the cell size boxlen/2**ilevel of that test (:213); must be > 0 when n_jeans > 0 */
+  double factG;          /* :209-210, 1 without cosmology; taken as 1 when <= 0 */
+  double thr;            /* the threshold of thr_mode 1: m_refine(ilevel)*d_scale (amr/flag_utils.f90:481-483) */
+  double var_cut_refine; /* the cut of thr_mode 2 (:467-469) */
+  int32_t thr_mode;      /* 0: off; 1: uold(:,1) >= thr (poisson_refine without poisson, :480-485); 2: uold(:,ivar_refine)/uold(:,1)
+                          * > var_cut_refine (poisson_refine's init branch, :465-470) */
+  int32_t ivar_refine;   /* the variable of thr_mode 2, 1-based: 6 .. nvar; 0 otherwise */
+} ramses_amd_refine_crit;
+/*   ramses_amd_amrres_refine_flag  hydro_flag's loop (hydro/hydro_flag.f90:80-178: hydro_refine and jeans_length_refine) and the
+ *                                  branches of poisson_refine that read uold (amr/flag_utils.f90:465-470,480-485), ORed: cells as
+ *                                  ramses_amd_amrres_hydro_flag returns them, which it equals when only the gradient fields are set
+ *   ramses_amd_amrres_mass_map     rho_fine's quasi-Lagrangian map (pm/rho_fine.f90:96-118,201-211) on the level's own cells:
+ *                                  phi_n = rho/d_scale -- where ivar_refine > 0 only in the cells with uold(ivar_refine) /
+ *                                  max(uold(1),smallr) > var_cut_refine, 0 elsewhere -- and cells = those with phi_n >= m_refine
+ *                                  (cpu_map2 == 1).  rho = NULL: the deposit the device holds (ramses_amd_amrres_rho_fine,
+ *                                  _rho_mpi_*); otherwise the host vector rho(1:ncell), whose cells of the listed octs are sent.
+ * Both refuse NULL pointers, ivar_refine outside 0 or 6 .. nvar and n_jeans > 0 with tail_pix <= 0 (RAMSES_AMD_EINVAL).
+ * ramses_amd_refine_crit_size: sizeof(ramses_amd_refine_crit) as the library was compiled (bindings check theirs against it). */
+size_t ramses_amd_refine_crit_size(void);
+int ramses_amd_amrres_refine_flag(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, const ramses_amd_refine_crit *crit,
+                                  int *cells, int *ncells);
+int ramses_amd_amrres_mass_map(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double d_scale, double m_refine,
+                               int ivar_refine, double var_cut_refine, const double *rho, int *cells, int *ncells);
 int ramses_amd_amrres_godunov(const ramses_amd_hydro_params *p, int ilevel, int ngrid, const int *igrid, double dx, double dt,
                               int nvector, int interpol_var, int interpol_type);
 /* The device numbers the octs of a resident run itself (csrc/amr_layout.hpp): the cell vectors keep the reference's formula

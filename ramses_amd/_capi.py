@@ -44,6 +44,25 @@ class Brick(C.Structure):
     ]
 
 
+class RefineCrit(C.Structure):
+    """struct ramses_amd_refine_crit: the local refinement criteria of a level (a value <= 0 switches a field off;
+    err_grad_*: a negative one)."""
+    _fields_ = [
+        ("err_grad_d", C.c_double), ("err_grad_p", C.c_double), ("err_grad_u", C.c_double),
+        ("floor_d", C.c_double), ("floor_p", C.c_double), ("floor_u", C.c_double),
+        ("n_jeans", C.c_double), ("tail_pix", C.c_double), ("factG", C.c_double),
+        ("thr", C.c_double), ("var_cut_refine", C.c_double),
+        ("thr_mode", C.c_int32), ("ivar_refine", C.c_int32),
+    ]
+
+
+def make_refine_crit(err_grad_d=-1.0, err_grad_p=-1.0, err_grad_u=-1.0, floor_d=1e-10, floor_p=1e-10, floor_u=1e-10,
+                     n_jeans=-1.0, tail_pix=0.0, factG=1.0, thr=0.0, var_cut_refine=-1.0, thr_mode=0, ivar_refine=0):
+    """Every criterion off unless asked for (the floors' defaults are the reference's, hydro/hydro_parameters.f90:50-52)."""
+    return RefineCrit(err_grad_d, err_grad_p, err_grad_u, floor_d, floor_p, floor_u, n_jeans, tail_pix, factG, thr,
+                      var_cut_refine, thr_mode, ivar_refine)
+
+
 _lib = None
 
 # every symbol include/ramses_amd.h declares: (name, restype, argtypes)
@@ -255,6 +274,9 @@ SYMBOLS = [
     ("ramses_amd_amrres_rho_mpi_deposit", _i, [_i, _i, _d]),
     ("ramses_amd_amrres_rho_mpi_finish", _i, [_i, _i, _i, _vp, _vp, _vp]),
     ("ramses_amd_amrres_hydro_flag", _i, [_PP, _i, _vp, _d, _d, _d, _d, _d, _d, _vp, _vp]),
+    ("ramses_amd_refine_crit_size", C.c_size_t, []),
+    ("ramses_amd_amrres_refine_flag", _i, [_PP, _i, _vp, C.POINTER(RefineCrit), _vp, _vp]),
+    ("ramses_amd_amrres_mass_map", _i, [_PP, _i, _vp, _d, _d, _i, _d, _vp, _vp, _vp]),
     ("ramses_amd_amrres_godunov", _i, [_PP, _i, _i, _vp, _d, _d, _i, _i, _i]),
     # AMR residency under MPI: the virtual-boundary exchanges on the resident cell vectors
     ("ramses_amd_which_column", _i, [_vp, _vp, _i64, _i]),
@@ -282,6 +304,9 @@ def lib():
             f.argtypes = args
         if L.ramses_amd_abi_check(C.sizeof(HydroParams), C.sizeof(Brick)) != 0:
             raise RamsesAmdError(L.ramses_amd_last_error().decode())
+        if L.ramses_amd_refine_crit_size() != C.sizeof(RefineCrit):
+            raise RamsesAmdError("struct ramses_amd_refine_crit: the library has %d bytes, the binding %d"
+                                 % (L.ramses_amd_refine_crit_size(), C.sizeof(RefineCrit)))
         _lib = L
     return _lib
 

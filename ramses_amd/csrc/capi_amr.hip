@@ -7,6 +7,9 @@
 //   upload_fine   hydro/interpol_hydro.f90:5-263       lvl_upload_kernel (upl: restriction, interpol_var 0/1/2)
 //   courant_fine  hydro/courant_fine.f90:1-159         lvl_courant_kernel (cmpdt on the leaf cells)
 //   hydro_flag    hydro/hydro_flag.f90:1-178 + hydro_refine hydro/godunov_utils.f90:125-263   lvl_flag_kernel
+//   every local refinement criterion in one pass: the same gradients, jeans_length_refine hydro/hydro_flag.f90:185-258,
+//                 poisson_refine's branches on uold amr/flag_utils.f90:465-470,480-485             lvl_refine_kernel
+//   rho_fine's quasi-Lagrangian refinement map    pm/rho_fine.f90:96-118,201-211                  lvl_mass_map_kernel
 // The mesh itself stays the reference's host code: before refine_fine rebuilds levels the shim brings the
 // levels it reads back to the host (sync_level), and afterwards the tree and the rebuilt levels are sent
 // again (tree, load_level) -- the other levels never leave the device.  NDIM=3, hydro only.
@@ -242,6 +245,144 @@ __global__ __launch_bounds__(256) void lvl_flag_kernel(LvlArgs A, FlagCrit F, in
       base = __shfl(base, 0, 64);
       if (flag) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int)(c + 1);
     }
+  }
+}
+
+// ---- every local refinement criterion of a level in one pass (ramses_amd_amrres_refine_flag, _mass_map) ----
+// IEEE division and square root, no contraction, whatever fast_math says: each criterion ends in a comparison and one flipped
+// flag is another mesh.
+struct RefineCrit {
+  FlagCrit F;                                  // the gradient criteria as lvl_flag_kernel has them
+  double n_jeans, tail_pix, factG, gm1, smallc2;   // jeans_length_refine (n_jeans <= 0: off)
+  double thr, var_cut;                         // thr_mode 1: uold(1) >= thr;  2: uold(ivar)/uold(1) > var_cut;  0: off
+  int thr_mode, ivar;                          // ivar: 0-based variable of thr_mode 2
+};
+// twopi/2d0 of the reference's constants module (amr/constants.f90:5-6: twopi = 6.2831853d0, not the double nearest to pi)
+#define RAMSES_PI (6.2831853 / 2.0)
+// the two neighbour cells of cell (ind, oct g) in direction d (getnborcells); a missing one is replaced by the neighbouring father
+// cell (hydro/hydro_flag.f90:107-117)
+__device__ __forceinline__ void refine_nbors(const LvlArgs &A, long c, int ind, int g, int d, long (&cn)[2]) {
+#pragma unroll
+  for (int side = 0; side < 2; side++) {
+    const int bit = (ind >> d) & 1;
+    if (bit != side) {
+      cn[side] = c + (side ? 1 : -1) * ((long)(1 << d) * A.ngridmax);
+    } else {
+      const int nb = A.nbor[(long)(2 * d + side) * A.ngridmax + g - 1];
+      const int g2 = A.son[nb - 1];
+      cn[side] = g2 > 0 ? A.ncoarse + (long)(ind ^ (1 << d)) * A.ngridmax + g2 - 1 : (long)nb - 1;
+    }
+  }
+}
+// hydro_refine (hydro/godunov_utils.f90:125-263) on a cell and its two neighbours of one direction
+__device__ __forceinline__ bool refine_grad(const FlagCrit &F, const double (&qg)[5], const double (&qm)[5], const double (&qd)[5]) {
+  bool flag = false;
+  if (F.err_grad_d >= 0.0) {
+    const double e = 2.0 * __builtin_fmax(__builtin_fabs((qd[0] - qm[0]) / (qd[0] + qm[0] + F.floor_d)),
+                                          __builtin_fabs((qm[0] - qg[0]) / (qm[0] + qg[0] + F.floor_d)));
+    flag = flag || e > F.err_grad_d;
+  }
+  if (F.err_grad_p >= 0.0) {
+    const double e = 2.0 * __builtin_fmax(__builtin_fabs((qd[4] - qm[4]) / (qd[4] + qm[4] + F.floor_p)),
+                                          __builtin_fabs((qm[4] - qg[4]) / (qm[4] + qg[4] + F.floor_p)));
+    flag = flag || e > F.err_grad_p;
+  }
+  if (F.err_grad_u >= 0.0) {
+    const double cg = __builtin_sqrt(__builtin_fmax(F.gamma * qg[4] / qg[0], F.floor_u * F.floor_u));
+    const double cm = __builtin_sqrt(__builtin_fmax(F.gamma * qm[4] / qm[0], F.floor_u * F.floor_u));
+    const double cd = __builtin_sqrt(__builtin_fmax(F.gamma * qd[4] / qd[0], F.floor_u * F.floor_u));
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const double vg = qg[1 + k], vm = qm[1 + k], vd = qd[1 + k];
+      const double e = 2.0 * __builtin_fmax(__builtin_fabs((vd - vm) / (cd + cm + __builtin_fabs(vd) + __builtin_fabs(vm) + F.floor_u)),
+                                            __builtin_fabs((vm - vg) / (cm + cg + __builtin_fabs(vm) + __builtin_fabs(vg) + F.floor_u)));
+      flag = flag || e > F.err_grad_u;
+    }
+  }
+  return flag;
+}
+// the flagged cells of a wavefront into the compact list: one atomic per wavefront (as lvl_flag_kernel)
+__device__ __forceinline__ void refine_compact(bool flag, long c, int *__restrict__ list, int *__restrict__ count) {
+  const unsigned long long m = __ballot(flag);
+  if (m) {
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(count, __popcll(m));
+    base = __shfl(base, 0, 64);
+    if (flag) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int)(c + 1);
+  }
+}
+// GRAD = false: all three err_grad_* are off and the six neighbour gathers are skipped
+template <bool GRAD>
+__global__ __launch_bounds__(256) void lvl_refine_kernel(LvlArgs A, RefineCrit X, int *__restrict__ list, int *__restrict__ count) {
+  const long total = (long)A.ngrid * 8;
+  const long span = (long)gridDim.x * blockDim.x;
+  for (long t0 = (long)blockIdx.x * blockDim.x; t0 < total; t0 += span) {
+    const long t = t0 + threadIdx.x;
+    bool flag = false;
+    long c = 0;
+    if (t < total) {
+      const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
+      const int g = A.igrid[i];
+      c = A.ncoarse + (long)ind * A.ngridmax + g - 1;
+      if (GRAD) {
+        double qm[5];
+        refine_prim(A, c, X.F, qm);
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+          long cn[2];
+          refine_nbors(A, c, ind, g, d, cn);
+          double qg[5], qd[5];
+          refine_prim(A, cn[0], X.F, qg);
+          refine_prim(A, cn[1], X.F, qd);
+          flag = flag || refine_grad(X.F, qg, qm, qd);
+        }
+      }
+      const double rho = A.uold[c];
+      if (X.n_jeans > 0.0) {
+        // jeans_length_refine (hydro/hydro_flag.f90:214-256), NDIM = 3, NENER = 0, in its operation order
+        const double dens = __builtin_fmax(rho, X.F.smallr);
+        double etherm = A.uold[c + 4 * A.ncell];
+#pragma unroll
+        for (int k = 1; k <= 3; k++) {
+          const double m = A.uold[c + (long)k * A.ncell];
+          etherm = etherm - 0.5 * (m * m) / dens;
+        }
+        double tempe = etherm / dens * X.gm1;
+        tempe = __builtin_fmax(tempe, X.smallc2);
+        const double lamb = __builtin_sqrt(tempe * RAMSES_PI / dens / X.factG);
+        flag = flag || X.n_jeans * X.tail_pix >= lamb;
+      }
+      if (X.thr_mode == 1) {
+        flag = flag || rho >= X.thr;                                                   // amr/flag_utils.f90:483
+      } else if (X.thr_mode == 2) {
+        flag = flag || A.uold[c + (long)X.ivar * A.ncell] / rho > X.var_cut;           // :467-469 (no smallr floor there)
+      }
+    }
+    refine_compact(flag, c, list, count);
+  }
+}
+// rho_fine's quasi-Lagrangian map (pm/rho_fine.f90:96-118,201-211): phi_n = rho/d_scale (IVAR: only where the scalar passes the
+// cut, 0 elsewhere -- phi was reset at :74), listed when phi_n >= m_refine
+template <bool IVAR>
+__global__ __launch_bounds__(256) void lvl_mass_map_kernel(LvlArgs A, const double *__restrict__ rho, double d_scale, double m_refine, int ivar,
+                                                           double var_cut, double smallr, int *__restrict__ list, int *__restrict__ count) {
+  const long total = (long)A.ngrid * 8;
+  const long span = (long)gridDim.x * blockDim.x;
+  for (long t0 = (long)blockIdx.x * blockDim.x; t0 < total; t0 += span) {
+    const long t = t0 + threadIdx.x;
+    bool flag = false;
+    long c = 0;
+    if (t < total) {
+      const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
+      c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
+      double phi_n = 0.0;
+      bool take = true;
+      if (IVAR) take = A.uold[c + (long)ivar * A.ncell] / __builtin_fmax(A.uold[c], smallr) > var_cut;
+      if (take) phi_n = rho[c] / d_scale;
+      flag = phi_n >= m_refine;
+    }
+    refine_compact(flag, c, list, count);
   }
 }
 
@@ -1288,6 +1429,109 @@ int ramses_amd_amrres_hydro_flag(const ramses_amd_hydro_params *p, int ngrid, co
   }
   *ncells = n;
   return check_lists(R, "hydro_flag");
+}
+
+namespace {
+// the compact list a flag kernel left behind d_count, into the host's cell numbers, ascending
+int fetch_flag_list(AmrRes &R, int ngrid, int *d_count, int *cells, int *ncells, const char *who) {
+  int *d_list = d_count + 1;
+  int n = 0;
+  HCHK(hipMemcpy(&n, d_count, sizeof(int), hipMemcpyDeviceToHost), "D2H flag count");
+  if (n < 0 || (long)n > 8L * ngrid) return fail(RAMSES_AMD_EHIP, "%s: bad flag count %d", who, n);
+  if (n > 0) {
+    if (R.map.on) hipLaunchKernelGGL(amrlayout::cells_d2h_kernel, dim3(amrlayout::grid1(n)), dim3(256), 0, nullptr, d_list, n, R.map.iperm.as<int>(), R.ncoarse, R.ngh, R.ngridmax);
+    HCHK(hipMemcpy(cells, d_list, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost), "D2H flagged cells");
+    std::sort(cells, cells + n);
+  }
+  *ncells = n;
+  return check_lists(R, who);
+}
+int check_ivar_refine(const char *who, int ivar_refine, int nvar) {
+  if (ivar_refine != 0 && (ivar_refine < 6 || ivar_refine > nvar))
+    return fail(RAMSES_AMD_EINVAL, "%s: ivar_refine=%d must be 0 or a passive scalar 6 .. nvar=%d", who, ivar_refine, nvar);
+  return 0;
+}
+}  // namespace
+
+size_t ramses_amd_refine_crit_size(void) { return sizeof(ramses_amd_refine_crit); }
+
+// hydro_flag's loop over the level (hydro/hydro_flag.f90:80-178: hydro_refine on the three directions, jeans_length_refine
+// :185-258) and poisson_refine's branches that read uold (amr/flag_utils.f90:465-470 init with ivar_refine, :480-485 without
+// poisson), ORed in one pass over the resident state; the list as ramses_amd_amrres_hydro_flag returns it
+int ramses_amd_amrres_refine_flag(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, const ramses_amd_refine_crit *crit,
+                                  int *cells, int *ncells) {
+  const char *who = "ramses_amd_amrres_refine_flag";
+  if (int rc_ = refuse_amr(p, who)) return rc_;
+  if (!p) return fail(RAMSES_AMD_EINVAL, "%s: NULL argument p", who);
+  if (!crit) return fail(RAMSES_AMD_EINVAL, "%s: NULL argument crit", who);
+  if (!cells) return fail(RAMSES_AMD_EINVAL, "%s: NULL argument cells", who);
+  if (!ncells) return fail(RAMSES_AMD_EINVAL, "%s: NULL argument ncells", who);
+  *ncells = 0;
+  if (crit->n_jeans > 0.0 && !(crit->tail_pix > 0.0))
+    return fail(RAMSES_AMD_EINVAL, "%s: n_jeans=%g needs tail_pix > 0 (got %g)", who, crit->n_jeans, crit->tail_pix);
+  if (crit->thr_mode < 0 || crit->thr_mode > 2) return fail(RAMSES_AMD_EINVAL, "%s: thr_mode=%d must be 0, 1 or 2", who, crit->thr_mode);
+  if (int rc = check_ivar_refine(who, crit->ivar_refine, p->nvar)) return rc;
+  if (crit->thr_mode == 2 && crit->ivar_refine == 0) return fail(RAMSES_AMD_EINVAL, "%s: thr_mode=2 needs ivar_refine", who);
+  LvlArgs A;
+  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
+  if (ngrid == 0) return 0;
+  if (A.nvar < 5) return fail(RAMSES_AMD_EUNSUPPORTED, "%s: NVAR", who);
+  if (crit->ivar_refine > A.nvar) return fail(RAMSES_AMD_EINVAL, "%s: ivar_refine=%d beyond the resident state's nvar=%d", who, crit->ivar_refine, A.nvar);
+  AmrRes &R = g_ar;
+  if (int rc = sorted_list(R, A)) return rc;          // (the flagged cells come back sorted anyway)
+  HCHK(R.okbuf.ensure(sizeof(int) * (8 * (size_t)ngrid + 1)), "hipMalloc");
+  int *d_count = R.okbuf.as<int>();
+  HCHK(hipMemsetAsync(d_count, 0, sizeof(int), nullptr), "memset");
+  RefineCrit X;
+  X.F = {crit->err_grad_d, crit->err_grad_p, crit->err_grad_u, crit->floor_d, crit->floor_p, crit->floor_u, p->gamma, p->smallr};
+  X.n_jeans = crit->n_jeans; X.tail_pix = crit->tail_pix; X.factG = crit->factG > 0.0 ? crit->factG : 1.0;
+  X.gm1 = p->gamma - 1.0; X.smallc2 = p->smallc * p->smallc;
+  X.thr = crit->thr; X.var_cut = crit->var_cut_refine; X.thr_mode = crit->thr_mode; X.ivar = crit->ivar_refine - 1;
+  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
+  if (crit->err_grad_d >= 0.0 || crit->err_grad_p >= 0.0 || crit->err_grad_u >= 0.0)
+    hipLaunchKernelGGL(lvl_refine_kernel<true>, g, b, 0, nullptr, A, X, d_count + 1, d_count);
+  else
+    hipLaunchKernelGGL(lvl_refine_kernel<false>, g, b, 0, nullptr, A, X, d_count + 1, d_count);
+  HCHK(hipGetLastError(), "refine_flag launch");
+  return fetch_flag_list(R, ngrid, d_count, cells, ncells, who);
+}
+
+// rho_fine's quasi-Lagrangian refinement map of the level's own cells (pm/rho_fine.f90:96-118: phi = rho/d_scale, with
+// ivar_refine only where the scalar passes var_cut_refine; :201-211: cpu_map2 = phi >= m_refine): the cells with cpu_map2 == 1
+int ramses_amd_amrres_mass_map(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double d_scale, double m_refine,
+                               int ivar_refine, double var_cut_refine, const double *rho, int *cells, int *ncells) {
+  const char *who = "ramses_amd_amrres_mass_map";
+  if (int rc_ = refuse_amr(p, who)) return rc_;
+  if (!p) return fail(RAMSES_AMD_EINVAL, "%s: NULL argument p", who);
+  if (!cells) return fail(RAMSES_AMD_EINVAL, "%s: NULL argument cells", who);
+  if (!ncells) return fail(RAMSES_AMD_EINVAL, "%s: NULL argument ncells", who);
+  *ncells = 0;
+  if (!(d_scale > 0.0)) return fail(RAMSES_AMD_EINVAL, "%s: d_scale=%g must be > 0", who, d_scale);
+  if (int rc = check_ivar_refine(who, ivar_refine, p->nvar)) return rc;
+  LvlArgs A;
+  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
+  if (ngrid == 0) return 0;
+  if (ivar_refine > A.nvar) return fail(RAMSES_AMD_EINVAL, "%s: ivar_refine=%d beyond the resident state's nvar=%d", who, ivar_refine, A.nvar);
+  AmrRes &R = g_ar;
+  const size_t cb = sizeof(double) * (size_t)R.ncell;
+  if (rho) {
+    // the deposit lives in the host vector: its cells of the listed octs go up (8*ngrid doubles)
+    HCHK(R.rho.ensure(cb), "hipMalloc rho");
+    if (int rc = level_from_host(R, R.rho.as<double>(), 1, R.cur_ig, ngrid, igrid, rho, "rho")) return rc;
+  } else if (R.rho.cap < cb) {
+    return fail(RAMSES_AMD_EINVAL, "%s: rho is NULL and the device holds no deposit (ramses_amd_amrres_rho_fine)", who);
+  }
+  if (int rc = sorted_list(R, A)) return rc;
+  HCHK(R.okbuf.ensure(sizeof(int) * (8 * (size_t)ngrid + 1)), "hipMalloc");
+  int *d_count = R.okbuf.as<int>();
+  HCHK(hipMemsetAsync(d_count, 0, sizeof(int), nullptr), "memset");
+  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
+  if (ivar_refine > 0)
+    hipLaunchKernelGGL(lvl_mass_map_kernel<true>, g, b, 0, nullptr, A, R.rho.as<double>(), d_scale, m_refine, ivar_refine - 1, var_cut_refine, p->smallr, d_count + 1, d_count);
+  else
+    hipLaunchKernelGGL(lvl_mass_map_kernel<false>, g, b, 0, nullptr, A, R.rho.as<double>(), d_scale, m_refine, 0, var_cut_refine, p->smallr, d_count + 1, d_count);
+  HCHK(hipGetLastError(), "mass_map launch");
+  return fetch_flag_list(R, ngrid, d_count, cells, ncells, who);
 }
 
 namespace {

@@ -5,7 +5,8 @@
 ! jeans_length_refine stays the reference's).  While the hydro state of an AMR run is
 ! device-resident the gradient criteria (hydro_refine, hydro/godunov_utils.f90:125-263:
 ! err_grad_d / err_grad_p / err_grad_u on a cell and its two neighbours per direction, a missing
-! neighbour replaced by the neighbouring father cell) are evaluated on the GPU, which also compacts
+! neighbour replaced by the neighbouring father cell) and, with self-gravity, the Jeans criterion
+! (jeans_length_refine, hydro/hydro_flag.f90:185-258) are evaluated on the GPU, which also compacts
 ! the answer: the host receives the LIST of cells that ask for refinement (a few thousand ints at
 ! most, not one flag per cell of the level) and marks them in flag1.  Geometry-based refinement
 ! (r_refine: a mask on the cell position, no hydro data) filters that list through the reference's
@@ -29,6 +30,7 @@ subroutine hydro_flag(ilevel)
   real(dp)::half,scale
   real(dp),dimension(1:3)::corner
   type(ramses_amd_hydro_params)::p
+  type(ramses_amd_refine_crit)::crit
   integer(8)::t0
 
   if(.not.ramses_amd_amr_resident())then
@@ -45,8 +47,16 @@ subroutine hydro_flag(ilevel)
   call ramses_amd_fill_hydro_params(p)
   ncache=active(ilevel)%ngrid
   allocate(cand(1:twotondim*max(ncache,1)))
-  rc=ramses_amd_amrres_hydro_flag(p,ncache,ramses_amd_octs(ilevel),dble(err_grad_d),dble(err_grad_p),dble(err_grad_u), &
-       & dble(floor_d),dble(floor_p),dble(floor_u),cand,ncand)
+  crit%err_grad_d=dble(err_grad_d); crit%err_grad_p=dble(err_grad_p); crit%err_grad_u=dble(err_grad_u)
+  crit%floor_d=dble(floor_d); crit%floor_p=dble(floor_p); crit%floor_u=dble(floor_u)
+  crit%n_jeans=-1.0d0; crit%tail_pix=0.0d0; crit%factG=1.0d0
+  crit%thr=0.0d0; crit%var_cut_refine=0.0d0; crit%thr_mode=0; crit%ivar_refine=0
+  if(poisson.and.jeans_refine(ilevel)>0.0)then
+     ! hydro/hydro_flag.f90:140,209-213 (cosmo keeps the run off the device: factG = 1)
+     crit%n_jeans=jeans_refine(ilevel)
+     crit%tail_pix=boxlen/(2d0)**ilevel
+  end if
+  rc=ramses_amd_amrres_refine_flag(p,ncache,ramses_amd_octs(ilevel),crit,cand,ncand)
   if(rc/=0)call ramses_amd_fatal('hydro_flag')
 
   allocate(keep(1:max(ncand,1)))

@@ -28,6 +28,14 @@ module ramses_amd_cabi
      integer(c_int64_t) :: pitch_y, pitch_z, pitch_var
   end type ramses_amd_brick
 
+  ! struct ramses_amd_refine_crit: the local refinement criteria of a level (a value <= 0 switches a field off)
+  type, bind(C) :: ramses_amd_refine_crit
+     real(c_double)     :: err_grad_d, err_grad_p, err_grad_u, floor_d, floor_p, floor_u
+     real(c_double)     :: n_jeans, tail_pix, factG
+     real(c_double)     :: thr, var_cut_refine
+     integer(c_int32_t) :: thr_mode, ivar_refine
+  end type ramses_amd_refine_crit
+
   ! struct ramses_amd_mg_transport: the caller's message layer of the distributed multigrid (host buffers)
   type, bind(C) :: ramses_amd_mg_transport
      type(c_ptr)    :: user
@@ -929,6 +937,31 @@ module ramses_amd_cabi
        real(c_double), value :: egd, egp, egu, fld, flp, flu
        integer(c_int) :: rc
      end function ramses_amd_amrres_hydro_flag
+     function ramses_amd_refine_crit_size() bind(C, name='ramses_amd_refine_crit_size') result(n)
+       import :: c_size_t
+       integer(c_size_t) :: n
+     end function ramses_amd_refine_crit_size
+     function ramses_amd_amrres_refine_flag(p, ngrid, igrid, crit, cells, ncells) &
+          & bind(C, name='ramses_amd_amrres_refine_flag') result(rc)
+       import :: ramses_amd_hydro_params, ramses_amd_refine_crit, c_int
+       type(ramses_amd_hydro_params), intent(in) :: p
+       integer(c_int), value :: ngrid
+       integer(c_int) :: igrid(*), cells(*)
+       type(ramses_amd_refine_crit), intent(in) :: crit
+       integer(c_int), intent(out) :: ncells
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_refine_flag
+     function ramses_amd_amrres_mass_map(p, ngrid, igrid, d_scale, m_refine, ivar_refine, var_cut_refine, rho, cells, ncells) &
+          & bind(C, name='ramses_amd_amrres_mass_map') result(rc)
+       import :: ramses_amd_hydro_params, c_int, c_double, c_ptr
+       type(ramses_amd_hydro_params), intent(in) :: p
+       integer(c_int), value :: ngrid, ivar_refine
+       integer(c_int) :: igrid(*), cells(*)
+       real(c_double), value :: d_scale, m_refine, var_cut_refine
+       type(c_ptr), value :: rho               ! c_loc of the host vector rho(1:ncell), or c_null_ptr: the device's deposit
+       integer(c_int), intent(out) :: ncells
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_mass_map
      ! ---- AMR residency under MPI: the virtual-boundary exchanges on the resident cell vectors ----
      function ramses_amd_which_column(xx, base, ncell, ncol) bind(C, name='ramses_amd_which_column') result(k)
        import :: c_int, c_int64_t, c_double

@@ -103,12 +103,14 @@ contains
     integer :: stat, rc
     type(ramses_amd_hydro_params) :: p
     type(ramses_amd_brick) :: b
+    type(ramses_amd_refine_crit) :: crit
     if (.not. ramses_amd_checked) then
        call get_environment_variable('RAMSES_AMD', val, status=stat)
        if (stat == 0) ramses_amd_on = (trim(val) /= '0')
        if (ramses_amd_on) then
           rc = ramses_amd_abi_check(c_sizeof(p), c_sizeof(b))
           if (rc /= 0) call ramses_amd_fatal('ramses_amd_abi_check')
+          if (ramses_amd_refine_crit_size() /= c_sizeof(crit)) call ramses_amd_fatal('size of ramses_amd_refine_crit')
           rc = ramses_amd_set_device_auto(ramses_amd_world_rank())
           if (rc /= 0) call ramses_amd_fatal('ramses_amd_set_device_auto')
           call ramses_amd_check_build()
@@ -684,9 +686,17 @@ contains
              if (trim(val) == '0') ramses_amd_amr_ok = .false.
           end if
           if (gravity_type > 0 .or. cosmo) ramses_amd_amr_ok = .false.
-          do l = 1, nlevelmax
-             if (m_refine(l) > -1.0d0) ramses_amd_amr_ok = .false.    ! rho_fine's quasi-Lagrangian map reads uold on the host
-          end do
+       end if
+       ! jeans_refine and m_refine are evaluated on the resident state (hydro_flag.f90, flag_utils.f90, rho_fine.f90 of this
+       ! directory: ramses_amd_amrres_refine_flag / _mass_map); RAMSES_AMD_RESIDENT_REFINE=0 keeps such runs staged, as they
+       ! were before (A/B runs)
+       call get_environment_variable('RAMSES_AMD_RESIDENT_REFINE', val, status=stat)
+       if (stat == 0) then
+          if (trim(val) == '0') then
+             do l = 1, nlevelmax
+                if (refine_crit_on(l)) ramses_amd_amr_ok = .false.
+             end do
+          end if
        end if
        if (tracer .or. MC_tracer .or. clumpfind .or. lightcone .or. movie .or. aton) ramses_amd_amr_ok = .false.
        if (static .or. static_gas .or. neq_chem .or. barotropic_eos .or. isothermal .or. metal) ramses_amd_amr_ok = .false.
@@ -694,9 +704,6 @@ contains
        if (ndim /= 3 .or. levelmin < 3) ramses_amd_amr_ok = .false.
        if (icoarse_max - icoarse_min /= 0 .or. jcoarse_max - jcoarse_min /= 0 .or. kcoarse_max - kcoarse_min /= 0) &
             & ramses_amd_amr_ok = .false.
-       do l = 1, nlevelmax
-          if (jeans_refine(l) > -1.0d0) ramses_amd_amr_ok = .false.     ! jeans_length_refine reads uold on the host
-       end do
 #if USE_TURB==1
        if (turb) ramses_amd_amr_ok = .false.
 #endif
@@ -704,6 +711,14 @@ contains
             & write(*,*) 'ramses_amd: hydro state and tree of the AMR levels stay resident on the GPU'
     end if
     ramses_amd_amr_config = ramses_amd_amr_ok
+  contains
+    ! what kept a run staged before the criteria moved to the device: the Jeans length on any level, the mass criterion with
+    ! self-gravity
+    logical function refine_crit_on(l)
+      integer, intent(in) :: l
+      refine_crit_on = jeans_refine(l) > -1.0d0
+      if (poisson) refine_crit_on = refine_crit_on .or. m_refine(l) > -1.0d0
+    end function refine_crit_on
   end function ramses_amd_amr_config
 
   ! RAMSES_AMD_FORCE_MPI=0: force_fine of AMR levels with several ranks keeps the reference's host loops
@@ -810,6 +825,13 @@ contains
        rc = ramses_amd_amrres_rho_keep(0)
     end if
   end subroutine ramses_amd_pois_mpi_sync_host
+
+  ! the address of a host vector for the entries of the C ABI that take a pointer or NULL
+  function ramses_amd_vec_addr(x) result(addr)
+    real(c_double), target :: x(*)
+    type(c_ptr) :: addr
+    addr = c_loc(x)
+  end function ramses_amd_vec_addr
 
   logical function ramses_amd_amr_resident()
     ramses_amd_amr_resident = .false.

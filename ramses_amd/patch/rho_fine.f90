@@ -73,8 +73,9 @@ end subroutine rho_fine_amd
 ! for l = nlevelmax .. ilevel) runs on the GPU on the resident density -- multipoles of leaf and split cells, the
 ! order-tagged CIC gather through the tree, the four sequential multipole sums at levelmin (csrc/rho_fine.hip) -- and
 ! only rho of the visited levels comes back.  What else the reference's routine does in this configuration is the
-! reset of phi on the level and rho_tot (:66-70,176-183); everything tied to particles, cic_levelmax, m_refine,
-! physical boundaries or several ranks keeps the reference's routine (ramses_amd_rho_amr_device says no).
+! reset of phi on the level, rho_tot (:66-70,176-183) and, with m_refine(ilevel) > -1, the quasi-Lagrangian refinement map
+! (ramses_amd_rho_mass_map below); everything tied to particles, cic_levelmax or physical boundaries keeps the reference's
+! routine (ramses_amd_rho_amr_device says no).
 !------------------------------------------------------------------------------
 logical function ramses_amd_rho_amr_device(ilevel)
   use amr_commons
@@ -85,7 +86,7 @@ logical function ramses_amd_rho_amr_device(ilevel)
   implicit none
   integer,intent(in)::ilevel
   character(len=16)::val
-  integer::stat,l
+  integer::stat
   logical,save::first=.true.,enabled=.true.,enabled_mpi=.true.
   if(first)then
      call get_environment_variable('RAMSES_AMD_RESIDENT_RHO',val,status=stat)
@@ -113,9 +114,6 @@ logical function ramses_amd_rho_amr_device(ilevel)
   ! RAMSES_AMD_RESIDENT_RHO_MPI=0 keeps the reference's host routine there (the density comes back first)
   if(ncpu>1.and..not.enabled_mpi)return
   if(icoarse_max/=icoarse_min)return
-  do l=ilevel,nlevelmax
-     if(m_refine(l)>-1.0d0)return
-  end do
   ramses_amd_rho_amr_device=.true.
 end function ramses_amd_rho_amr_device
 
@@ -177,6 +175,7 @@ subroutine rho_fine(ilevel,icount)
            end do
         end do
         rho_tot=multipole(1)/boxlen**ndim
+        call ramses_amd_rho_mass_map(ilevel,ilevel==levelmin.or.icount>1)
         ramses_amd_pois_dev=.false.
         ramses_amd_pois_amr_level=0
         call ramses_amd_toc('rho_fine',ilevel,t0)
@@ -193,6 +192,14 @@ subroutine rho_fine(ilevel,icount)
               if(rc/=0)call ramses_amd_fatal('rho_fine (density back to the host)')
            end if
         end do
+     end if
+     ! with ivar_refine > 0 its quasi-Lagrangian map also reads that scalar and the density of the level's own cells, on every
+     ! call (:100-109): the level comes back
+     if(ramses_amd_amrres_active()/=0.and.poisson.and.m_refine(ilevel)>-1.0d0.and.ivar_refine>0)then
+        if(numbtot(1,ilevel)>0.and.ilevel<ramses_amd_amr_host_from)then
+           rc=ramses_amd_amrres_sync_level(active(ilevel)%ngrid,ramses_amd_octs(ilevel),uold)
+           if(rc/=0)call ramses_amd_fatal('rho_fine (the level of the refinement map back to the host)')
+        end if
      end if
   end if
   call rho_fine_amd(ilevel,icount)
@@ -265,7 +272,63 @@ subroutine ramses_amd_rho_fine_mpi(ilevel,icount)
      multipole(1:ndim+1)=multipole_out
   endif
   rho_tot=multipole(1)/boxlen**ndim
+  call ramses_amd_rho_mass_map(ilevel,ilevel==levelmin.or.icount>1)
   ramses_amd_pois_dev=.false.
   ramses_amd_pois_amr_level=0
 #endif
 end subroutine ramses_amd_rho_fine_mpi
+
+!------------------------------------------------------------------------------
+! The quasi-Lagrangian refinement map of rho_fine on a resident run (pm/rho_fine.f90:96-118,201-214): on the level's own
+! cells phi = rho/d_scale -- with ivar_refine > 0 only where uold(ivar_refine)/max(uold(1),smallr) > var_cut_refine, 0
+! elsewhere -- and cpu_map2 = 1 where phi >= m_refine(ilevel), 0 elsewhere, followed by the reference's own
+! make_virtual_fine_int.  The test runs on the device (ramses_amd_amrres_mass_map), where the scalar lives; the cells with
+! cpu_map2 = 1 come back as a list.  rho: the deposit this call has just left on the device (fresh), otherwise the host vector
+! an earlier call filled (its cells of the level are sent: the device copy may have been rebuilt since).
+! phi itself stays 0 on the host, as it does without m_refine: nothing reads the number density again.  save_phi_old runs
+! before rho_fine (amr/amr_step.f90), the solver of the level overwrites phi of its own cells with its first guess before
+! it reads any (make_initial_phi / make_multipole_phi, poisson/multigrid_fine_commons.f90:58-62, poisson/phi_fine_cg.f90)
+! and the exchange that follows the guess (:63) overwrites what :164-165 had spread to the reception cells.
+!------------------------------------------------------------------------------
+subroutine ramses_amd_rho_mass_map(ilevel,fresh)
+  use amr_commons
+  use hydro_commons, only: smallr, mass_sph
+  use poisson_commons
+  use ramses_amd_iface
+  implicit none
+  integer,intent(in)::ilevel
+  logical,intent(in)::fresh
+  integer::rc,n,nc,k,ind,i,nx_loc,iskip
+  real(dp)::dx,dx_loc,scale,d_scale
+  integer,allocatable,dimension(:)::cells
+  type(c_ptr)::addr
+  type(ramses_amd_hydro_params)::p
+  integer(8)::t0
+  if(.not.(m_refine(ilevel)>-1.0d0))return
+  call ramses_amd_tic(t0)
+  dx=0.5D0**ilevel
+  nx_loc=icoarse_max-icoarse_min+1
+  scale=boxlen/dble(nx_loc)
+  dx_loc=dx*scale
+  d_scale=max(mass_sph/dx_loc**ndim,smallr)
+  n=active(ilevel)%ngrid
+  allocate(cells(1:twotondim*max(n,1)))
+  call ramses_amd_fill_hydro_params(p)
+  addr=c_null_ptr
+  if(.not.fresh)addr=ramses_amd_vec_addr(rho)
+  rc=ramses_amd_amrres_mass_map(p,n,ramses_amd_octs(ilevel),d_scale,dble(m_refine(ilevel)),max(ivar_refine,0), &
+       & dble(var_cut_refine),addr,cells,nc)
+  if(rc/=0)call ramses_amd_fatal('rho_fine (quasi-Lagrangian refinement map)')
+  do ind=1,twotondim
+     iskip=ncoarse+(ind-1)*ngridmax
+     do i=1,n
+        cpu_map2(active(ilevel)%igrid(i)+iskip)=0
+     end do
+  end do
+  do k=1,nc
+     cpu_map2(cells(k))=1
+  end do
+  deallocate(cells)
+  call make_virtual_fine_int(cpu_map2(1),ilevel)
+  call ramses_amd_toc('rho_fine (shim: refinement map kernel + list + cpu_map2)',ilevel,t0)
+end subroutine ramses_amd_rho_mass_map

@@ -430,6 +430,60 @@ bound_type= 1, 1, 2, 2, 1, 1
         if which in ("all", "ref"):
             run_grav("reference (1 core)", ref, {"RAMSES_AMD": "0"}, level, nstep)
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "jeans":
+        # python scripts/dropin_timing.py jeans LMIN LMAX NSTEP [REPEATS] [BINARY TAG]
+        # AMR + self-gravity refined by the Jeans length alone (tests/test_refine_criteria_dropin_gpu.py case (a): jeans_refine=4.
+        # on every level but the last, pressure 0.1, no gradient criteria) at levels lmin..lmax: resident (default) against
+        # RAMSES_AMD_RESIDENT_REFINE=0 (staged, the gating before the criteria ran on the device).  BINARY: another build of the
+        # patched program (it loads the library it was linked with), timed alone under TAG
+        lmin, lmax, nstep = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+        repeats = int(sys.argv[5]) if len(sys.argv) > 5 else 3
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("mkb", os.path.join(ROOT, "tests", "golden", "make_golden_baseline.py"))
+        mkb = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mkb)
+        nml = mkb.amr_grav_namelist(lmin, lmax, nstep, foutput=1000)
+        for old, new in (("err_grad_p=0.1\n", ""), ("err_grad_d=0.2\n", ""), ("p_region=1e-5,0.4,1e-3", "p_region=0.1,0.4,0.1"),
+                         ("&REFINE_PARAMS\n", "&REFINE_PARAMS\njeans_refine=%d*4.\n" % (lmax - lmin))):
+            assert old in nml
+            nml = nml.replace(old, new)
+
+        def run_jeans(tag, binary, env):
+            old = {k: os.environ.get(k) for k in env}
+            os.environ.update(env)
+            t0 = time.time()
+            try:
+                work, out = rs.run_reference(nml, binary=binary, timeout=3000)
+            finally:
+                for k, v in old.items():
+                    if v is None:
+                        os.environ.pop(k, None)
+                    else:
+                        os.environ[k] = v
+            wall = time.time() - t0
+            shutil.rmtree(work, ignore_errors=True)
+            rows = {}
+            for line in out.splitlines():
+                m = re.match(r"^\s*([0-9.]+)\s+([0-9.]+)\s+([a-zA-Z].*?)\s*$", line)
+                if m and "STEP" not in m.group(3):
+                    rows[m.group(3)] = float(m.group(1))
+            last = {}
+            for l, g in re.findall(r"Level\s+(\d+) has\s+(\d+) grids", out):
+                last[int(l)] = int(g)
+            # the time loop alone: the program's TOTAL timer row starts after the initial refinement (amr/adaptive_loop.f90)
+            print(json.dumps({"config": tag, "levels": [lmin, lmax], "steps": nstep, "wall_s": round(wall, 3),
+                              "resident": "AMR levels stay resident on the GPU" in out,
+                              "octs_per_level": {k: v for k, v in last.items() if k >= lmin}, "timers_s": rows}), flush=True)
+
+        if len(sys.argv) > 7:
+            for _ in range(repeats):
+                run_jeans(sys.argv[7], sys.argv[6], {"RAMSES_AMD": "1"})
+            sys.exit(0)
+        pat = os.path.join(ROOT, "oracle", "_ref", "ramses3d_patch")
+        for _ in range(repeats):
+            run_jeans("patched, resident: Jeans criterion on the device", pat, {"RAMSES_AMD": "1"})
+            run_jeans("patched, RAMSES_AMD_RESIDENT_REFINE=0: staged", pat, {"RAMSES_AMD": "1", "RAMSES_AMD_RESIDENT_REFINE": "0"})
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "amr":
         lmin, lmax, nstep = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
         which = sys.argv[5] if len(sys.argv) > 5 else "all"
