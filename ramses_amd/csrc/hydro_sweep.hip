@@ -169,6 +169,12 @@ constexpr int yflux_wave(int f) { return !DUTY ? f : (f == 2 ? 0 : (f == BY - 2 
 #define SWEEP_TRIM 0
 #endif
 #endif
+// The loop's bookkeeping (sweep_march BOOK: the fast LLF 12-row kernels of the brick, slope types 1 and 7): the ring addresses
+// of a tracing row from one lane register and immediate offsets (LB), the store's lane offset switched on once (SO1): 605 ->
+// 593 instructions per plane of a full row of the fast minmod kernel (468 -> 460 VALU), 152 VGPRs as before, same bits; 512^3
+// LLF + minmod 2.925 -> 2.892 ms (medians of five alternating runs), below the bar of three spreads.  Carried plane offsets without the wrap ladders, and the y slots and the
+// parked update through such registers, shorten the listing to 549 instructions and measured SLOWER (2.93 -> 3.12 and 3.03
+// ms): left out, the numbers are in profiles/r09_sweep_bookkeeping.txt.
 
 // SWEEP_CYCLE_PROBE=1 (a build of its own, never the shipped one: with 0 nothing of it is compiled): every wave sums, per
 // plane, the shader clocks from the loop top to the barrier, inside the barrier and from the barrier to the loop end, and
@@ -204,6 +210,21 @@ __device__ __forceinline__ void plane_store(double *var_base, unsigned plane_byt
   __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(var_base, 0, BUF_RANGE, 0x00020000);
   __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32, x), r, off, plane_bytes, SWEEP_STORE_AUX);
 }
+
+// LDS through an address register and an immediate offset, both chosen by hand (sweep_march, the ring reads of a tracing
+// row).  lds_reg() hands the compiler an address it cannot take apart again: what is added to it afterwards is a constant
+// and goes into the instruction's offset field, and two accesses whose offsets are multiples of 512 pair into one
+// ds_read2st64 / ds_write2st64 without a new base register.
+typedef __attribute__((address_space(3))) double lds_f64;
+__device__ __forceinline__ unsigned lds_reg(unsigned a) {
+  asm("" : "+v"(a));
+  return a;
+}
+__device__ __forceinline__ unsigned lds_addr(const void *p) {
+  return (unsigned)(size_t)(const __attribute__((address_space(3))) unsigned char *)p;
+}
+__device__ __forceinline__ double lds_ld(unsigned reg, unsigned imm) { return *(const lds_f64 *)(size_t)(reg + imm); }
+__device__ __forceinline__ void lds_st(unsigned reg, unsigned imm, double x) { *(lds_f64 *)(size_t)(reg + imm) = x; }
 
 __device__ __forceinline__ int wave_shr1_i(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ int wave_shl1_i(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xf, 0xf, true); }   // (lane 63: 0, as wave_shl1)
@@ -394,6 +415,18 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
   // (the traced states of trace3d_cell are floored: llf_flux_fast FLOORED; 1 / rho rides from ctoprim_cell to the trace)
   // (the LLF kernels: the others sit at their register limit and keep the instructions they had)
   constexpr bool TRIM = SWEEP_TRIM != 0 && RS == RIEMANN_LLF && SCHEME == 0 && NE == 0 && !PFIX;
+  // BOOK: the kernels whose marching loop takes the two bookkeeping steps below (LB, SO1) -- the fast LLF 12-row kernels of
+  // the brick without gravity with the minmod and the type-7 slopes, which keep their VGPR counts (152, 144).  Everywhere else
+  // the loop stays the code it was: slope types 0, 2 and 8 of the same family would take one or two VGPRs more (150 -> 151,
+  // 144 -> 146), and the strict 12-row kernels, HLLC, gravity, the 8-row and the tile kernels sit at 166 - 168 or 256 VGPRs,
+  // where a changed schedule costs scratch.  (What LB and SO1 carry from trip to trip is declared before the loop like the
+  // rest of the carried state; where BOOK is false nothing reads it and none of it is compiled.)
+#ifdef RAMSES_AMD_FAST
+  constexpr bool BOOK = (ST == 1 || ST == 7) && RS == RIEMANN_LLF && BY == 12 && !GRAV && SCHEME == 0 && NV == 5 && !MASK && NE == 0 &&
+                        !PFIX && !DIFMAG;
+#else
+  constexpr bool BOOK = false;
+#endif
   const bool r_upd = r_fxz && (tx >= 2) && (tx <= BX - 3) && (xu < A.nx) && (yu < A.ny);
   const unsigned colb_upd = r_upd ? colb : BUF_OOB;   // lanes that own no cell store nowhere
 
@@ -569,6 +602,21 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     for (int n = 0; n < DPN; n++) dpark[n][ty - 2][tx] = n < NV + 2 ? 0.0 : 1.0;      // (as fzlo, the corners and qmz start)
   }
 
+  // SO1: the store's lane offset is colb_upd from the third trip of a chunk on (c >= z0 + 1) and beyond every range before:
+  // an all-ones word (BUF_OOB) that is or-ed on and cleared once, instead of a predicate rebuilt every plane
+  constexpr bool SO1 = BOOK;
+  unsigned so_oob = BUF_OOB;
+  // LB: the ring addresses of a tracing row (two ring planes, the seven-point slopes) -- the thread's column one row up in
+  // slot 0, and the byte offsets of the slots of planes c and c-1, which change places every trip (slots 0 and 1: one xor
+  // each).  Rows 1 .. BY-2 trace, so row ty-1 exists and no address register is below the ring's first byte; the cells read
+  // are the ones read before, those of lanes 0 and 63 (the end of the row above, the start of the row below) and of rows 1
+  // and BY-2 (the halo rows' cells) included: what they return stays in columns and rows that are never stored, as before.
+  constexpr bool LB = BOOK && r_trace;
+  static_assert(!BOOK || RING == 2, "BOOK: two ring planes, the seven-point slopes");
+  constexpr unsigned QROW = BX * 8u, QVAR = BY * BX * 8u, QSLOT = (unsigned)sizeof(Plane<BY, NV>);
+  const unsigned q_lane = lds_addr(qring) + (unsigned)((ty - 1) * BX + tx) * 8u;
+  unsigned q_cur = QSLOT, q_prev = 0u;          // (sb = 1, sa = 0)
+
   for (int c = z0 - 1; c <= z1; c++) {
     Plane<L::MR, NF> &M = mring[c & 1];
     Plane<L::MR, NF> &Mprev = mring[(c & 1) ^ 1];
@@ -639,6 +687,21 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
           dq[1][n] = slope1_1d<ST>(qs.v[n][tym][tx], qb[n], qs.v[n][typ][tx], dc1, n);
           dq[2][n] = slope1_1d<ST>(qprev.v[n][ty][tx], qb[n], qc[n], dc2, n);
         }
+      } else if constexpr (LB) {
+        // the same 5 NV cells of the ring at the same addresses, through three address registers of plane c -- column tx from
+        // row ty-1 on (q_c: rows ty-1, ty, ty+1 at 0, QROW, 2 QROW), columns tx-1 and tx+1 of row ty (q_m, q_p) -- and one of
+        // plane c-1's slot (q_s), every variable a multiple of 512 B further on: no address is computed per cell
+        const unsigned q_c = lds_reg(q_lane + q_cur), q_s = lds_reg(q_lane + q_prev);
+        const unsigned q_m = lds_reg(q_c + (QROW - 8u)), q_p = lds_reg(q_c + (QROW + 8u));
+#pragma unroll
+        for (int n = 0; n < NV; n++) {
+          qb[n] = lds_ld(q_c, QROW + n * QVAR);
+          dq[0][n] = slope1<ST>(lds_ld(q_m, n * QVAR), qb[n], lds_ld(q_p, n * QVAR), P);
+          dq[1][n] = slope1<ST>(lds_ld(q_c, n * QVAR), qb[n], lds_ld(q_c, 2 * QROW + n * QVAR), P);
+          dq[2][n] = slope1<ST>(lds_ld(q_s, QROW + n * QVAR), qb[n], qc[n], P);
+        }
+#pragma unroll
+        for (int n = 0; n < NV; n++) lds_st(q_s, QROW + n * QVAR, qc[n]);
       } else {
 #pragma unroll
         for (int n = 0; n < NV; n++) {
@@ -648,7 +711,7 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
           dq[2][n] = slope1<ST>(qprev.v[n][ty][tx], qb[n], qc[n], P);
         }
       }
-      if (RING == 2) {
+      if (RING == 2 && !LB) {
 #pragma unroll
         for (int n = 0; n < NV; n++) qring[sa].v[n][ty][tx] = qc[n];
       }
@@ -914,7 +977,8 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
       }
       {
         const unsigned pb = MASK ? zpart(c - 1) * 8u : plane_off(c - 1);
-        const unsigned so = (c >= z0 + 1) ? (MASK ? ((r_upd && (ok_zlo & CELL_OWNED)) ? tbp(c - 1) : BUF_OOB) : colb_upd) : BUF_OOB;
+        const unsigned so = SO1 ? (colb_upd | so_oob)
+                                : ((c >= z0 + 1) ? (MASK ? ((r_upd && (ok_zlo & CELL_OWNED)) ? tbp(c - 1) : BUF_OOB) : colb_upd) : BUF_OOB);
 #pragma unroll
         for (int n = 0; n < NV; n++) {
           if (MASK) plane_store(unew + (long)(n & ~1) * A.pitch_var, pb + (n & 1) * odd_var, so, un[n]);
@@ -932,6 +996,8 @@ __device__ __forceinline__ void sweep_march(const SweepArgs &A, unsigned char *s
     else { const int t = sa; sa = sb; sb = t; }
     if (MASK) ok_zlo = okc;
     if (TRIM) rinv_c = rinv_n;
+    if (SO1) so_oob = c >= z0 ? 0u : so_oob;
+    if (LB) { q_cur ^= QSLOT; q_prev ^= QSLOT; }
 #if SWEEP_CYCLE_PROBE
     pr_a += pr_t1 - pr_t0; pr_w += pr_t2 - pr_t1; pr_b += __builtin_readcyclecounter() - pr_t2; pr_n += 1;
 #endif
