@@ -6,9 +6,10 @@
 //   set_uold      hydro/godunov_fine.f90:135-232       lvl_set_uold_kernel (incl. the passive-scalar floor fix :176-190)
 //   upload_fine   hydro/interpol_hydro.f90:5-263       lvl_upload_kernel (upl: restriction, interpol_var 0/1/2)
 //   courant_fine  hydro/courant_fine.f90:1-159         lvl_courant_kernel (cmpdt on the leaf cells)
-//   hydro_flag    hydro/hydro_flag.f90:1-178 + hydro_refine hydro/godunov_utils.f90:125-263   lvl_flag_kernel
-//   every local refinement criterion in one pass: the same gradients, jeans_length_refine hydro/hydro_flag.f90:185-258,
-//                 poisson_refine's branches on uold amr/flag_utils.f90:465-470,480-485             lvl_refine_kernel
+//   hydro_flag    hydro/hydro_flag.f90:1-178 + hydro_refine hydro/godunov_utils.f90:125-263,
+//                 jeans_length_refine hydro/hydro_flag.f90:185-258 and poisson_refine's branches on uold
+//                 amr/flag_utils.f90:465-470,480-485: every local refinement criterion in one pass  lvl_refine_kernel
+//                 (the gradients alone, ramses_amd_amrres_hydro_flag: the same kernel with the others off)
 //   rho_fine's quasi-Lagrangian refinement map    pm/rho_fine.f90:96-118,201-211                  lvl_mass_map_kernel
 // The mesh itself stays the reference's host code: before refine_fine rebuilds levels the shim brings the
 // levels it reads back to the host (sync_level), and afterwards the tree and the rebuilt levels are sent
@@ -43,20 +44,43 @@ using namespace ramses_amd;
 
 namespace {
 
-struct LvlArgs {
-  double *uold, *unew;
-  const int *son, *nbor;
+// an oct list of a level on the device and the cell vectors it addresses: their strides and how many variables they hold
+struct LvlList {
   const int *igrid;
   int ngrid, nvar;
   long ncell, ncoarse, ngridmax;
 };
+// ... with the hydro state and the tree (the list comes last: the kernels' argument layout)
+struct LvlState {
+  double *uold, *unew;
+  const int *son, *nbor;
+};
+struct LvlArgs : LvlState, LvlList {};
+// THE walk over the cells of an oct list: thread t of 8*ngrid -> octant ind, oct g (1-based), cell c (0-based)
+__device__ __forceinline__ long lvl_cell(const LvlList &L, long t, int &ind, int &g) {
+  ind = (int)(t / L.ngrid);
+  g = L.igrid[(int)(t % L.ngrid)];
+  return L.ncoarse + (long)ind * L.ngridmax + g - 1;
+}
+__device__ __forceinline__ long lvl_cell(const LvlList &L, long t) { int ind, g; return lvl_cell(L, t, ind, g); }
+// THE same-level neighbour step of getnborcells: the neighbour of cell c = (ind, oct g) in direction d on side 0 | 1.  The sibling
+// inside the oct, else the cell of the oct son(nbor(g, 2d+side)); where that oct is missing the neighbouring father cell, at the
+// coarser level (`coarse`; hydro/hydro_flag.f90:107-117)
+__device__ __forceinline__ long lvl_nbor(const LvlArgs &A, long c, int ind, int g, int d, int side, bool &coarse) {
+  coarse = false;
+  if (((ind >> d) & 1) != side) return c + (side ? 1 : -1) * ((long)(1 << d) * A.ngridmax);
+  const int nb = A.nbor[(long)(2 * d + side) * A.ngridmax + g - 1];
+  const int g2 = A.son[nb - 1];
+  if (g2 > 0) return A.ncoarse + (long)(ind ^ (1 << d)) * A.ngridmax + g2 - 1;
+  coarse = true;
+  return (long)nb - 1;
+}
 
 // dst(cells of the level's octs, 1:nvar) = src(...)
 __global__ __launch_bounds__(256) void lvl_copy_kernel(LvlArgs A, double *__restrict__ dst, const double *__restrict__ src) {
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const long c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
+    const long c = lvl_cell(A, t);
     for (int v = 0; v < A.nvar; v++) dst[c + (long)v * A.ncell] = src[c + (long)v * A.ncell];
   }
 }
@@ -65,8 +89,7 @@ __global__ __launch_bounds__(256) void lvl_copy_kernel(LvlArgs A, double *__rest
 __global__ __launch_bounds__(256) void lvl_set_uold_kernel(LvlArgs A, double smallr) {
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const long c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
+    const long c = lvl_cell(A, t);
     if (A.nvar > 5) {
       const double ro = A.uold[c], rn = A.unew[c];
       if (ro < smallr && rn > ro) {
@@ -85,8 +108,7 @@ template <int NV>
 __global__ __launch_bounds__(256) void lvl_upload_kernel(LvlArgs A, int interpol_var, double smallr) {
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const long c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
+    const long c = lvl_cell(A, t);
     const int gs = A.son[c];
     if (gs <= 0) continue;
     double ch[8][NV];
@@ -121,8 +143,7 @@ __global__ __launch_bounds__(256) void lvl_courant_kernel(LvlArgs A, const doubl
   double dtmin = dt_init, mass = 0.0, etot = 0.0, eint = 0.0;
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const long c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
+    const long c = lvl_cell(A, t);
     if (A.son[c] != 0) continue;
     double u[5], g[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -165,7 +186,7 @@ __global__ void lvl_courant_final_kernel(double *out, int nblocks) {
   out[1 + k] = s;
 }
 
-// hydro_flag's gradient criteria (hydro_refine): ok[ind*ngrid+i] = 1 when the cell is to be refined
+// hydro_flag's gradient criteria (hydro_refine)
 struct FlagCrit { double err_grad_d, err_grad_p, err_grad_u, floor_d, floor_p, floor_u, gamma, smallr; };
 __device__ __forceinline__ void refine_prim(const LvlArgs &A, long c, const FlagCrit &F, double (&q)[5]) {
   // conservative -> (rho, u, v, w, P) as hydro_refine does (:150-190)
@@ -180,99 +201,23 @@ __device__ __forceinline__ void refine_prim(const LvlArgs &A, long c, const Flag
   for (int d = 0; d < 3; d++) ek = ek + 0.5 * q[0] * (q[1 + d] * q[1 + d]);
   q[4] = (F.gamma - 1.0) * (u[4] - ek);
 }
-// out: the cells that ask for refinement as a compact list of 1-based cell indices (one atomic per wavefront; the order
-// is whatever the waves arrive in -- the host sorts the few that come back)
-__global__ __launch_bounds__(256) void lvl_flag_kernel(LvlArgs A, FlagCrit F, int *__restrict__ list, int *__restrict__ count) {
-  const long total = (long)A.ngrid * 8;
-  const long span = (long)gridDim.x * blockDim.x;
-  for (long t0 = (long)blockIdx.x * blockDim.x; t0 < total; t0 += span) {
-    const long t = t0 + threadIdx.x;
-    bool flag = false;
-    long c = 0;
-    if (t < total) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const int g = A.igrid[i];
-    c = A.ncoarse + (long)ind * A.ngridmax + g - 1;
-    double qm[5];
-    refine_prim(A, c, F, qm);
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      // neighbour cells in direction d (getnborcells); a missing one is replaced by the neighbouring father cell
-      long cn[2];
-#pragma unroll
-      for (int side = 0; side < 2; side++) {
-        const int bit = (ind >> d) & 1;
-        if (bit != side) {
-          cn[side] = c + (side ? 1 : -1) * ((long)(1 << d) * A.ngridmax);
-        } else {
-          const int nb = A.nbor[(long)(2 * d + side) * A.ngridmax + g - 1];
-          const int g2 = A.son[nb - 1];
-          cn[side] = g2 > 0 ? A.ncoarse + (long)(ind ^ (1 << d)) * A.ngridmax + g2 - 1 : (long)nb - 1;
-        }
-      }
-      double qg[5], qd[5];
-      refine_prim(A, cn[0], F, qg);
-      refine_prim(A, cn[1], F, qd);
-      if (F.err_grad_d >= 0.0) {
-        const double e = 2.0 * __builtin_fmax(__builtin_fabs((qd[0] - qm[0]) / (qd[0] + qm[0] + F.floor_d)),
-                                              __builtin_fabs((qm[0] - qg[0]) / (qm[0] + qg[0] + F.floor_d)));
-        flag = flag || e > F.err_grad_d;
-      }
-      if (F.err_grad_p >= 0.0) {
-        const double e = 2.0 * __builtin_fmax(__builtin_fabs((qd[4] - qm[4]) / (qd[4] + qm[4] + F.floor_p)),
-                                              __builtin_fabs((qm[4] - qg[4]) / (qm[4] + qg[4] + F.floor_p)));
-        flag = flag || e > F.err_grad_p;
-      }
-      if (F.err_grad_u >= 0.0) {
-        const double cg = __builtin_sqrt(__builtin_fmax(F.gamma * qg[4] / qg[0], F.floor_u * F.floor_u));
-        const double cm = __builtin_sqrt(__builtin_fmax(F.gamma * qm[4] / qm[0], F.floor_u * F.floor_u));
-        const double cd = __builtin_sqrt(__builtin_fmax(F.gamma * qd[4] / qd[0], F.floor_u * F.floor_u));
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          const double vg = qg[1 + k], vm = qm[1 + k], vd = qd[1 + k];
-          const double e = 2.0 * __builtin_fmax(__builtin_fabs((vd - vm) / (cd + cm + __builtin_fabs(vd) + __builtin_fabs(vm) + F.floor_u)),
-                                                __builtin_fabs((vm - vg) / (cm + cg + __builtin_fabs(vm) + __builtin_fabs(vg) + F.floor_u)));
-          flag = flag || e > F.err_grad_u;
-        }
-      }
-    }
-    }
-    const unsigned long long m = __ballot(flag);
-    if (m) {
-      const int lane = threadIdx.x & 63;
-      int base = 0;
-      if (lane == 0) base = atomicAdd(count, __popcll(m));
-      base = __shfl(base, 0, 64);
-      if (flag) list[base + __popcll(m & ((1ull << lane) - 1ull))] = (int)(c + 1);
-    }
-  }
-}
 
-// ---- every local refinement criterion of a level in one pass (ramses_amd_amrres_refine_flag, _mass_map) ----
+// ---- every local refinement criterion of a level in one pass (ramses_amd_amrres_hydro_flag, _refine_flag, _mass_map) ----
 // IEEE division and square root, no contraction, whatever fast_math says: each criterion ends in a comparison and one flipped
 // flag is another mesh.
 struct RefineCrit {
-  FlagCrit F;                                  // the gradient criteria as lvl_flag_kernel has them
+  FlagCrit F;                                  // the gradient criteria (all three negative: off)
   double n_jeans, tail_pix, factG, gm1, smallc2;   // jeans_length_refine (n_jeans <= 0: off)
   double thr, var_cut;                         // thr_mode 1: uold(1) >= thr;  2: uold(ivar)/uold(1) > var_cut;  0: off
   int thr_mode, ivar;                          // ivar: 0-based variable of thr_mode 2
 };
 // twopi/2d0 of the reference's constants module (amr/constants.f90:5-6: twopi = 6.2831853d0, not the double nearest to pi)
 #define RAMSES_PI (6.2831853 / 2.0)
-// the two neighbour cells of cell (ind, oct g) in direction d (getnborcells); a missing one is replaced by the neighbouring father
-// cell (hydro/hydro_flag.f90:107-117)
+// the two neighbour cells of cell (ind, oct g) in direction d; a missing one is replaced by the neighbouring father cell
 __device__ __forceinline__ void refine_nbors(const LvlArgs &A, long c, int ind, int g, int d, long (&cn)[2]) {
+  bool coarse;
 #pragma unroll
-  for (int side = 0; side < 2; side++) {
-    const int bit = (ind >> d) & 1;
-    if (bit != side) {
-      cn[side] = c + (side ? 1 : -1) * ((long)(1 << d) * A.ngridmax);
-    } else {
-      const int nb = A.nbor[(long)(2 * d + side) * A.ngridmax + g - 1];
-      const int g2 = A.son[nb - 1];
-      cn[side] = g2 > 0 ? A.ncoarse + (long)(ind ^ (1 << d)) * A.ngridmax + g2 - 1 : (long)nb - 1;
-    }
-  }
+  for (int side = 0; side < 2; side++) cn[side] = lvl_nbor(A, c, ind, g, d, side, coarse);
 }
 // hydro_refine (hydro/godunov_utils.f90:125-263) on a cell and its two neighbours of one direction
 __device__ __forceinline__ bool refine_grad(const FlagCrit &F, const double (&qg)[5], const double (&qm)[5], const double (&qd)[5]) {
@@ -301,7 +246,8 @@ __device__ __forceinline__ bool refine_grad(const FlagCrit &F, const double (&qg
   }
   return flag;
 }
-// the flagged cells of a wavefront into the compact list: one atomic per wavefront (as lvl_flag_kernel)
+// the cells that ask for refinement as a compact list of 1-based cell indices: one atomic per wavefront; the order is whatever
+// the waves arrive in -- the host sorts the few that come back.  EVERY lane of the wavefront calls this (ballot, shuffle)
 __device__ __forceinline__ void refine_compact(bool flag, long c, int *__restrict__ list, int *__restrict__ count) {
   const unsigned long long m = __ballot(flag);
   if (m) {
@@ -322,9 +268,8 @@ __global__ __launch_bounds__(256) void lvl_refine_kernel(LvlArgs A, RefineCrit X
     bool flag = false;
     long c = 0;
     if (t < total) {
-      const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-      const int g = A.igrid[i];
-      c = A.ncoarse + (long)ind * A.ngridmax + g - 1;
+      int ind, g;
+      c = lvl_cell(A, t, ind, g);
       if (GRAD) {
         double qm[5];
         refine_prim(A, c, X.F, qm);
@@ -374,8 +319,7 @@ __global__ __launch_bounds__(256) void lvl_mass_map_kernel(LvlArgs A, const doub
     bool flag = false;
     long c = 0;
     if (t < total) {
-      const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-      c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
+      c = lvl_cell(A, t);
       double phi_n = 0.0;
       bool take = true;
       if (IVAR) take = A.uold[c + (long)ivar * A.ncell] / __builtin_fmax(A.uold[c], smallr) > var_cut;
@@ -391,8 +335,7 @@ __global__ __launch_bounds__(256) void lvl_mass_map_kernel(LvlArgs A, const doub
 __global__ __launch_bounds__(256) void lvl_synchro_kernel(LvlArgs A, const double *__restrict__ f, double dteff, double smallr) {
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const long c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
+    const long c = lvl_cell(A, t);
     const double d = __builtin_fmax(A.uold[c], smallr);
     double m[3] = {A.uold[c + A.ncell], A.uold[c + 2 * A.ncell], A.uold[c + 3 * A.ncell]};
     double pp = A.uold[c + 4 * A.ncell];
@@ -413,8 +356,7 @@ __global__ __launch_bounds__(256) void lvl_synchro_kernel(LvlArgs A, const doubl
 __global__ __launch_bounds__(256) void lvl_gravity_source_kernel(LvlArgs A, const double *__restrict__ f, double dt, double smallr) {
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const long c = A.ncoarse + (long)ind * A.ngridmax + A.igrid[i] - 1;
+    const long c = lvl_cell(A, t);
     const long N = A.ncell;
     const double d = __builtin_fmax(A.unew[c], smallr);
     double u = A.unew[c + N] / d, v = A.unew[c + 2 * N] / d, w = A.unew[c + 3 * N] / d;
@@ -434,33 +376,33 @@ __global__ __launch_bounds__(256) void lvl_gravity_source_kernel(LvlArgs A, cons
   }
 }
 
-// one variable (or ncomp of them, stride ncell) of the level's cells <-> packed [ncomp][8*ngrid]
+// the L.nvar variables of vec (stride ncell) on the level's cells <-> packed [nvar][8*ngrid]
 template <bool GATHER>
-__global__ void lvl_pack_comp_kernel(double *vec, double *buf, const int *igrid, int ngrid, int ncomp, long ncell, long ncoarse, long ngridmax) {
-  const long total = (long)ngrid * 8;
+__global__ void lvl_pack_comp_kernel(LvlList L, double *vec, double *buf) {
+  const long total = (long)L.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const long c = ncoarse + (long)(t / ngrid) * ngridmax + igrid[t % ngrid] - 1;
-    for (int k = 0; k < ncomp; k++) {
-      if (GATHER) buf[(long)k * total + t] = vec[c + (long)k * ncell];
-      else vec[c + (long)k * ncell] = buf[(long)k * total + t];
+    const long c = lvl_cell(L, t);
+    for (int k = 0; k < L.nvar; k++) {
+      if (GATHER) buf[(long)k * total + t] = vec[c + (long)k * L.ncell];
+      else vec[c + (long)k * L.ncell] = buf[(long)k * total + t];
     }
   }
 }
 
 // make_virtual_reverse_dp's scatter (amr/virtual_boundaries.f90:857-867): vec(emission cells) += what the peer's virtual cells held
-__global__ void lvl_acc_comp_kernel(double *vec, const double *buf, const int *igrid, int ngrid, int ncomp, long ncell, long ncoarse, long ngridmax) {
-  const long total = (long)ngrid * 8;
+__global__ void lvl_acc_comp_kernel(LvlList L, double *vec, const double *buf) {
+  const long total = (long)L.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const long c = ncoarse + (long)(t / ngrid) * ngridmax + igrid[t % ngrid] - 1;
-    for (int k = 0; k < ncomp; k++) vec[c + (long)k * ncell] = vec[c + (long)k * ncell] + buf[(long)k * total + t];
+    const long c = lvl_cell(L, t);
+    for (int k = 0; k < L.nvar; k++) vec[c + (long)k * L.ncell] = vec[c + (long)k * L.ncell] + buf[(long)k * total + t];
   }
 }
-// set_unew's loop over the virtual octs (hydro/godunov_fine.f90:92-122): vec(cells of the octs, 1:ncomp) = 0
-__global__ void lvl_zero_comp_kernel(double *vec, const int *igrid, int ngrid, int ncomp, long ncell, long ncoarse, long ngridmax) {
-  const long total = (long)ngrid * 8;
+// set_unew's loop over the virtual octs (hydro/godunov_fine.f90:92-122): vec(cells of the octs, 1:nvar) = 0
+__global__ void lvl_zero_comp_kernel(LvlList L, double *vec) {
+  const long total = (long)L.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const long c = ncoarse + (long)(t / ngrid) * ngridmax + igrid[t % ngrid] - 1;
-    for (int k = 0; k < ncomp; k++) vec[c + (long)k * ncell] = 0.0;
+    const long c = lvl_cell(L, t);
+    for (int k = 0; k < L.nvar; k++) vec[c + (long)k * L.ncell] = 0.0;
   }
 }
 
@@ -469,7 +411,7 @@ __global__ void lvl_zero_comp_kernel(double *vec, const int *igrid, int ngrid, i
 __global__ __launch_bounds__(256) void lvl_pfix_init_kernel(LvlArgs A, double *__restrict__ divu, double *__restrict__ enew, double smallr) {
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const long c = A.ncoarse + (long)(t / A.ngrid) * A.ngridmax + A.igrid[t % A.ngrid] - 1;
+    const long c = lvl_cell(A, t);
     const long N = A.ncell;
     const double d = __builtin_fmax(A.uold[c], smallr);
     const double u = A.uold[c + N] / d, v = A.uold[c + 2 * N] / d, w = A.uold[c + 3 * N] / d;
@@ -482,27 +424,18 @@ __global__ __launch_bounds__(256) void lvl_pfix_init_kernel(LvlArgs A, double *_
 __global__ __launch_bounds__(256) void lvl_pdv_kernel(LvlArgs A, double *__restrict__ enew, double dx_loc, double dt, double gamma, double smallr) {
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.ngrid), i = (int)(t % A.ngrid);
-    const int g = A.igrid[i];
+    int ind, g;
+    const long c = lvl_cell(A, t, ind, g);
     const long N = A.ncell;
-    const long c = A.ncoarse + (long)ind * A.ngridmax + g - 1;
     double divu_loc = 0.0;
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-      const int bit = (ind >> d) & 1, jnd = ind ^ (1 << d);
       double vel[2], dxs[2];
 #pragma unroll
       for (int side = 0; side < 2; side++) {
-        long cn;
-        dxs[side] = dx_loc;
-        if (bit != side) {
-          cn = A.ncoarse + (long)jnd * A.ngridmax + g - 1;             // inside the oct
-        } else {
-          const int nb = A.nbor[(long)(2 * d + side) * A.ngridmax + g - 1];
-          const int g2 = A.son[nb - 1];
-          if (g2 > 0) cn = A.ncoarse + (long)jnd * A.ngridmax + g2 - 1;
-          else { cn = nb - 1; dxs[side] = dx_loc * 1.5; }
-        }
+        bool coarse;
+        const long cn = lvl_nbor(A, c, ind, g, d, side, coarse);
+        dxs[side] = coarse ? dx_loc * 1.5 : dx_loc;
         vel[side] = A.uold[cn + (long)(d + 1) * N] / __builtin_fmax(A.uold[cn], smallr);
       }
       divu_loc = divu_loc + (vel[1] - vel[0]) / (dxs[0] + dxs[1]);
@@ -518,7 +451,7 @@ __global__ __launch_bounds__(256) void lvl_pfix_switch_kernel(LvlArgs A, const d
                                                               double dt, double beta_fix, double hexp, double smallr) {
   const long total = (long)A.ngrid * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const long c = A.ncoarse + (long)(t / A.ngrid) * A.ngridmax + A.igrid[t % A.ngrid] - 1;
+    const long c = lvl_cell(A, t);
     const long N = A.ncell;
     const double d = __builtin_fmax(A.uold[c], smallr);
     const double u = A.uold[c + N] / d, v = A.uold[c + 2 * N] / d, w = A.uold[c + 3 * N] / d;
@@ -863,8 +796,7 @@ __global__ __launch_bounds__(256) void bnd_compute_kernel(BndArgs A) {
 __global__ __launch_bounds__(256) void bnd_store_kernel(BndArgs A) {
   const long total = (long)A.n * 8;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-    const int ind = (int)(t / A.n), i = (int)(t % A.n);
-    const long c = A.ncoarse + (long)ind * A.ngridmax + A.list[i] - 1;
+    const long c = lvl_cell(LvlList{A.list, A.n, A.nvar, A.ncell, A.ncoarse, A.ngridmax}, t);
     for (int v = 0; v < A.nvar; v++) A.uold[(long)v * A.ncell + c] = A.tmp[(long)v * total + t];
   }
 }
@@ -963,6 +895,10 @@ struct AmrRes {
 AmrRes g_ar;
 
 constexpr int GRID_CAP = 8192;   // blocks of this unit's one-dimensional launches: grid_for(n, GRID_CAP)
+// one thread per cell of a level's oct list, in workgroups of 256: the launch geometry of every kernel that goes through lvl_cell
+dim3 lvl_grid(int ngrid) { return dim3(grid_for((long)ngrid * 8, GRID_CAP)); }
+// an oct list on the device for a resident vector of ncomp variables
+LvlList lvl_list(const AmrRes &R, const int *d_ig, int n, int ncomp) { return LvlList{d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax}; }
 
 // RAMSES_AMD_EVENT_ORDER (A/B of the order the surface pass visits the (oct, face) events in): face | tile | oct
 int event_order() {
@@ -1065,8 +1001,8 @@ int set_level(AmrRes &R, int ngrid, const int *igrid, LvlArgs &A) {
     R.cur_slot = hit;
   }
   A.uold = R.uold.as<double>(); A.unew = R.unew.as<double>();
-  A.son = R.son.as<int>(); A.nbor = R.nbor.as<int>(); A.igrid = R.cur_ig;
-  A.ngrid = ngrid; A.nvar = R.nvar; A.ncell = R.ncell; A.ncoarse = R.ncoarse; A.ngridmax = R.ngridmax;
+  A.son = R.son.as<int>(); A.nbor = R.nbor.as<int>();
+  static_cast<LvlList &>(A) = lvl_list(R, R.cur_ig, ngrid, R.nvar);
   return 0;
 }
 
@@ -1079,7 +1015,7 @@ int xfer_hip(hipError_t e, const char *step, const char *what) { return e == hip
 int level_fetch(AmrRes &R, double *dvec, int ncomp, const int *d_ig, int n, hipStream_t s, const char *what) {
   const size_t cnt = (size_t)n * 8 * (size_t)ncomp;
   XCHK(R.pack.ensure(sizeof(double) * cnt), "hipMalloc");
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, s, dvec, R.pack.as<double>(), d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax);
+  hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, lvl_grid(n), dim3(256), 0, s, lvl_list(R, d_ig, n, ncomp), dvec, R.pack.as<double>());
   XCHK(hipGetLastError(), "pack launch");
   R.hpack.resize(cnt);
   XCHK(hipMemcpy(R.hpack.data(), R.pack.p, sizeof(double) * cnt, hipMemcpyDeviceToHost), "D2H");
@@ -1108,7 +1044,7 @@ int level_from_host(AmrRes &R, double *dvec, int ncomp, const int *d_ig, int n, 
     }
   XCHK(R.pack.ensure(sizeof(double) * cnt), "hipMalloc");
   XCHK(hipMemcpy(R.pack.p, R.hpack.data(), sizeof(double) * cnt, hipMemcpyHostToDevice), "H2D");
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, dvec, R.pack.as<double>(), d_ig, n, ncomp, R.ncell, R.ncoarse, R.ngridmax);
+  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, lvl_grid(n), dim3(256), 0, nullptr, lvl_list(R, d_ig, n, ncomp), dvec, R.pack.as<double>());
   XCHK(hipGetLastError(), "unpack launch");
   XCHK(hipStreamSynchronize(nullptr), "sync");
   return 0;
@@ -1336,24 +1272,35 @@ int ramses_amd_amrres_sync_all(double *uold) {
   return 0;
 }
 
+// How a level entry opens, each refusal in its fixed place: NENER / NVAR, NULL p, the resident state and the list (set_level), what
+// the entry needs on the device (`what`: the routine's name in that refusal's text), and for a list that is not empty the list in
+// device order (sorted_list).  0 with ngrid == 0: nothing to do.  An entry that does anything in between opens with the plain calls.
+enum LvlNeed { NEED_NONE, NEED_GRAV, NEED_PFIX };
+static int level_entry(const ramses_amd_hydro_params *p, const char *who, int ngrid, const int *igrid, LvlArgs &A, LvlNeed need = NEED_NONE,
+                       const char *what = nullptr) {
+  if (int rc = refuse_amr(p, who)) return rc;
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
+  if (need == NEED_GRAV && !g_ar.grav) return fail(RAMSES_AMD_EINVAL, "%s: no acceleration on the device (ramses_amd_amrres_load_f)", what);
+  if (need == NEED_PFIX && !g_ar.pfix) return fail(RAMSES_AMD_EINVAL, "%s: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)", what);
+  return ngrid == 0 ? 0 : sorted_list(g_ar, A);
+}
+
 int ramses_amd_amrres_set_unew(int ngrid, const int *igrid) {
   LvlArgs A;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  hipLaunchKernelGGL(lvl_copy_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, A.unew, A.uold);
+  hipLaunchKernelGGL(lvl_copy_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, A, A.unew, A.uold);
   HCHK(hipGetLastError(), "set_unew launch");
   return 0;
 }
 
 int ramses_amd_amrres_set_uold(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
-  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold")) return rc_;
-  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
-  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
+  if (int rc = level_entry(p, "ramses_amd_amrres_set_uold", ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
-  if (int rc = sorted_list(g_ar, A)) return rc;
-  hipLaunchKernelGGL(lvl_set_uold_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, p->smallr);
+  hipLaunchKernelGGL(lvl_set_uold_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, A, p->smallr);
   HCHK(hipGetLastError(), "set_uold launch");
   return 0;
 }
@@ -1366,7 +1313,7 @@ int ramses_amd_amrres_upload_fine(const ramses_amd_hydro_params *p, int ngrid, c
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
   if (int rc = sorted_list(g_ar, A)) return rc;
-  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
+  const dim3 g = lvl_grid(ngrid), b(256);
   switch (A.nvar) {
     case 5: hipLaunchKernelGGL(lvl_upload_kernel<5>, g, b, 0, nullptr, A, interpol_var, p->smallr); break;
     case 6: hipLaunchKernelGGL(lvl_upload_kernel<6>, g, b, 0, nullptr, A, interpol_var, p->smallr); break;
@@ -1400,38 +1347,16 @@ int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const
   return check_lists(R, "courant_fine");
 }
 
-// hydro_flag's gradient criteria: the cells (1-based indices into the cell vectors, ascending) where hydro_refine asks
-// for refinement come back as a compact list -- cells[0..*ncells), capacity 8*ngrid -- and nothing else crosses PCIe
-int ramses_amd_amrres_hydro_flag(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double err_grad_d, double err_grad_p,
-                                 double err_grad_u, double floor_d, double floor_p, double floor_u, int *cells, int *ncells) {
-  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_hydro_flag")) return rc_;
-  if (!p || !cells || !ncells) return fail(RAMSES_AMD_EINVAL, "NULL argument");
-  *ncells = 0;
-  LvlArgs A;
-  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
-  if (ngrid == 0) return 0;
-  if (A.nvar < 5) return fail(RAMSES_AMD_EUNSUPPORTED, "NVAR");
-  AmrRes &R = g_ar;
-  if (int rc = sorted_list(R, A)) return rc;          // (the flagged cells come back sorted anyway)
-  HCHK(R.okbuf.ensure(sizeof(int) * (8 * (size_t)ngrid + 1)), "hipMalloc");
-  int *d_count = R.okbuf.as<int>(), *d_list = d_count + 1;
-  HCHK(hipMemsetAsync(d_count, 0, sizeof(int), nullptr), "memset");
-  FlagCrit F = {err_grad_d, err_grad_p, err_grad_u, floor_d, floor_p, floor_u, p->gamma, p->smallr};
-  hipLaunchKernelGGL(lvl_flag_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, F, d_list, d_count);
-  HCHK(hipGetLastError(), "hydro_flag launch");
-  int n = 0;
-  HCHK(hipMemcpy(&n, d_count, sizeof(int), hipMemcpyDeviceToHost), "D2H flag count");
-  if (n < 0 || (long)n > 8L * ngrid) return fail(RAMSES_AMD_EHIP, "hydro_flag: bad flag count %d", n);
-  if (n > 0) {
-    if (R.map.on) hipLaunchKernelGGL(amrlayout::cells_d2h_kernel, dim3(amrlayout::grid1(n)), dim3(256), 0, nullptr, d_list, n, R.map.iperm.as<int>(), R.ncoarse, R.ngh, R.ngridmax);
-    HCHK(hipMemcpy(cells, d_list, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost), "D2H flagged cells");
-    std::sort(cells, cells + n);
-  }
-  *ncells = n;
-  return check_lists(R, "hydro_flag");
-}
-
 namespace {
+// the list of the level in device order (the flagged cells come back sorted anyway) and the compact list's buffer: the count, zeroed,
+// then room for every cell of the level
+int flag_buffer(AmrRes &R, LvlArgs &A, int *&d_count) {
+  if (int rc = sorted_list(R, A)) return rc;
+  HCHK(R.okbuf.ensure(sizeof(int) * (8 * (size_t)A.ngrid + 1)), "hipMalloc");
+  d_count = R.okbuf.as<int>();
+  HCHK(hipMemsetAsync(d_count, 0, sizeof(int), nullptr), "memset");
+  return 0;
+}
 // the compact list a flag kernel left behind d_count, into the host's cell numbers, ascending
 int fetch_flag_list(AmrRes &R, int ngrid, int *d_count, int *cells, int *ncells, const char *who) {
   int *d_list = d_count + 1;
@@ -1446,12 +1371,42 @@ int fetch_flag_list(AmrRes &R, int ngrid, int *d_count, int *cells, int *ncells,
   *ncells = n;
   return check_lists(R, who);
 }
+// lvl_refine_kernel on a level that is set and not empty, and its list home: what both flag entries end in (`launch`: the HIP
+// error's text).  With all three gradient criteria off the kernel without the neighbour gathers runs
+int run_refine(AmrRes &R, LvlArgs &A, const RefineCrit &X, int *cells, int *ncells, const char *who, const char *launch) {
+  int *d_count = nullptr;
+  if (int rc = flag_buffer(R, A, d_count)) return rc;
+  const dim3 g = lvl_grid(A.ngrid), b(256);
+  if (X.F.err_grad_d >= 0.0 || X.F.err_grad_p >= 0.0 || X.F.err_grad_u >= 0.0)
+    hipLaunchKernelGGL(lvl_refine_kernel<true>, g, b, 0, nullptr, A, X, d_count + 1, d_count);
+  else
+    hipLaunchKernelGGL(lvl_refine_kernel<false>, g, b, 0, nullptr, A, X, d_count + 1, d_count);
+  HCHK(hipGetLastError(), launch);
+  return fetch_flag_list(R, A.ngrid, d_count, cells, ncells, who);
+}
 int check_ivar_refine(const char *who, int ivar_refine, int nvar) {
   if (ivar_refine != 0 && (ivar_refine < 6 || ivar_refine > nvar))
     return fail(RAMSES_AMD_EINVAL, "%s: ivar_refine=%d must be 0 or a passive scalar 6 .. nvar=%d", who, ivar_refine, nvar);
   return 0;
 }
 }  // namespace
+
+// hydro_flag's gradient criteria: the cells (1-based indices into the cell vectors, ascending) where hydro_refine asks
+// for refinement come back as a compact list -- cells[0..*ncells), capacity 8*ngrid -- and nothing else crosses PCIe.
+// (ramses_amd_amrres_refine_flag with the other criteria off: the same kernel)
+int ramses_amd_amrres_hydro_flag(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double err_grad_d, double err_grad_p,
+                                 double err_grad_u, double floor_d, double floor_p, double floor_u, int *cells, int *ncells) {
+  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_hydro_flag")) return rc_;
+  if (!p || !cells || !ncells) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  *ncells = 0;
+  LvlArgs A;
+  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
+  if (ngrid == 0) return 0;
+  if (A.nvar < 5) return fail(RAMSES_AMD_EUNSUPPORTED, "NVAR");
+  RefineCrit X = {};                                       // n_jeans = 0, thr_mode = 0: off
+  X.F = {err_grad_d, err_grad_p, err_grad_u, floor_d, floor_p, floor_u, p->gamma, p->smallr};
+  return run_refine(g_ar, A, X, cells, ncells, "hydro_flag", "hydro_flag launch");
+}
 
 size_t ramses_amd_refine_crit_size(void) { return sizeof(ramses_amd_refine_crit); }
 
@@ -1477,23 +1432,12 @@ int ramses_amd_amrres_refine_flag(const ramses_amd_hydro_params *p, int ngrid, c
   if (ngrid == 0) return 0;
   if (A.nvar < 5) return fail(RAMSES_AMD_EUNSUPPORTED, "%s: NVAR", who);
   if (crit->ivar_refine > A.nvar) return fail(RAMSES_AMD_EINVAL, "%s: ivar_refine=%d beyond the resident state's nvar=%d", who, crit->ivar_refine, A.nvar);
-  AmrRes &R = g_ar;
-  if (int rc = sorted_list(R, A)) return rc;          // (the flagged cells come back sorted anyway)
-  HCHK(R.okbuf.ensure(sizeof(int) * (8 * (size_t)ngrid + 1)), "hipMalloc");
-  int *d_count = R.okbuf.as<int>();
-  HCHK(hipMemsetAsync(d_count, 0, sizeof(int), nullptr), "memset");
   RefineCrit X;
   X.F = {crit->err_grad_d, crit->err_grad_p, crit->err_grad_u, crit->floor_d, crit->floor_p, crit->floor_u, p->gamma, p->smallr};
   X.n_jeans = crit->n_jeans; X.tail_pix = crit->tail_pix; X.factG = crit->factG > 0.0 ? crit->factG : 1.0;
   X.gm1 = p->gamma - 1.0; X.smallc2 = p->smallc * p->smallc;
   X.thr = crit->thr; X.var_cut = crit->var_cut_refine; X.thr_mode = crit->thr_mode; X.ivar = crit->ivar_refine - 1;
-  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
-  if (crit->err_grad_d >= 0.0 || crit->err_grad_p >= 0.0 || crit->err_grad_u >= 0.0)
-    hipLaunchKernelGGL(lvl_refine_kernel<true>, g, b, 0, nullptr, A, X, d_count + 1, d_count);
-  else
-    hipLaunchKernelGGL(lvl_refine_kernel<false>, g, b, 0, nullptr, A, X, d_count + 1, d_count);
-  HCHK(hipGetLastError(), "refine_flag launch");
-  return fetch_flag_list(R, ngrid, d_count, cells, ncells, who);
+  return run_refine(g_ar, A, X, cells, ncells, who, "refine_flag launch");
 }
 
 // rho_fine's quasi-Lagrangian refinement map of the level's own cells (pm/rho_fine.f90:96-118: phi = rho/d_scale, with
@@ -1521,11 +1465,9 @@ int ramses_amd_amrres_mass_map(const ramses_amd_hydro_params *p, int ngrid, cons
   } else if (R.rho.cap < cb) {
     return fail(RAMSES_AMD_EINVAL, "%s: rho is NULL and the device holds no deposit (ramses_amd_amrres_rho_fine)", who);
   }
-  if (int rc = sorted_list(R, A)) return rc;
-  HCHK(R.okbuf.ensure(sizeof(int) * (8 * (size_t)ngrid + 1)), "hipMalloc");
-  int *d_count = R.okbuf.as<int>();
-  HCHK(hipMemsetAsync(d_count, 0, sizeof(int), nullptr), "memset");
-  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
+  int *d_count = nullptr;
+  if (int rc = flag_buffer(R, A, d_count)) return rc;
+  const dim3 g = lvl_grid(ngrid), b(256);
   if (ivar_refine > 0)
     hipLaunchKernelGGL(lvl_mass_map_kernel<true>, g, b, 0, nullptr, A, R.rho.as<double>(), d_scale, m_refine, ivar_refine - 1, var_cut_refine, p->smallr, d_count + 1, d_count);
   else
@@ -1555,7 +1497,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   int *cnt = R.okbuf.as<int>();
   HCHK(hipMemsetAsync(cnt, 0, sizeof(int) * 2, s), "memset");
   hipLaunchKernelGGL(plan_clear_kernel, dim3(grid_for(L.cap * 8, GRID_CAP)), dim3(256), 0, s, A.stat, A.octpos, R.ncoarse, R.ngridmax, L.base, L.cap, P.gfather.as<int>());
-  hipLaunchKernelGGL(plan_owned_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, s, A);
+  hipLaunchKernelGGL(plan_owned_kernel, lvl_grid(ngrid), dim3(256), 0, s, A);
   // (a level that holds every oct of the periodic box has no neighbour position without an oct)
   if ((long)L.n < (long)L.no * L.no * L.no)
     hipLaunchKernelGGL(plan_ghost_kernel, dim3(grid_for((long)ngrid * 26, GRID_CAP)), dim3(256), 0, s, A, P.gfather.as<int>(), P.gslot.as<int>(), P.gcell.as<int>(), cnt, gcap, cnt + 1);
@@ -1887,8 +1829,8 @@ int ramses_amd_amrres_take_f_device(int ngrid, const int *igrid, const double *d
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (int rc = ensure_f(R)) return rc;
   if (ngrid == 0) return 0;
-  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, R.f.as<double>(), const_cast<double *>(d_fpack), R.cur_ig,
-                     ngrid, 3, R.ncell, R.ncoarse, R.ngridmax);
+  hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, lvl_grid(ngrid), dim3(256), 0, nullptr, lvl_list(R, R.cur_ig, ngrid, 3), R.f.as<double>(),
+                     const_cast<double *>(d_fpack));
   HCHK(hipGetLastError(), "f unpack launch");
   return 0;
 }
@@ -2080,16 +2022,14 @@ int ramses_amd_amrres_sync_rho(int ngrid, const int *igrid, double *rho) {
 // the deposit of the rank's own octs into a dense brick on the device: brick[order[ind * ngrid + g]] = rho(cell ind of oct igrid[g])
 // (order: the list of ramses_amd_mgdist_set_order); and max |rho| over those cells (force_fine's diagnostic, :177-181)
 namespace {
-__global__ __launch_bounds__(256) void rho_to_brick_kernel(const double *__restrict__ rho, const int *__restrict__ ig, const int *__restrict__ order, long ngrid,
-                                                           long ncoarse, long ngridmax, double *__restrict__ brick) {
+__global__ __launch_bounds__(256) void rho_to_brick_kernel(LvlList L, const double *__restrict__ rho, const int *__restrict__ order, double *__restrict__ brick) {
   const long k = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < 8 * ngrid) brick[order[k]] = rho[ncoarse + (k / ngrid) * ngridmax + ig[k % ngrid] - 1];
+  if (k < 8 * (long)L.ngrid) brick[order[k]] = rho[lvl_cell(L, k)];
 }
-__global__ __launch_bounds__(256) void rho_absmax_kernel(const double *__restrict__ rho, const int *__restrict__ ig, long ngrid, long ncoarse, long ngridmax,
-                                                         unsigned long long *__restrict__ out) {
+__global__ __launch_bounds__(256) void rho_absmax_kernel(LvlList L, const double *__restrict__ rho, unsigned long long *__restrict__ out) {
   double m = 0.0;
-  for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < 8 * ngrid; k += (long)gridDim.x * blockDim.x)
-    m = fmax(m, fabs(rho[ncoarse + (k / ngrid) * ngridmax + ig[k % ngrid] - 1]));
+  for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < 8 * (long)L.ngrid; k += (long)gridDim.x * blockDim.x)
+    m = fmax(m, fabs(rho[lvl_cell(L, k)]));
   // (non-negative doubles order like their bit patterns)
   atomicMax(out, (unsigned long long)__double_as_longlong(m));
 }
@@ -2101,8 +2041,8 @@ int ramses_amd_amrres_rho_to_brick(int ngrid, const int *igrid, const int *d_ord
   if (!R.rho.p) return fail(RAMSES_AMD_EINVAL, "rho_to_brick: rho_fine has not run on the device");
   if (int rc = set_level(R, ngrid, igrid, A)) return rc;
   if (ngrid == 0) return 0;
-  hipLaunchKernelGGL(rho_to_brick_kernel, dim3((unsigned)(((long)ngrid * 8 + 255) / 256)), dim3(256), 0, nullptr, R.rho.as<double>(), R.cur_ig, d_order, (long)ngrid,
-                     R.ncoarse, R.ngridmax, d_brick);
+  hipLaunchKernelGGL(rho_to_brick_kernel, dim3((unsigned)(((long)ngrid * 8 + 255) / 256)), dim3(256), 0, nullptr, lvl_list(R, R.cur_ig, ngrid, 1), R.rho.as<double>(),
+                     d_order, d_brick);
   HCHK(hipGetLastError(), "rho -> brick launch");
   return 0;
 }
@@ -2117,7 +2057,7 @@ int ramses_amd_amrres_rho_absmax(int ngrid, const int *igrid, double *out) {
   HCHK(R.okbuf.ensure(sizeof(unsigned long long) * 2), "hipMalloc");
   unsigned long long *d = reinterpret_cast<unsigned long long *>(R.okbuf.p);
   HCHK(hipMemsetAsync(d, 0, sizeof(unsigned long long), nullptr), "memset");
-  hipLaunchKernelGGL(rho_absmax_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, R.rho.as<double>(), R.cur_ig, (long)ngrid, R.ncoarse, R.ngridmax, d);
+  hipLaunchKernelGGL(rho_absmax_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, lvl_list(R, R.cur_ig, ngrid, 1), R.rho.as<double>(), d);
   HCHK(hipGetLastError(), "max |rho| launch");
   unsigned long long bits = 0;
   HCHK(hipMemcpy(&bits, d, sizeof(bits), hipMemcpyDeviceToHost), "D2H");
@@ -2138,29 +2078,21 @@ int ramses_amd_amrres_sync_density(int ngrid, const int *igrid, double *uold) {
 }
 
 int ramses_amd_amrres_synchro(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dteff) {
-  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_synchro")) return rc_;
-  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
-  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
-  if (!g_ar.grav) return fail(RAMSES_AMD_EINVAL, "synchro_hydro_fine: no acceleration on the device (ramses_amd_amrres_load_f)");
+  if (int rc = level_entry(p, "ramses_amd_amrres_synchro", ngrid, igrid, A, NEED_GRAV, "synchro_hydro_fine")) return rc;
   if (ngrid == 0) return 0;
-  if (int rc = sorted_list(g_ar, A)) return rc;
-  hipLaunchKernelGGL(lvl_synchro_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dteff, p->smallr);
+  hipLaunchKernelGGL(lvl_synchro_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dteff, p->smallr);
   HCHK(hipGetLastError(), "synchro launch");
   return 0;
 }
 
 // set_uold with poisson: add_gravity_source_terms on unew, then the scalar fix and uold = unew
 int ramses_amd_amrres_set_uold_grav(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt) {
-  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold_grav")) return rc_;
-  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
-  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
-  if (!g_ar.grav) return fail(RAMSES_AMD_EINVAL, "set_uold: no acceleration on the device (ramses_amd_amrres_load_f)");
+  if (int rc = level_entry(p, "ramses_amd_amrres_set_uold_grav", ngrid, igrid, A, NEED_GRAV, "set_uold")) return rc;
   if (ngrid == 0) return 0;
-  if (int rc = sorted_list(g_ar, A)) return rc;
-  hipLaunchKernelGGL(lvl_gravity_source_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dt, p->smallr);
-  hipLaunchKernelGGL(lvl_set_uold_kernel, dim3(grid_for((long)ngrid * 8, GRID_CAP)), dim3(256), 0, nullptr, A, p->smallr);
+  hipLaunchKernelGGL(lvl_gravity_source_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dt, p->smallr);
+  hipLaunchKernelGGL(lvl_set_uold_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, A, p->smallr);
   HCHK(hipGetLastError(), "set_uold launch");
   return 0;
 }
@@ -2178,14 +2110,10 @@ int ramses_amd_amrres_enable_pfix(void) {
 }
 // set_unew with pressure_fix: unew = uold, divu = 0, enew = internal energy
 int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
-  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_unew_pfix")) return rc_;
-  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
-  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
-  if (!g_ar.pfix) return fail(RAMSES_AMD_EINVAL, "set_unew: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
+  if (int rc = level_entry(p, "ramses_amd_amrres_set_unew_pfix", ngrid, igrid, A, NEED_PFIX, "set_unew")) return rc;
   if (ngrid == 0) return 0;
-  if (int rc = sorted_list(g_ar, A)) return rc;
-  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
+  const dim3 g = lvl_grid(ngrid), b(256);
   hipLaunchKernelGGL(lvl_copy_kernel, g, b, 0, nullptr, A, A.unew, A.uold);
   hipLaunchKernelGGL(lvl_pfix_init_kernel, g, b, 0, nullptr, A, g_ar.divu.as<double>(), g_ar.enew.as<double>(), p->smallr);
   HCHK(hipGetLastError(), "set_unew launch");
@@ -2194,15 +2122,11 @@ int ramses_amd_amrres_set_unew_pfix(const ramses_amd_hydro_params *p, int ngrid,
 // set_uold with pressure_fix: (add_gravity_source_terms,) add_pdv_source_terms, the scalar fix and uold = unew, the energy switch
 int ramses_amd_amrres_set_uold_pfix(const ramses_amd_hydro_params *p, int ngrid, const int *igrid, double dt, double dx_loc, double beta_fix,
                                     double hexp) {
-  if (int rc_ = refuse_amr(p, "ramses_amd_amrres_set_uold_pfix")) return rc_;
-  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
-  if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
-  AmrRes &R = g_ar;
-  if (!R.pfix) return fail(RAMSES_AMD_EINVAL, "set_uold: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)");
+  if (int rc = level_entry(p, "ramses_amd_amrres_set_uold_pfix", ngrid, igrid, A, NEED_PFIX, "set_uold")) return rc;
   if (ngrid == 0) return 0;
-  if (int rc = sorted_list(g_ar, A)) return rc;
-  const dim3 g(grid_for((long)ngrid * 8, GRID_CAP)), b(256);
+  AmrRes &R = g_ar;
+  const dim3 g = lvl_grid(ngrid), b(256);
   if (R.grav) hipLaunchKernelGGL(lvl_gravity_source_kernel, g, b, 0, nullptr, A, R.f.as<double>(), dt, p->smallr);
   hipLaunchKernelGGL(lvl_pdv_kernel, g, b, 0, nullptr, A, R.enew.as<double>(), dx_loc, dt, p->gamma, p->smallr);
   hipLaunchKernelGGL(lvl_set_uold_kernel, g, b, 0, nullptr, A, p->smallr);
@@ -2313,8 +2237,8 @@ int halo_pack(AmrRes &R, CommLevel &L, const HaloSpec &S) {
   for (int c = 0; c < L.ncpu; c++) {
     const int n = sf[c + 1] - sf[c];
     if (n <= 0) continue;
-    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.halo.sendbuf.as<double>() + per * sf[c],
-                       sig + sf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
+    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, lvl_grid(n), dim3(256), 0, nullptr, lvl_list(R, sig + sf[c], n, S.ncomp), S.vec,
+                       R.halo.sendbuf.as<double>() + per * sf[c]);
   }
   HCHK(hipGetLastError(), "halo pack launch");
   return 0;
@@ -2327,10 +2251,10 @@ int halo_unpack(AmrRes &R, CommLevel &L, const HaloSpec &S) {
   for (int c = 0; c < L.ncpu; c++) {
     const int n = rf[c + 1] - rf[c];
     if (n <= 0) continue;
-    if (S.reverse) hipLaunchKernelGGL(lvl_acc_comp_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.halo.recvbuf.as<double>() + per * rf[c],
-                                      rig + rf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
-    else hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, S.vec, R.halo.recvbuf.as<double>() + per * rf[c],
-                            rig + rf[c], n, S.ncomp, R.ncell, R.ncoarse, R.ngridmax);
+    if (S.reverse) hipLaunchKernelGGL(lvl_acc_comp_kernel, lvl_grid(n), dim3(256), 0, nullptr, lvl_list(R, rig + rf[c], n, S.ncomp), S.vec,
+                                      R.halo.recvbuf.as<double>() + per * rf[c]);
+    else hipLaunchKernelGGL(lvl_pack_comp_kernel<false>, lvl_grid(n), dim3(256), 0, nullptr, lvl_list(R, rig + rf[c], n, S.ncomp), S.vec,
+                            R.halo.recvbuf.as<double>() + per * rf[c]);
   }
   HCHK(hipGetLastError(), "halo unpack launch");
   return 0;
@@ -2385,11 +2309,11 @@ int ramses_amd_amrres_boundary_hydro(int nregion, const int *btype, const int *n
         const size_t cnt = (size_t)n * 8 * (size_t)R.nvar;
         HCHK(hipMemcpyAsync(A.tmp, imposed + imp_off, sizeof(double) * cnt, hipMemcpyHostToDevice, nullptr), "H2D imposed states");
         imp_off += (long)cnt;
-        hipLaunchKernelGGL(bnd_store_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, A);
+        hipLaunchKernelGGL(bnd_store_kernel, lvl_grid(n), dim3(256), 0, nullptr, A);
       } else {
         hipLaunchKernelGGL(bnd_mark_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, nullptr, A, 0);
-        hipLaunchKernelGGL(bnd_compute_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, A);
-        hipLaunchKernelGGL(bnd_store_kernel, dim3(grid_for((long)n * 8, GRID_CAP)), dim3(256), 0, nullptr, A);
+        hipLaunchKernelGGL(bnd_compute_kernel, lvl_grid(n), dim3(256), 0, nullptr, A);
+        hipLaunchKernelGGL(bnd_store_kernel, lvl_grid(n), dim3(256), 0, nullptr, A);
         hipLaunchKernelGGL(bnd_mark_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, nullptr, A, 1);
       }
     }
@@ -2409,11 +2333,12 @@ int ramses_amd_amrres_zero_unew_virtual(int ilevel) {
   if (int rc = comm_of(R, ilevel, L)) return rc;
   const int n = L->rc_first[L->ncpu];
   if (n <= 0) return 0;
-  const dim3 g(grid_for((long)n * 8, GRID_CAP)), b(256);
-  hipLaunchKernelGGL(lvl_zero_comp_kernel, g, b, 0, nullptr, R.unew.as<double>(), L->rc_ig.as<int>(), n, R.nvar, R.ncell, R.ncoarse, R.ngridmax);
+  const dim3 g = lvl_grid(n), b(256);
+  const int *ig = L->rc_ig.as<int>();                          // the virtual octs
+  hipLaunchKernelGGL(lvl_zero_comp_kernel, g, b, 0, nullptr, lvl_list(R, ig, n, R.nvar), R.unew.as<double>());
   if (R.pfix) {
-    hipLaunchKernelGGL(lvl_zero_comp_kernel, g, b, 0, nullptr, R.divu.as<double>(), L->rc_ig.as<int>(), n, 1, R.ncell, R.ncoarse, R.ngridmax);
-    hipLaunchKernelGGL(lvl_zero_comp_kernel, g, b, 0, nullptr, R.enew.as<double>(), L->rc_ig.as<int>(), n, 1, R.ncell, R.ncoarse, R.ngridmax);
+    hipLaunchKernelGGL(lvl_zero_comp_kernel, g, b, 0, nullptr, lvl_list(R, ig, n, 1), R.divu.as<double>());
+    hipLaunchKernelGGL(lvl_zero_comp_kernel, g, b, 0, nullptr, lvl_list(R, ig, n, 1), R.enew.as<double>());
   }
   HCHK(hipGetLastError(), "set_unew (virtual octs) launch");
   return 0;

@@ -1,11 +1,13 @@
 #!/usr/bin/env python
-"""The refinement-criteria kernels of a resident level beside lvl_flag_kernel, for a kernel trace:
+"""The refinement-criteria kernels of a resident level, for a kernel trace:
 
-    rocprofv3 --kernel-trace --stats -f csv -d DIR -o t -- python scripts/refine_flag_probe.py [L] [REPEATS]
+    rocprofv3 --kernel-trace --stats -f csv -d DIR -o t -- python scripts/refine_flag_probe.py [L] [REPEATS] [ONLY]
 
 Level L (default 7: 128^3 cells) complete, a mild random state with NVAR=7; each entry point is called REPEATS times on the
 level: ramses_amd_amrres_hydro_flag (three gradients), ramses_amd_amrres_refine_flag with the same gradients, with the Jeans
 criterion alone (no neighbour gathers), with everything at once, and ramses_amd_amrres_mass_map with ivar_refine 0 and 6.
+hydro_flag and refine_flag run the same kernel, lvl_refine_kernel<true>: ONLY (a prefix of the names below, e.g. hydro_flag)
+keeps a trace to the dispatches of one entry.
 Prints the number of cells each flags and the wall time per call (launch, count and list back to the host included)."""
 import ctypes as C
 import os
@@ -30,6 +32,7 @@ def vp(a):
 def main():
     L = int(sys.argv[1]) if len(sys.argv) > 1 else 7
     rep = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+    only = sys.argv[3] if len(sys.argv) > 3 else ""
     lib = ramses_amd.lib()
     T = ic.uniform_tree(L, order="morton")
     u = mild_tree_state(T, 3, nvar=7)
@@ -49,7 +52,7 @@ def main():
         return lambda: lib.ramses_amd_amrres_refine_flag(C.byref(p), len(ig), vp(ig), C.byref(crit), vp(cells), C.byref(n))
 
     runs = [
-        ("hydro_flag  (lvl_flag_kernel, three gradients)",
+        ("hydro_flag  (lvl_refine_kernel<true>, three gradients, the others off)",
          lambda: lib.ramses_amd_amrres_hydro_flag(C.byref(p), len(ig), vp(ig), 0.25, 0.25, 0.4, 1e-10, 1e-10, 1e-10, vp(cells), C.byref(n))),
         ("refine_flag (lvl_refine_kernel<true>, the same gradients)", flag(**grad)),
         ("refine_flag (lvl_refine_kernel<false>, Jeans alone)", flag(**jeans)),
@@ -61,6 +64,8 @@ def main():
     ]
     print("level %d: %d octs, %d cells, %d calls each" % (L, len(ig), 8 * len(ig), rep))
     for name, call in runs:
+        if not name.startswith(only):
+            continue
         check(call())
         t0 = time.perf_counter()
         for _ in range(rep):

@@ -8,14 +8,18 @@ ramses_amd_amrres_refine_flag / ramses_amd_amrres_mass_map) against a numpy rest
 on the refined shell (level L+1) of a synthetic tree whose level L is complete: L=4 in the host's numbering, L=6 in tiles and
 with RAMSES_AMD_DEVICE_ORDER=0, octs created in scrambled and in Z order.  Every list must EQUAL the checker's, sorted.  The
 state is helpers.harsh_tree_state with NVAR=7 and smallr=0.6; smallc and the thresholds are placed on quantiles of the checker's
-own intermediate values, and the shares that make a pass mean something are asserted on the numpy result alone."""
+own intermediate values, and the shares that make a pass mean something are asserted on the numpy result alone.
+ramses_amd_amrres_hydro_flag runs the same kernel with the other criteria off: its lists are compared with the checker's directly,
+not only with refine_flag's.  Both entries also run on short lists -- one oct (8 threads: one partial wavefront) and the 37 octs
+of helpers.level_case (296 threads: a full workgroup and a partial wavefront of 40 lanes) -- where the wavefront compaction and
+the guard of the last threads can go wrong, with thresholds on quantiles of the checker's values over that list's own cells."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
-from helpers import harsh_tree_state, shell_mask
+from helpers import harsh_tree_state, level_case, shell_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -135,15 +139,59 @@ def _params(K):
     return ramses_amd.make_params(nvar=NVAR, gamma=GAMMA, smallr=SMALLR, smallc=K["smallc"])
 
 
-def _flag(gpu_lib, K, **kw):
+def _flag(gpu_lib, K, ig=None, **kw):
     from ramses_amd._capi import check, make_refine_crit
-    ig = K["ig"]
+    ig = K["ig"] if ig is None else ig
     cells = np.zeros(8 * len(ig), np.int32)
     n = C.c_int(-1)
     crit = make_refine_crit(floor_d=FLOOR, floor_p=FLOOR, floor_u=FLOOR, **kw)
     p = _params(K)
     check(gpu_lib.ramses_amd_amrres_refine_flag(C.byref(p), len(ig), _vp(ig), C.byref(crit), _vp(cells), C.byref(n)))
     return cells[:n.value].copy()
+
+
+def _hydro_flag(gpu_lib, K, egd, egp, egu, ig=None):
+    """ramses_amd_amrres_hydro_flag's list"""
+    from ramses_amd._capi import check
+    ig = K["ig"] if ig is None else ig
+    cells = np.zeros(8 * len(ig), np.int32)
+    n = C.c_int(-1)
+    p = _params(K)
+    check(gpu_lib.ramses_amd_amrres_hydro_flag(C.byref(p), len(ig), _vp(ig), egd, egp, egu, FLOOR, FLOOR, FLOOR, _vp(cells), C.byref(n)))
+    return cells[:n.value].copy()
+
+
+@functools.lru_cache(maxsize=None)
+def _short(L, order, n):
+    """A short list of the level's octs -- the 37 that helpers.level_case draws from the same tree, or one of them -- with the
+    checker's values of its own cells: thresholds on their quantiles (a quarter of the cells per gradient criterion, a fifth for
+    the Jeans length and the density), the flags per criterion and the cells as the device lists them (1-based, ascending).
+    An oct below the density floor has eight equal densities and no density gradient, one on the smallc floor eight equal Jeans
+    lengths: no threshold splits those.  The one-oct list is the first of the 37 that every criterion splits."""
+    K = _case(L, order)
+    ig = np.ascontiguousarray(level_case(L, order)[0]["lists"][L + 1]["sub"])
+    if n == 1:
+        for g in ig:
+            S = _short_of(K, np.array([g], np.int32))
+            if all(0.1 <= f.mean() <= 0.9 for f in S["flags"].values()):
+                return S
+    assert len(ig) == n
+    return _short_of(K, ig)
+
+
+def _short_of(K, ig):
+    where = {int(g): i for i, g in enumerate(K["ig"])}
+    pos = np.array([where[int(g)] for g in ig])                    # (KeyError: not the tree of _case)
+    at = (np.arange(8)[:, None] * len(K["ig"]) + pos[None, :]).ravel()
+    S = dict(ig=ig, c=K["c"][at])
+    S["egd"], S["egp"], S["egu"] = (float(np.quantile(e[at], 0.75)) for e in K["err"])
+    S["n_jeans"] = float(np.quantile(K["lamb"][at], 0.2)) / K["tail_pix"]
+    S["thr"] = float(np.quantile(K["dens_raw"][at], 0.8))
+    S["flags"] = {"d": K["err"][0][at] > S["egd"], "p": K["err"][1][at] > S["egp"], "u": K["err"][2][at] > S["egu"],
+                  "jeans": S["n_jeans"] * K["tail_pix"] >= K["lamb"][at], "thr": K["dens_raw"][at] >= S["thr"]}
+    S["grad"] = S["flags"]["d"] | S["flags"]["p"] | S["flags"]["u"]
+    S["mixed"] = S["flags"]["d"] | S["flags"]["jeans"] | S["flags"]["thr"]
+    return S
 
 
 def _crit_args(K, name):
@@ -153,6 +201,7 @@ def _crit_args(K, name):
             "cut": dict(thr_mode=2, ivar_refine=6, var_cut_refine=K["cut"])}[name]
 
 
+SHORT = [(4, "scrambled", None, 1), (4, "scrambled", None, 37), (6, "scrambled", "1", 1), (6, "scrambled", "1", 37)]
 CASES = [(4, "scrambled", None), (6, "scrambled", "1"), (6, "scrambled", "0"), (6, "morton", "1"), (6, "morton", "0")]
 
 
@@ -171,6 +220,44 @@ def test_the_input_exercises_every_criterion_and_floor():
         for f in K["flags"].values():
             union |= f
         assert any((union != f).any() for f in K["flags"].values())
+
+
+def test_the_short_lists_flag_a_share_of_their_cells():
+    """(on the numpy result alone) on the one-oct and the 37-oct lists every criterion alone, the three gradients together and
+    density gradient | Jeans | threshold together flag 10 % .. 90 % of the list's cells: neither 'all' nor 'none' passes"""
+    for L, order, n in sorted({(L, order, n) for L, order, _, n in SHORT}):
+        S = _short(L, order, n)
+        assert len(S["c"]) == 8 * n and len(np.unique(S["ig"])) == n
+        for name, f in list(S["flags"].items()) + [("grad", S["grad"]), ("mixed", S["mixed"])]:
+            assert 0.1 <= f.mean() <= 0.9, (L, order, n, name, f.mean())
+
+
+@pytest.mark.parametrize("L,order,device_order,n", SHORT)
+def test_short_lists_equal_the_restated_reference(gpu_lib, monkeypatch, L, order, device_order, n):
+    """one partial wavefront (n = 1), one full workgroup and a partial wavefront (n = 37): hydro_flag and refine_flag against the
+    checker, in the host's numbering (L = 4) and in tiles (L = 6)"""
+    if device_order is None:
+        monkeypatch.delenv("RAMSES_AMD_DEVICE_ORDER", raising=False)
+    else:
+        monkeypatch.setenv("RAMSES_AMD_DEVICE_ORDER", device_order)
+    K, S = _case(L, order), _short(L, order, n)
+    _load(gpu_lib, K)
+    assert gpu_lib.ramses_amd_amrres_tiled_levels() == (2 if L == 6 else 0)
+    want = _cells(S, S["grad"])
+    got = _hydro_flag(gpu_lib, K, S["egd"], S["egp"], S["egu"], ig=S["ig"])
+    assert np.array_equal(got, want), ("hydro_flag", len(got), len(want))
+    got = _flag(gpu_lib, K, ig=S["ig"], err_grad_d=S["egd"], err_grad_p=S["egp"], err_grad_u=S["egu"])
+    assert np.array_equal(got, want), ("refine_flag", len(got), len(want))
+    for name, eg in (("d", (S["egd"], -1.0, -1.0)), ("p", (-1.0, S["egp"], -1.0)), ("u", (-1.0, -1.0, S["egu"]))):
+        got = _hydro_flag(gpu_lib, K, *eg, ig=S["ig"])
+        assert np.array_equal(got, _cells(S, S["flags"][name])), (name, len(got))
+    got = _flag(gpu_lib, K, ig=S["ig"], err_grad_d=S["egd"], n_jeans=S["n_jeans"], tail_pix=K["tail_pix"], factG=1.0, thr_mode=1, thr=S["thr"])
+    assert np.array_equal(got, _cells(S, S["mixed"])), ("mixed", len(got))
+    # the kernel without the neighbour gathers on the same partial wavefronts
+    got = _flag(gpu_lib, K, ig=S["ig"], n_jeans=S["n_jeans"], tail_pix=K["tail_pix"], factG=1.0)
+    assert np.array_equal(got, _cells(S, S["flags"]["jeans"])), ("jeans", len(got))
+    assert len(_hydro_flag(gpu_lib, K, -1.0, -1.0, -1.0, ig=S["ig"])) == 0
+    gpu_lib.ramses_amd_amrres_invalidate()
 
 
 @pytest.mark.parametrize("L,order,device_order", CASES)
@@ -197,15 +284,20 @@ def test_every_criterion_equals_the_restated_reference(gpu_lib, monkeypatch, L, 
             kw.update(_crit_args(K, name))
             union |= F[name]
         assert np.array_equal(_flag(gpu_lib, K, **kw), _cells(K, union)), mode
-    # gradient-only == ramses_amd_amrres_hydro_flag on the same state
+    # ramses_amd_amrres_hydro_flag on the same state: the checker's list for the gradients that are on (all three, each alone),
+    # which is also what refine_flag returns for them; all three off: an empty list and no error
     ig = K["ig"]
     p = _params(K)
-    for egd, egp, egu in ((K["egd"], K["egp"], K["egu"]), (K["egd"], -1.0, -1.0), (-1.0, -1.0, K["egu"])):
-        cells = np.zeros(8 * len(ig), np.int32)
-        n = C.c_int(-1)
-        check(gpu_lib.ramses_amd_amrres_hydro_flag(C.byref(p), len(ig), _vp(ig), egd, egp, egu, FLOOR, FLOOR, FLOOR, _vp(cells), C.byref(n)))
-        assert n.value > 0
-        assert np.array_equal(_flag(gpu_lib, K, err_grad_d=egd, err_grad_p=egp, err_grad_u=egu), cells[:n.value])
+    for names in (("d", "p", "u"), ("d",), ("p",), ("u",)):
+        egd, egp, egu = (K["eg" + k] if k in names else -1.0 for k in ("d", "p", "u"))
+        want = np.zeros(len(K["c"]), bool)
+        for k in names:
+            want |= F[k]
+        cells = _hydro_flag(gpu_lib, K, egd, egp, egu)
+        assert len(cells) > 0
+        assert np.array_equal(cells, _cells(K, want)), (names, len(cells), int(want.sum()))
+        assert np.array_equal(_flag(gpu_lib, K, err_grad_d=egd, err_grad_p=egp, err_grad_u=egu), cells)
+    assert len(_hydro_flag(gpu_lib, K, -1.0, -1.0, -1.0)) == 0
     # nothing asked for: nothing flagged
     assert len(_flag(gpu_lib, K)) == 0
     # the map, from the host's deposit and then from the copy that call left on the device
