@@ -867,6 +867,13 @@ int ramses_amd_mpires_invalidate(void);
  *                                  for refinement, compacted on the device; capacity of cells: 8*ngrid
  * ------------------------------------------------------------------------- */
 int ramses_amd_amrres_active(void);
+/* The coarse grid of the loads that follow (call it before ramses_amd_amrres_load; 1, 1, 1 until told): nx x ny x nz coarse cells
+ * (amr/amr_parameters.f90: nx, ny, nz; amr/amr_commons.f90: ncoarse = nx*ny*nz), coarse cell (i, j, k), 0-based, at index
+ * 1 + i + nx*j + nx*ny*k (amr/init_amr.f90 numbers son / nbor of the coarse level that way).  A box between walls has one more
+ * coarse cell per wall (nx = ny = nz = 3 between six).  The device's own oct numbering (levels in tiles, Z-order) starts from
+ * these positions; ramses_amd_amrres_load refuses an ncoarse that is not nx*ny*nz.  (A load of several coarse cells while the
+ * grid is still 1, 1, 1 keeps the host's numbering on the device: nothing says where the cells lie.) */
+int ramses_amd_amrres_coarse_grid(int nx, int ny, int nz);
 int ramses_amd_amrres_load(int nvar, int64_t ngridmax, int64_t ncoarse, const double *uold, const int *son, const int *nbor,
                            const int *father);
 int ramses_amd_amrres_tree(const int *son, const int *nbor, const int *father);

@@ -218,6 +218,7 @@ SYMBOLS = [
     ("ramses_amd_lowdim_device_sweeps", _i64, []),
     ("ramses_amd_lowdim_reference_sweeps", _i64, []),
     ("ramses_amd_amrres_active", _i, []),
+    ("ramses_amd_amrres_coarse_grid", _i, [_i, _i, _i]),
     ("ramses_amd_amrres_load", _i, [_i, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("ramses_amd_amrres_tree", _i, [_vp, _vp, _vp]),
     ("ramses_amd_amrres_first_changed", _i, []),

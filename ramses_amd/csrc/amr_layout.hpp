@@ -6,7 +6,8 @@
 // that FORMULA -- every kernel of the path walks the tree through it -- but not the numbers: the resident copy of the cell
 // vectors is private to the device, so the octs get device indices of their own, chosen level by level such that
 //
-//   * a level stored in TILES (levels of 64^3 cells up to 4096^3): the periodic box of the level is cut into tiles of
+//   * a level stored in TILES (levels of 64^3 cells up to 4096^3; with a coarse grid of nx x ny x nz cells every level whose
+//     extents nx 2^(l-1) x ny 2^(l-1) x nz 2^(l-1) octs are multiples of 32, 4 and 4 and lie in 32 .. 2048): the periodic box of the level is cut into tiles of
 //     32 x 4 x 4 octs (64 x 8 x 8 cells); every tile that holds an oct of the level, or borders one (room for the ghost octs a
 //     sweep interpolates), owns 512 consecutive device indices, oct (lx, ly, lz) of the tile at lx + 32 (ly + 4 lz).  For one
 //     octant position the cells of a tile are then a dense 32 x 4 x 4 brick of doubles: a wavefront of the dense sweep
@@ -19,11 +20,20 @@
 // translated on the way out (iperm), level data moves through the lists anyway.  The tree arrays son / nbor / father are
 // rewritten into device numbers after every regrid.  A level whose set of octs did not change keeps its device indices and
 // therefore its data: only the levels refine_fine rebuilt (which the host re-sends anyway, a suffix of the levels) move.
-// RAMSES_AMD_DEVICE_ORDER=0 (or a coarse grid of more than one cell: physical boundaries) keeps the host's numbering.
+// RAMSES_AMD_DEVICE_ORDER=0 keeps the host's numbering.
+//
+// A coarse grid of several cells (ramses_amd_amrres_coarse_grid: nx = ny = nz = 3 between six walls, an elongated periodic box)
+// is numbered the same way: coarse cell (i, j, k) has the index 1 + i + nx j + nx ny k (amr/amr_commons.f90), its level-1 oct the
+// position (i, j, k), and the walk starts from every coarse cell that has an oct -- boundary cells and their octs included: they
+// are octs of the tree, read as neighbours, never listed.  A level's box has per-axis extents (LevelMap::nox, noy, noz) and wraps
+// by them; the tile lattice need be neither cubic nor a power of two.  The levels of such a grid are stored in tiles by the same
+// rule (RAMSES_AMD_COARSE_GRID_TILES=0: Z-order, the A/B switch of the measurement in DESIGN.md 3.7e).  A tree with a
+// level whose oct coordinates do not fit KEY_BITS keeps the host's numbering altogether (why_not says so).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <vector>
@@ -37,7 +47,11 @@ namespace amrlayout {
 typedef unsigned long long u64;
 constexpr int KEY_BITS = 19;                  // oct coordinates of levels <= 20
 constexpr u64 KEY_MASK = (1ull << KEY_BITS) - 1;
-constexpr int MAX_LEVEL = 20, TILE_MIN_LEVEL = 6, TILE_MAX_LEVEL = 12;   // tiles: 2^(L-1) octs per side in [32, 2048] (64^3 .. 4096^3 cells)
+constexpr int MAX_LEVEL = 20;
+// tiles: extents in octs multiples of (32, 4, 4), none above 2048, none below 32 (64^3 .. 4096^3 cells for one coarse cell; the
+// lower bound keeps the first level in tiles the one it is there -- level 5 of a (2, 1, 1) box, 32 x 16 x 16 octs, is a handful
+// of tiles that no sweep would take: the dense kernel pays off from 32768 octs on)
+constexpr int TILE_MIN_EXTENT = 32, TILE_MAX_EXTENT = 2048;
 __host__ __device__ inline u64 key_pack(unsigned x, unsigned y, unsigned z) { return (u64)x | ((u64)y << KEY_BITS) | ((u64)z << (2 * KEY_BITS)); }
 __host__ __device__ inline unsigned key_x(u64 k) { return (unsigned)(k & KEY_MASK); }
 __host__ __device__ inline unsigned key_y(u64 k) { return (unsigned)((k >> KEY_BITS) & KEY_MASK); }
@@ -91,14 +105,14 @@ __global__ void same_level_kernel(const int *__restrict__ hoct, const u64 *__res
 __device__ __forceinline__ int tile_of(unsigned x, unsigned y, unsigned z, int ntx, int nty) {
   return (int)(x / TILE_OX) + ntx * ((int)(y / TILE_OY) + nty * (int)(z / TILE_OZ));
 }
-// every tile that holds an oct, or one of an oct's 26 neighbours (periodic box of `no` octs per side)
-__global__ void tile_mark_kernel(const u64 *__restrict__ key, int n, int no, int ntx, int nty, int *__restrict__ need) {
+// every tile that holds an oct, or one of an oct's 26 neighbours (periodic box of nox x noy x noz octs)
+__global__ void tile_mark_kernel(const u64 *__restrict__ key, int n, int nox, int noy, int noz, int ntx, int nty, int *__restrict__ need) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long)n * 27) return;
   const int i = (int)(t / 27), o = (int)(t % 27);
   const u64 k = key[i];
-  const unsigned x = (key_x(k) + no + (o % 3) - 1) & (no - 1), y = (key_y(k) + no + ((o / 3) % 3) - 1) & (no - 1),
-                 z = (key_z(k) + no + (o / 9) - 1) & (no - 1);
+  const unsigned x = (key_x(k) + nox + (o % 3) - 1) % nox, y = (key_y(k) + noy + ((o / 3) % 3) - 1) % noy,
+                 z = (key_z(k) + noz + (o / 9) - 1) % noz;
   need[tile_of(x, y, z, ntx, nty)] = 1;
 }
 // dir[t] = 0-based cell index of the tile's first cell (octant position 1), -1: no tile; tileid[rank] = t
@@ -225,7 +239,9 @@ struct LevelMap {
   int version = 0;             // changes when the level is laid out again (what was derived from its device indices is stale)
   int layout = 0;              // 0: compact (Z-order), 1: tiles
   long base = 0, cap = 0;      // device indices [base, base + cap), 1-based
-  int no = 0, ntx = 0, nty = 0, ntz = 0, ntiles = 0;
+  int nox = 0, noy = 0, noz = 0;  // the level's periodic box in octs, per axis: (nx, ny, nz) of the coarse grid x 2^(level-1)
+  int ntx = 0, nty = 0, ntz = 0, ntiles = 0;
+  long box_octs() const { return (long)nox * noy * noz; }
   DevBuf hoct, key, doct;         // the level's octs: host index, position, device index (same order)
   DevBuf dir, tileid;             // tiles: directory [ntz][nty][ntx], rank -> tile
 };
@@ -235,6 +251,9 @@ inline int grid1(long n, int b = 256) { long g = (n + b - 1) / b; return (int)(g
 struct DevMap {
   bool on = false;             // false: the host's numbering on the device too (perm = identity, nothing is translated)
   long ngh = 0, ngd = 0, ncoarse = 0;
+  int cnx = 1, cny = 1, cnz = 1;  // the coarse grid (ncoarse = cnx cny cnz cells)
+  int lmax = MAX_LEVEL;        // the finest level whose oct coordinates fit KEY_BITS
+  bool nofit = false;          // the last build failed because the tree is deeper than lmax
   int serial = 0;              // bumped by every build(): whatever was derived from device indices is stale
   int nlev = 0;
   std::vector<LevelMap> lev;   // [0] unused, [l] level l
@@ -253,10 +272,15 @@ struct DevMap {
   static void drop(LevelMap &L) {
     for (DevBuf *b : {&L.hoct, &L.key, &L.doct, &L.dir, &L.tileid}) b->release();
   }
-  void reset(long ngh_, long ngd_, long ncoarse_, bool want) {
+  void reset(long ngh_, long ngd_, long ncoarse_, int nx, int ny, int nz, bool want) {
     for (size_t l = 1; l < lev.size(); l++) drop(lev[l]);
     ngh = ngh_; ngd = ngd_; ncoarse = ncoarse_; nlev = 0; lev.clear(); lev.resize(1);
-    on = want && ncoarse == 1;
+    cnx = nx; cny = ny; cnz = nz;
+    const long nmax = std::max(nx, std::max(ny, nz));
+    lmax = 0;
+    while (lmax < MAX_LEVEL && (nmax << lmax) <= (1l << KEY_BITS)) lmax++;      // extent of level l: nmax 2^(l-1) <= 2^KEY_BITS
+    nofit = false;
+    on = want && lmax >= 1;
     const char *e = getenv("RAMSES_AMD_DEVICE_ORDER");
     if (e && e[0] == '0') on = false;
     if (!on) ngd = ngh;
@@ -285,7 +309,7 @@ struct DevMap {
   // status bytes.  With `on` false the arrays are copied as they are.
   hipError_t build(const int *son, const int *nbor, const int *father, int *son_d, int *nbor_d, int *father_d, unsigned char *stat, hipStream_t s) {
     serial++;
-    overflow = false;
+    overflow = false; nofit = false;
     const size_t ncell_h = (size_t)(ncoarse + 8 * ngh), ncell_d = (size_t)(ncoarse + 8 * ngd);
     if (!on) {
       LCHK(hipMemcpyAsync(son_d, son, sizeof(int) * ncell_h, hipMemcpyHostToDevice, s));
@@ -313,20 +337,23 @@ struct DevMap {
     //         every level is taken over from the scratch lists and laid out again (the host re-sends those levels: a level can
     //         only change when refine_fine rebuilt it, and it rebuilds a suffix of the levels).  No allocation unless a list grows.
     if (lev.size() < (size_t)MAX_LEVEL + 2) lev.resize((size_t)MAX_LEVEL + 2);
-    const int g1 = son[0];
-    if (g1 <= 0) { why_not = "the coarse cell has no oct"; return hipErrorInvalidValue; }
+    // level 1: the oct of coarse cell (i, j, k) = 1 + i + nx j + nx ny k (amr/amr_commons.f90) sits at (i, j, k)
+    std::vector<int> g1;
+    std::vector<u64> k1;
+    for (long c = 0; c < ncoarse; c++)
+      if (son[c] > 0) { g1.push_back(son[c]); k1.push_back(key_pack((unsigned)(c % cnx), (unsigned)((c / cnx) % cny), (unsigned)(c / ((long)cnx * cny)))); }
+    if (g1.empty()) { why_not = "no coarse cell has an oct"; return hipErrorInvalidValue; }
     bool keeping = !fresh;
     int k0 = 0, nnew = 0;
     for (int l = 1; l <= MAX_LEVEL + 1; l++) {
       DevBuf &bo = c_hoct[l & 1], &bk = c_key[l & 1];
       int nc = 0;
       if (l == 1) {
-        const u64 kz = 0;
-        LCHK(bo.ensure(sizeof(int))); LCHK(bk.ensure(sizeof(u64)));
-        LCHK(hipMemcpyAsync(bo.p, &g1, sizeof(int), hipMemcpyHostToDevice, s));
-        LCHK(hipMemcpyAsync(bk.p, &kz, sizeof(u64), hipMemcpyHostToDevice, s));
+        nc = (int)g1.size();
+        LCHK(bo.ensure(sizeof(int) * (size_t)nc)); LCHK(bk.ensure(sizeof(u64) * (size_t)nc));
+        LCHK(hipMemcpyAsync(bo.p, g1.data(), sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, s));
+        LCHK(hipMemcpyAsync(bk.p, k1.data(), sizeof(u64) * (size_t)nc, hipMemcpyHostToDevice, s));
         LCHK(hipStreamSynchronize(s));
-        nc = 1;
       } else {
         LevelMap &P = lev[l - 1];
         const long capl = std::min<long>((long)P.n * 8, ngh);
@@ -340,6 +367,11 @@ struct DevMap {
       }
       if (nc == 0) break;
       if (l > MAX_LEVEL) { why_not = "more than 20 levels"; return hipErrorInvalidValue; }
+      if (l > lmax) {
+        why_not = "the oct coordinates of the finest levels do not fit the position keys (a coarse grid of several cells): the host's numbering is kept";
+        nofit = true;
+        return hipErrorInvalidValue;
+      }
       nnew = l;
       LevelMap &L = lev[l];
       if (keeping) {
@@ -356,7 +388,7 @@ struct DevMap {
         keeping = false;
       }
       if (k0 == 0) k0 = l;
-      L.level = l; L.n = nc; L.no = 1 << (l - 1);
+      L.level = l; L.n = nc; L.nox = cnx << (l - 1); L.noy = cny << (l - 1); L.noz = cnz << (l - 1);
       LCHK(L.hoct.ensure(sizeof(int) * (size_t)nc)); LCHK(L.key.ensure(sizeof(u64) * (size_t)nc)); LCHK(L.doct.ensure(sizeof(int) * (size_t)nc));
       LCHK(hipMemcpyAsync(L.hoct.p, bo.p, sizeof(int) * (size_t)nc, hipMemcpyDeviceToDevice, s));
       LCHK(hipMemcpyAsync(L.key.p, bk.p, sizeof(u64) * (size_t)nc, hipMemcpyDeviceToDevice, s));
@@ -372,17 +404,26 @@ struct DevMap {
     std::vector<long> after((size_t)nlev + 2, 0);            // octs of the finer levels (they need at least that much)
     for (int l = nlev; l >= 1; l--) after[l] = after[l + 1] + lev[l].n;
     const char *et = getenv("RAMSES_AMD_TILES");
-    const bool tiles_on = !(et && et[0] == '0');
+    bool tiles_on = !(et && et[0] == '0');
+    if (ncoarse > 1) {
+      // a coarse grid of several cells: tiles by default -- measured against the tree walker of the host's numbering on a walled
+      // 256^3 level (4.0 x quicker fast, 2.5 x strict) and a walled shell level (2.6 x, 1.75 x): profiles/r10_coarse_grid_probe.txt;
+      // RAMSES_AMD_COARSE_GRID_TILES=0 keeps such levels in Z-order (A/B)
+      const char *ec = getenv("RAMSES_AMD_COARSE_GRID_TILES");
+      if (ec && ec[0] == '0') tiles_on = false;
+    }
     for (int l = k0; l <= nlev; l++) {
       LevelMap &L = lev[l];
       L.layout = 0; L.base = next; L.cap = L.n; L.ntiles = 0;
       L.version = ++version_counter;
-      if (tiles_on && l >= TILE_MIN_LEVEL && l <= TILE_MAX_LEVEL) {
-        L.ntx = L.no / TILE_OX; L.nty = L.no / TILE_OY; L.ntz = L.no / TILE_OZ;
+      if (tiles_on && L.nox % TILE_OX == 0 && L.noy % TILE_OY == 0 && L.noz % TILE_OZ == 0 && L.nox <= TILE_MAX_EXTENT && L.noy <= TILE_MAX_EXTENT &&
+          L.noz <= TILE_MAX_EXTENT && std::min(L.nox, std::min(L.noy, L.noz)) >= TILE_MIN_EXTENT) {
+        L.ntx = L.nox / TILE_OX; L.nty = L.noy / TILE_OY; L.ntz = L.noz / TILE_OZ;
         const int nt = L.ntx * L.nty * L.ntz;
         LCHK(need.ensure(sizeof(int) * (size_t)nt)); LCHK(rank.ensure(sizeof(int) * (size_t)nt));
         LCHK(hipMemsetAsync(need.p, 0, sizeof(int) * (size_t)nt, s));
-        hipLaunchKernelGGL(tile_mark_kernel, dim3(grid1((long)L.n * 27)), dim3(256), 0, s, L.key.as<u64>(), L.n, L.no, L.ntx, L.nty, need.as<int>());
+        hipLaunchKernelGGL(tile_mark_kernel, dim3(grid1((long)L.n * 27)), dim3(256), 0, s, L.key.as<u64>(), L.n, L.nox, L.noy, L.noz, L.ntx, L.nty,
+                           need.as<int>());
         int ntiles = 0;
         LCHK(scan_need(nt, ntiles, s));
         const long capt = (long)ntiles * TILE_OCTS;

@@ -487,7 +487,7 @@ struct PlanArgs {
   // the level's tiles
   const int *dir, *tileid;
   long base;                   // first device index of the level (1-based)
-  int no, ntx, nty, ntz;
+  int ntx, nty, ntz;           // the level's periodic box in tiles, per axis (its extents in octs are whole tiles)
 };
 // coordinates of a device oct of a level in tiles
 __device__ __forceinline__ void plan_oct_pos(const PlanArgs &A, int d, int &x, int &y, int &z) {
@@ -531,8 +531,13 @@ __global__ __launch_bounds__(256) void plan_ghost_kernel(PlanArgs A, int *gfathe
     const int d = A.ig[i];
     int x, y, z;
     plan_oct_pos(A, d, x, y, z);
-    const int m = A.no - 1;
-    const int dn = plan_oct_at(A, (x + sx) & m, (y + sy) & m, (z + sz) & m);
+    // (the box wraps by its own extent on every axis: a coarse grid of several cells is neither a cube nor a power of two)
+    const int nox = A.ntx * TILE_OX, noy = A.nty * TILE_OY, noz = A.ntz * TILE_OZ;
+    int xn = x + sx, yn = y + sy, zn = z + sz;
+    xn = xn < 0 ? xn + nox : (xn >= nox ? xn - nox : xn);
+    yn = yn < 0 ? yn + noy : (yn >= noy ? yn - noy : yn);
+    zn = zn < 0 ? zn + noz : (zn >= noz ? zn - noz : zn);
+    const int dn = plan_oct_at(A, xn, yn, zn);
     if (dn == 0) { atomicAdd(err, 1); continue; }       // (the layout gave every neighbour position a tile)
     if (A.iperm[dn - 1] != 0) continue;                  // an oct of the tree: nothing to interpolate
     // its father cell: from the oct's own father cell, x, then y, then z steps through son(nbor(...)) (getnborfather)
@@ -1077,7 +1082,7 @@ PlanArgs plan_args(AmrRes &R, amrlayout::LevelMap &L, int ngrid) {
   A.son = R.son.as<int>(); A.nbor = R.nbor.as<int>(); A.father = R.father.as<int>(); A.iperm = R.map.iperm.as<int>();
   A.stat = R.stat.as<unsigned char>(); A.octpos = R.octpos.as<int>(); A.ig = R.cur_ig; A.n = ngrid;
   A.ncell = R.ncell; A.ncoarse = R.ncoarse; A.ngd = R.ngridmax;
-  A.dir = L.dir.as<int>(); A.tileid = L.tileid.as<int>(); A.base = L.base; A.no = L.no; A.ntx = L.ntx; A.nty = L.nty; A.ntz = L.ntz;
+  A.dir = L.dir.as<int>(); A.tileid = L.tileid.as<int>(); A.base = L.base; A.ntx = L.ntx; A.nty = L.nty; A.ntz = L.ntz;
   return A;
 }
 }  // namespace
@@ -1174,11 +1179,32 @@ int ramses_amd_amrres_tree(const int *son, const int *nbor, const int *father) {
   return 0;
 }
 
+// The coarse grid of the loads that follow: nx x ny x nz cells (amr/amr_parameters.f90 nx, ny, nz; 1, 1, 1 unless told), coarse
+// cell (i, j, k), 0-based, at index 1 + i + nx j + nx ny k (amr/amr_commons.f90: ncoarse = nx*ny*nz, the coarse cells first in
+// every cell vector; amr/init_amr.f90 numbers them ind = 1 + i + j*nx + k*nx*ny).  The device's own oct numbering needs the
+// position of every oct, which starts from here (csrc/amr_layout.hpp).
+static int g_coarse_grid[3] = {1, 1, 1};
+int ramses_amd_amrres_coarse_grid(int nx, int ny, int nz) {
+  if (nx < 1 || ny < 1 || nz < 1 || (int64_t)nx * ny * nz >= (1ll << 31))
+    return fail(RAMSES_AMD_EINVAL, "ramses_amd_amrres_coarse_grid: nx, ny, nz must be >= 1 (got %d, %d, %d)", nx, ny, nz);
+  g_coarse_grid[0] = nx; g_coarse_grid[1] = ny; g_coarse_grid[2] = nz;
+  return 0;
+}
+
+static int amrres_load_as(AmrRes &R, int nvar, int64_t ngridmax, long ngd, int64_t ncoarse, int cnx, int cny, int cnz, bool want, const double *uold,
+                          const int *son, const int *nbor, const int *father);
 // everything: the hydro state uold(1:ncell,1:nvar) and the tree
 int ramses_amd_amrres_load(int nvar, int64_t ngridmax, int64_t ncoarse, const double *uold, const int *son, const int *nbor,
                            const int *father) {
   if (!uold || !son || !nbor || !father) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   if (nvar < 5 || nvar > 7 || ngridmax < 1 || ncoarse < 1) return fail(RAMSES_AMD_EUNSUPPORTED, "AMR residency implements NVAR=5..7");
+  const int cnx = g_coarse_grid[0], cny = g_coarse_grid[1], cnz = g_coarse_grid[2];
+  // (a caller that never gave a grid and loads several coarse cells -- the entry as it was before ramses_amd_amrres_coarse_grid
+  //  existed -- has told nothing about where they lie: the host's numbering, as before)
+  const bool grid_unknown = cnx == 1 && cny == 1 && cnz == 1 && ncoarse > 1;
+  if (!grid_unknown && ncoarse != (int64_t)cnx * cny * cnz)
+    return fail(RAMSES_AMD_EINVAL, "ramses_amd_amrres_load: ncoarse = %lld is not nx*ny*nz of the coarse grid %d x %d x %d (ramses_amd_amrres_coarse_grid)",
+                (long long)ncoarse, cnx, cny, cnz);
   AmrRes &R = g_ar;
   { static bool registered = false; if (!registered) { registered = true; atexit(amrres_report); } }
   R.valid = false; R.grav = false; R.pfix = false;
@@ -1189,7 +1215,14 @@ int ramses_amd_amrres_load(int nvar, int64_t ngridmax, int64_t ncoarse, const do
   if (const char *e = getenv("RAMSES_AMD_DEVICE_OCTS")) { fac = atof(e); if (!(fac >= 1.0 && fac <= 16.0)) fac = 1.0; }
   long ngd = (long)((double)ngridmax * fac);
   if ((unsigned long)(ncoarse + 8 * ngd) >= (1ul << 31)) ngd = ngridmax;      // cell indices are 32-bit ints
-  R.map.reset(ngridmax, ngd, ncoarse, son[0] > 0);      // (no oct in the coarse cell: nothing to lay out -- the host's numbering)
+  bool any_oct = false;                                  // (no oct in any coarse cell: nothing to lay out -- the host's numbering)
+  for (int64_t c = 0; c < ncoarse && !any_oct; c++) any_oct = son[c] > 0;
+  return amrres_load_as(R, nvar, ngridmax, ngd, ncoarse, cnx, cny, cnz, any_oct && !grid_unknown, uold, son, nbor, father);
+}
+// (the rest of the load, for a device index space of ngd octs; want: the device's own numbering, if the tree allows it)
+static int amrres_load_as(AmrRes &R, int nvar, int64_t ngridmax, long ngd, int64_t ncoarse, int cnx, int cny, int cnz, bool want, const double *uold,
+                          const int *son, const int *nbor, const int *father) {
+  R.map.reset(ngridmax, ngd, ncoarse, cnx, cny, cnz, want);
   R.ngridmax = R.map.ngd; R.ncell = ncoarse + 8 * R.ngridmax;
   for (LevelPlan &P : R.plan) P.release();        // (flux records of a big level are gigabytes)
   R.plan.clear();
@@ -1205,7 +1238,16 @@ int ramses_amd_amrres_load(int nvar, int64_t ngridmax, int64_t ncoarse, const do
   HCHK(R.err.ensure(sizeof(int)), "hipMalloc"); HCHK(R.red.ensure(sizeof(double) * (4 + 3 * 2048)), "hipMalloc");
   HCHK(hipMemsetAsync(R.unew.p, 0, vb, nullptr), "memset unew");
   R.valid = true;
-  if (int rc = ramses_amd_amrres_tree(son, nbor, father)) { R.valid = false; return rc; }
+  if (int rc = ramses_amd_amrres_tree(son, nbor, father)) {
+    R.valid = false;
+    // a tree deeper than the position keys reach (amr_layout.hpp KEY_BITS, a coarse grid of several cells): the host's numbering
+    if (want && R.map.nofit) {
+      static bool told = false;
+      if (!told) { told = true; fprintf(stderr, "ramses_amd: %s\n", R.map.why_not); }
+      return amrres_load_as(R, nvar, ngridmax, (long)ngridmax, ncoarse, cnx, cny, cnz, false, uold, son, nbor, father);
+    }
+    return rc;
+  }
   if (!R.map.on) {
     HCHK(hipMemcpyAsync(R.uold.p, uold, vb, hipMemcpyHostToDevice, nullptr), "H2D uold");
   } else {
@@ -1499,7 +1541,7 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   hipLaunchKernelGGL(plan_clear_kernel, dim3(grid_for(L.cap * 8, GRID_CAP)), dim3(256), 0, s, A.stat, A.octpos, R.ncoarse, R.ngridmax, L.base, L.cap, P.gfather.as<int>());
   hipLaunchKernelGGL(plan_owned_kernel, lvl_grid(ngrid), dim3(256), 0, s, A);
   // (a level that holds every oct of the periodic box has no neighbour position without an oct)
-  if ((long)L.n < (long)L.no * L.no * L.no)
+  if ((long)L.n < L.box_octs())
     hipLaunchKernelGGL(plan_ghost_kernel, dim3(grid_for((long)ngrid * 26, GRID_CAP)), dim3(256), 0, s, A, P.gfather.as<int>(), P.gslot.as<int>(), P.gcell.as<int>(), cnt, gcap, cnt + 1);
   hipLaunchKernelGGL(plan_target_kernel, dim3(grid_for((long)ngrid * 6, GRID_CAP)), dim3(256), 0, s, A, P.corr_tgt.as<int>());
   HCHK(P.events.ensure(sizeof(int) * ((size_t)ngrid * 6 + 1)), "hipMalloc");
@@ -1507,7 +1549,8 @@ int build_plan(AmrRes &R, int ilevel, int ngrid, const int *h_igrid, int rows, L
   hipLaunchKernelGGL(plan_events_kernel, dim3((unsigned)(((long)ngrid * 6 + 255) / 256)), dim3(256), 0, s, A, P.corr_tgt.as<int>(), P.events.as<int>() + 1, P.events.as<int>(), P.evt_of.as<int>());
   // work items: columns of 60 x 8 cells, runs of 8-plane chunks up to 128 planes
   // (rows: interior rows of a work item -- 8, or 4 for the kernels of 8 rows; even: an oct never straddles two)
-  const int n = 2 * L.no, wtx = (n + 59) / 60, wty = n / rows, wz = n / 8;
+  // (the level's box in cells, per axis: whole tiles, so ny is a multiple of 8 and nz of 8 whatever the coarse grid)
+  const int wtx = (2 * L.nox + 59) / 60, wty = 2 * L.noy / rows, wz = 2 * L.noz / 8;
   const size_t nflag = (size_t)wtx * wty * wz;
   HCHK(P.flag.ensure(nflag), "hipMalloc");
   HCHK(hipMemsetAsync(P.flag.p, 0, nflag, s), "memset");
@@ -1640,7 +1683,9 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   done = false;
   if (!R.map.on || ilevel < 3 || ilevel > R.map.nlev || R.map.lev[ilevel].layout != 1) return 0;
   amrlayout::LevelMap &L = R.map.lev[ilevel];
-  const bool covered = (long)L.n == (long)L.no * L.no * L.no && ngrid == L.n;
+  // (covered: the list is every position of the level's box -- an elongated periodic box can be, a level between walls never is:
+  //  its boundary octs are not listed.  Either way the level goes through the same masked kernel and work list, per-axis extents)
+  const bool covered = (long)L.n == L.box_octs() && ngrid == L.n;
   if (!env_on(covered ? "RAMSES_AMD_COVERED_DENSE" : "RAMSES_AMD_TILE_DENSE") || !env_on("RAMSES_AMD_TILE_SWEEP")) return 0;
   {
     // a small level is quicker through the tree: the dense sweep is a pipeline of >= 19 plane iterations per workgroup whatever
@@ -1707,10 +1752,9 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
   // (the finest level of the tree: nothing has touched unew since set_unew copied uold into it -- the contract of this routine,
   //  hydro/godunov_fine.f90:5-35 after amr_step's set_unew -- so the kernel re-reads uold from L2 instead of streaming unew)
   A.base_uold = (ilevel >= R.map.nlev || R.map.lev[ilevel + 1].n == 0) ? 1 : 0;
-  const int n = 2 * L.no;
-  A.nx = A.ny = A.nz = n; A.ng = 0;
-  A.pitch_y = n; A.pitch_z = (long)n * n; A.pitch_var = R.ncell;
-  A.zchunk = n < 128 ? n : 128;
+  A.nx = 2 * L.nox; A.ny = 2 * L.noy; A.nz = 2 * L.noz; A.ng = 0;
+  A.pitch_y = A.nx; A.pitch_z = (long)A.nx * A.ny; A.pitch_var = R.ncell;
+  A.zchunk = A.nz < 128 ? A.nz : 128;
   A.region = SWEEP_ALL;
   A.dt = dt; A.dx = dx; A.rdx = 1.0 / dx;
   int ex = 0;
@@ -1727,7 +1771,7 @@ int tile_level_sweep(AmrRes &R, const ramses_amd_hydro_params *p, int ilevel, in
     S.uold = A.uold; S.grav = A.grav; S.stat = A.stat; S.dir = A.dir; S.tileid = L.tileid.as<int>();
     S.events = P.events.as<int>() + 1; S.ig = R.cur_ig; S.rec = P.corr.as<double>(); S.nevent = P.nevent;
     S.base = L.base; S.ncoarse = R.ncoarse; S.ngd = R.ngridmax; S.ncell = R.ncell;
-    S.no = L.no; S.ntx = L.ntx; S.nty = L.nty; S.ntz = L.ntz;
+    S.ntx = L.ntx; S.nty = L.nty; S.ntz = L.ntz;
     S.dt = A.dt; S.dx = A.dx; S.rdx = A.rdx; S.pow2 = A.pow2; S.P = A.P;
     { const char *e = getenv("RAMSES_AMD_EVENT_LANES"); S.qminor = e ? (e[0] == 'q' ? 1 : 0) : EVENT_QMINOR_DEFAULT; }
     // (the pass on a stream of its own beside the marching kernel was measured in round 6 -- 2.62 -> 2.54 ms strict, 2.09 -> 2.08 fast

@@ -1360,8 +1360,12 @@ __global__ __launch_bounds__(BX * 8) void godunov_scalar_kernel(SweepArgs A, int
 // ---------------------------------------------------------------------------
 // index (0-based) of cell (x, y, z) of the level in a cell vector; the layout gave every position this pass asks for a tile
 __device__ __forceinline__ long surf_cell(const SurfArgs &A, int x, int y, int z) {
-  const int m = 2 * A.no - 1;
-  x &= m; y &= m; z &= m;
+  // (the level's box is whole tiles, per axis: a coarse grid of several cells is not a cube; the pass asks for cells at most
+  //  two beyond a face of the box)
+  const int nx = 2 * TILE_OX * A.ntx, ny = 2 * TILE_OY * A.nty, nz = 2 * TILE_OZ * A.ntz;
+  x = x < 0 ? x + nx : (x >= nx ? x - nx : x);
+  y = y < 0 ? y + ny : (y >= ny ? y - ny : y);
+  z = z < 0 ? z + nz : (z >= nz ? z - nz : z);
   const int ox = x >> 1, oy = y >> 1, oz = z >> 1;
   const int t = (ox / TILE_OX) + A.ntx * ((oy / TILE_OY) + A.nty * (oz / TILE_OZ));
   const long c0 = A.dir[t];

@@ -82,7 +82,7 @@ struct SurfArgs {
   double *rec = nullptr;                             // [nevent][4][nvar + 2]
   int nevent = 0;
   long base = 0, ncoarse = 0, ngd = 0, ncell = 0;
-  int no = 0, ntx = 0, nty = 0, ntz = 0;
+  int ntx = 0, nty = 0, ntz = 0;                     // the level's box in tiles, per axis (its extents are whole tiles)
   double dt = 0, dx = 0, rdx = 0;
   int pow2 = 0;
   int qminor = 0;               // thread t -> (event, fine face): 0: (t % nevent, t / nevent), 1: (t / 4, t % 4)

@@ -133,6 +133,103 @@ def _morton_rank(no):
     return np.argsort(np.argsort(key.reshape(-1))).reshape(no, no, no)
 
 
+def _morton_rank_box(noz, noy, nox):
+    """rank of every oct position (oz,oy,ox) of an noz x noy x nox lattice along the Z-order curve"""
+    oz, oy, ox = np.meshgrid(np.arange(noz), np.arange(noy), np.arange(nox), indexing="ij")
+    key = np.zeros_like(ox, dtype=np.int64)
+    for b in range(max(1, int(max(nox, noy, noz) - 1).bit_length())):
+        key |= ((ox >> b) & 1) << (3 * b) | ((oy >> b) & 1) << (3 * b + 1) | ((oz >> b) & 1) << (3 * b + 2)
+    return np.argsort(np.argsort(key.reshape(-1))).reshape(noz, noy, nox)
+
+
+def coarse_grid_tree(grid, L, slack=7, order="scrambled", refine_mask=None):
+    """RAMSES tree arrays of a box whose coarse grid has grid = (nx, ny, nz) cells (amr/amr_parameters.f90; walls add one
+    coarse cell each, an elongated periodic box has nx = 2, ...): coarse cell (i, j, k) has the index 1 + i + nx*j + nx*ny*k
+    (amr/amr_commons.f90, amr/init_amr.f90), every coarse cell is a complete subtree down to level L, level L+1 holds an oct in
+    every level-L cell of refine_mask[z, y, x] (shape (nz*2^L, ny*2^L, nx*2^L)).  The box is periodic as a whole: nbor of a
+    level-1 oct is the neighbouring coarse cell, wrapped (what the reference stores with or without walls: a wall is a coarse
+    cell whose octs make_boundary_hydro fills, not an end of the tree).  order: as uniform_tree; grid = (1, 1, 1) gives
+    uniform_tree's arrays.  Beyond uniform_tree's keys: grid, cell_of(l, cx, cy, cz) -> 1-based cell index of a level-l cell
+    (l = 0 .. L+1; 0 where the level has no oct there), oct_ids[l] = 1-based oct at every position [oz, oy, ox] of level l's
+    lattice (l = 1 .. L), fine_pos = (cz, cy, cx) father cells of igrid_fine's octs in the order of fine_ids."""
+    cnx, cny, cnz = (int(v) for v in grid)
+    rng = np.random.default_rng(L)
+    ncoarse = cnx * cny * cnz
+    counts = [ncoarse * 8 ** (l - 1) for l in range(1, L + 1)]
+    nextra = int(np.count_nonzero(refine_mask)) if refine_mask is not None else 0
+    ngridmax = sum(counts) + nextra + slack
+    ncell = ncoarse + 8 * ngridmax
+    son = np.zeros(ncell, np.int32)
+    nbor = np.zeros((6, ngridmax), np.int32)
+    father = np.zeros(ngridmax, np.int32)
+    ids = {}
+    free = rng.permutation(ngridmax) + 1
+    used = 0
+    fine = {}
+
+    def cell_of(l, cx, cy, cz):
+        cx, cy, cz = np.asarray(cx), np.asarray(cy), np.asarray(cz)
+        if l == 0:
+            return (1 + cx + cnx * cy + cnx * cny * cz).astype(np.int64)
+        if l <= L:
+            g = ids[l][cz >> 1, cy >> 1, cx >> 1].astype(np.int64)
+        else:
+            g = fine["ids"][cz >> 1, cy >> 1, cx >> 1].astype(np.int64)
+        ind = (cx & 1) + 2 * (cy & 1) + 4 * (cz & 1)
+        return np.where(g > 0, ncoarse + ind * ngridmax + g, 0)
+
+    for l in range(1, L + 1):
+        nox, noy, noz = cnx << (l - 1), cny << (l - 1), cnz << (l - 1)
+        n_oct = nox * noy * noz
+        if order == "morton":
+            idl = (used + 1 + _morton_rank_box(noz, noy, nox)).astype(np.int32)
+        else:
+            idl = free[used:used + n_oct].reshape(noz, noy, nox).astype(np.int32)
+        used += n_oct
+        oz, oy, ox = np.meshgrid(np.arange(noz), np.arange(noy), np.arange(nox), indexing="ij")
+        ids[l] = idl
+        fcell = cell_of(l - 1, ox, oy, oz)
+        father[idl - 1] = fcell
+        son[fcell - 1] = idl
+        ext = (nox, noy, noz)
+        for d in range(6):
+            axis, up = d >> 1, d & 1
+            c = [ox.copy(), oy.copy(), oz.copy()]
+            c[axis] = (c[axis] + (1 if up else -1)) % ext[axis]
+            nbor[d, idl - 1] = cell_of(l - 1, c[0], c[1], c[2])
+    idL = ids[L]
+    igrid = np.sort(idL.reshape(-1)).astype(np.int32) if order == "morton" else rng.permutation(idL.reshape(-1)).astype(np.int32)
+    n = 2 ** L
+    out = dict(son=son, nbor=nbor, father=father, igrid=igrid, ncoarse=ncoarse, ngridmax=ngridmax, ncell=ncell, grid=(cnx, cny, cnz),
+               cell_of=cell_of, oct_ids=ids)
+    if refine_mask is not None:
+        ext = (cnx * n, cny * n, cnz * n)
+        assert refine_mask.shape == (ext[2], ext[1], ext[0])
+        cz, cy, cx = np.nonzero(refine_mask)
+        if order == "morton":
+            key = np.zeros(cx.size, dtype=np.int64)
+            for b in range(int(max(ext) - 1).bit_length()):
+                key |= ((cx >> b) & 1) << (3 * b) | ((cy >> b) & 1) << (3 * b + 1) | ((cz >> b) & 1) << (3 * b + 2)
+            o = np.argsort(key, kind="stable")
+            cz, cy, cx = cz[o], cy[o], cx[o]
+            idf = (used + 1 + np.arange(cx.size)).astype(np.int32)
+        else:
+            idf = free[used:used + cx.size].astype(np.int32)
+        fcell = cell_of(L, cx, cy, cz)
+        father[idf - 1] = fcell
+        son[fcell - 1] = idf
+        for d in range(6):
+            axis, up = d >> 1, d & 1
+            c = [cx.copy(), cy.copy(), cz.copy()]
+            c[axis] = (c[axis] + (1 if up else -1)) % ext[axis]
+            nbor[d, idf - 1] = cell_of(L, c[0], c[1], c[2])
+        fine["ids"] = np.zeros((ext[2], ext[1], ext[0]), np.int32)
+        fine["ids"][cz, cy, cx] = idf
+        out["fine_ids"], out["fine_pos"] = idf.copy(), (cz, cy, cx)
+        out["igrid_fine"] = idf.copy() if order == "morton" else rng.permutation(idf).astype(np.int32)
+    return out
+
+
 def uniform_tree(L, slack=7, order="scrambled", refine_box=None, refine_mask=None, refine_mask2=None, refine_mask3=None):
     """RAMSES tree arrays (amr/amr_commons.f90:67-75) of a periodic nx=ny=nz=1 box
     whose levels 1..L are fully refined; octs are numbered level by level in a

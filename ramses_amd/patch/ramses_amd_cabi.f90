@@ -735,6 +735,11 @@ module ramses_amd_cabi
        import :: c_int
        integer(c_int) :: rc
      end function ramses_amd_amrres_active
+     function ramses_amd_amrres_coarse_grid(nx, ny, nz) bind(C, name='ramses_amd_amrres_coarse_grid') result(rc)
+       import :: c_int
+       integer(c_int), value :: nx, ny, nz
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_coarse_grid
      function ramses_amd_amrres_load(nvar, ngridmax, ncoarse, uold, son, nbor, father) &
           & bind(C, name='ramses_amd_amrres_load') result(rc)
        import :: c_int, c_int64_t, c_double

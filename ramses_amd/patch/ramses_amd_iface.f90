@@ -849,6 +849,9 @@ contains
     integer :: rc, l, nl
     integer, allocatable :: list(:)
     if (ramses_amd_amrres_active() == 0) then
+       ! the coarse grid (one more cell per wall with &BOUNDARY_PARAMS): the device numbers its octs by position
+       rc = ramses_amd_amrres_coarse_grid(nx, ny, nz)
+       if (rc /= 0) call ramses_amd_fatal('AMR residency (coarse grid)')
        rc = ramses_amd_amrres_load(nvar, int(ngridmax, 8), int(ncoarse, 8), uold, son, nbor, father)
        if (rc /= 0) call ramses_amd_fatal('AMR residency (load)')
        ! whatever is cached per tree epoch on the device (rho_fine's oct centres) went with the old image
