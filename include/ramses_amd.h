@@ -1018,6 +1018,41 @@ int ramses_amd_amrres_tiled_levels(void);
  * region and passes the states, [nvar][8][ngrid[r]] per imposed region in order (host array; NULL when there is none). */
 int ramses_amd_amrres_boundary_hydro(int nregion, const int *btype, const int *ngrid, const int *igrid, int no_inflow, double smallr,
                                      int nvector, const double *imposed);
+/* Analytic gravity (gravity_type 1: constant vector, 2: point mass; poisson/gravana.f90:27-62) on the device: the acceleration
+ * is a function of the cell centre alone, so force_fine of such a run writes the resident f from the resident oct centres.
+ * Strict IEEE arithmetic in the reference's operation order: the reference's bits.
+ *   ramses_amd_gravana_set: gravity_type, gravity_params(1:10), skip = (icoarse_min, jcoarse_min, kcoarse_min), scale = boxlen /
+ *       nx_loc (poisson/force_fine.f90:37-43).  Any other gravity_type: RAMSES_AMD_EUNSUPPORTED (gravity_type 3 calls the pow of
+ *       the reference's runtime library; its bits do not follow from the source).
+ *   ramses_amd_gravana_eval: f[3][n] = gravana(x[3][n]) on the device, host arrays, positions in user units as gravana takes them
+ *       (the Fortran shim's self-check against the gravana linked into the program; tests).
+ *   ramses_amd_amrres_force_ana: force_fine(ilevel)'s analytic branch (:58-109) on the resident AMR state: f of the ngrid listed
+ *       octs, the rank's own octs followed by its virtual octs of the level (as many as ramses_amd_amrres_comm_set registered;
+ *       the value is the same on both, so no exchange of f follows), from the oct centres of ramses_amd_amrres_xg; dx = 0.5**ilevel.
+ *       diag2 over the OWN octs (:158-190): [0] fact * sum of f**2 over their leaf cells (a fixed tree: differs from the
+ *       reference's serial sum by rounding only; it feeds the energy print), [1] max |rho| where rho_fine's deposit is kept on
+ *       the device (ramses_amd_amrres_rho_keep), -1 where it is not (the caller computes it from its host vector, :175-177).
+ *   ramses_amd_amrres_boundary_force: make_boundary_force(ilevel) (poisson/boundary_potential.f90:5-174) on the resident f, with
+ *       the region arguments and the in-place, chunked semantics of ramses_amd_amrres_boundary_hydro: reflexive regions (1-6) copy
+ *       their reference cell and flip the component normal to the wall, free regions (11-16) copy, imposed regions (21-26) take
+ *       gravana at the boundary cell's own centre.
+ *   ramses_amd_resident_force_ana_f90: the same branch of force_fine on the one-level resident brick (ramses_amd_resident_*), diag2
+ *       = {fact * sum f**2, max |rho|} over the level as ramses_amd_resident_force_fine_f90 returns them.
+ * All of them return RAMSES_AMD_EINVAL without their state (no resident state, no oct centres, no ramses_amd_gravana_set). */
+int ramses_amd_gravana_set(int type, const double *params10, const double *skip3, double scale);
+int ramses_amd_gravana_eval(int64_t n, const double *x, double *f);
+int ramses_amd_amrres_force_ana(int ilevel, int ngrid, const int *igrid, double dx, double fact, double *diag2);
+int ramses_amd_amrres_boundary_force(int nregion, const int *btype, const int *ngrid, const int *igrid, int nvector, double dx);
+int ramses_amd_resident_force_ana_f90(int ilevel, double fact, double *diag2);
+/* The resident acceleration across a regrid, device to device (the host's oct numbers survive refine_fine, the device's do not).
+ *   ramses_amd_amrres_stash_f: before the tree changes, the listed octs of a level (host numbers: own, virtual, boundary octs)
+ *       park their f on the device in the host's numbering.
+ *   ramses_amd_amrres_restore_f: after ramses_amd_amrres_tree, level by level from the coarsest rebuilt one: oct i of the list
+ *       takes its father cell's f where inherit[i] != 0 (make_grid_fine gave a new oct that value, amr/refine_utils.f90:918-927),
+ *       else what it parked.  Only the list and the flags cross PCIe.
+ * RAMSES_AMD_EINVAL without a resident state or acceleration. */
+int ramses_amd_amrres_stash_f(int ngrid, const int *igrid);
+int ramses_amd_amrres_restore_f(int ngrid, const int *igrid, const int *inherit);
 /* Several MPI ranks (one per GPU): the virtual-boundary exchanges of amr_step on the resident cell vectors.
  *   make_virtual_fine_dp(uold(1,ivar),ilevel)     amr/virtual_boundaries.f90:373-528, callers amr/amr_step.f90:61,287,505
  *   make_virtual_reverse_dp(unew(1,ivar),ilevel)  amr/virtual_boundaries.f90:693-983, caller amr/amr_step.f90:397

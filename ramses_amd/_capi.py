@@ -256,6 +256,14 @@ SYMBOLS = [
     ("ramses_amd_amrres_relayouts", _i64, []),
     ("ramses_amd_amrres_tiled_levels", _i, []),
     ("ramses_amd_amrres_boundary_hydro", _i, [_i, _vp, _vp, _vp, _i, _d, _i, _vp]),
+    # analytic gravity (gravity_type 1, 2) on the device
+    ("ramses_amd_gravana_set", _i, [_i, _vp, _vp, _d]),
+    ("ramses_amd_gravana_eval", _i, [_i64, _vp, _vp]),
+    ("ramses_amd_amrres_force_ana", _i, [_i, _i, _vp, _d, _d, _vp]),
+    ("ramses_amd_amrres_boundary_force", _i, [_i, _vp, _vp, _vp, _i, _d]),
+    ("ramses_amd_resident_force_ana_f90", _i, [_i, _d, _vp]),
+    ("ramses_amd_amrres_stash_f", _i, [_i, _vp]),
+    ("ramses_amd_amrres_restore_f", _i, [_i, _vp, _vp]),
     ("ramses_amd_mhd_workspace_bytes", _i64, [_i, _i, _i]),
     ("ramses_amd_mhd_godunov_brick", _i, [_vp, _i, _i, _i, _vp, _vp, _d, _d, _vp, _i64, _vp]),
     ("ramses_amd_mhd_godunov_brick_fast", _i, [_vp, _i, _i, _i, _vp, _vp, _d, _d, _vp, _i64, _vp]),

@@ -35,6 +35,8 @@
 #include "amr_sweep_args.hpp"
 #include "amr_tree.hpp"
 #include "hydro_core.hpp"
+#include "gravana_core.hpp"
+#include "misc_args.hpp"
 #include "rho_args.hpp"
 #include "sweep_args.hpp"
 #include "capi_shared.hpp"
@@ -373,6 +375,77 @@ __global__ __launch_bounds__(256) void lvl_gravity_source_kernel(LvlArgs A, cons
     A.unew[c + 3 * N] = d * w;
     e_kin = 0.5 * d * (u * u + v * v + w * w);
     A.unew[c + 4 * N] = e_prim + e_kin;
+  }
+}
+
+// force_fine's analytic branch (poisson/force_fine.f90:58-103, gravity_type 1 | 2): f(cells of the listed octs, 1:3) = gravana at
+// the cell centre, from the oct centres xg(1:ngridmax,1:3) in the device's numbering.  One lane per cell, nothing else is written.
+__global__ __launch_bounds__(256) void lvl_gravana_kernel(LvlList L, const double *__restrict__ xg, double *__restrict__ f, GravAna G, double dx) {
+  const long total = (long)L.ngrid * 8;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    int ind, g;
+    const long c = lvl_cell(L, t, ind, g);
+    const double og[3] = {xg[g - 1], xg[L.ngridmax + g - 1], xg[2 * L.ngridmax + g - 1]};
+    double x[3], ff[3];
+    gravana_centre(G, og, ind, dx, x);
+    gravana_cell(G, x, ff);
+#pragma unroll
+    for (int d = 0; d < 3; d++) f[c + (long)d * L.ncell] = ff[d];
+  }
+}
+// leaf[t] = 1 where cell t of the list has no son: force_fine's potential-energy sum runs over the leaf cells (:169-171)
+__global__ __launch_bounds__(256) void lvl_leaf_kernel(LvlList L, const int *__restrict__ son, int *__restrict__ leaf) {
+  const long total = (long)L.ngrid * 8;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) leaf[t] = son[lvl_cell(L, t)] == 0;
+}
+// gravana on positions the caller gives: x[3][n] -> f[3][n] (ramses_amd_gravana_eval: the shim's self-check, the tests)
+__global__ __launch_bounds__(256) void gravana_eval_kernel(GravAna G, long n, const double *__restrict__ x, double *__restrict__ f) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const double xx[3] = {x[i], x[n + i], x[2 * n + i]};
+    double ff[3];
+    gravana_cell(G, xx, ff);
+    f[i] = ff[0]; f[n + i] = ff[1]; f[2 * n + i] = ff[2];
+  }
+}
+
+// The acceleration of a level across a regrid without a trip to the host.  The host's oct numbers survive refine_fine, the
+// device's do not: before the tree changes f of the listed octs is parked in the HOST's numbering (stage[3][ncell_h], device
+// memory; hraw = the list as the host wrote it, L.igrid = the same octs in device numbers) ...
+__global__ __launch_bounds__(256) void lvl_f_stash_kernel(LvlList L, const int *__restrict__ hraw, long ncell_h, long ngh, const double *__restrict__ f,
+                                                           double *__restrict__ stage) {
+  const long total = (long)L.ngrid * 8;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    int ind, g;
+    const long c = lvl_cell(L, t, ind, g);
+    const int gh = hraw[(int)(t % L.ngrid)];
+    if (gh < 1 || gh > ngh) continue;          // (not an oct of the host's: check_lists reports it)
+    const long ch = L.ncoarse + (long)ind * ngh + gh - 1;
+#pragma unroll
+    for (int k = 0; k < 3; k++) stage[(long)k * ncell_h + ch] = f[(long)k * L.ncell + c];
+  }
+}
+// ... and afterwards every oct of a rebuilt level takes it back from there into its new device cells -- or, where the caller says
+// so (inherit[i] != 0: make_grid_fine gave the oct its father cell's f, amr/refine_utils.f90:918-927), the father cell's f.  The
+// caller goes from the coarsest rebuilt level to the finest, so the father's level is complete.
+__global__ __launch_bounds__(256) void lvl_f_restore_kernel(LvlList L, const int *__restrict__ hraw, const int *__restrict__ inherit,
+                                                             const int *__restrict__ father, long ncell_h, long ngh, double *__restrict__ f,
+                                                             const double *__restrict__ stage) {
+  const long total = (long)L.ngrid * 8;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    int ind, g;
+    const long c = lvl_cell(L, t, ind, g);
+    const int i = (int)(t % L.ngrid);
+    if (inherit[i]) {
+      const long cf = (long)father[g - 1] - 1;
+      if (cf < 0 || cf >= L.ncell) continue;   // (an oct that is not in the tree)
+#pragma unroll
+      for (int k = 0; k < 3; k++) f[(long)k * L.ncell + c] = f[(long)k * L.ncell + cf];
+    } else {
+      if (hraw[i] < 1 || hraw[i] > ngh) continue;
+      const long ch = L.ncoarse + (long)ind * ngh + hraw[i] - 1;
+#pragma unroll
+      for (int k = 0; k < 3; k++) f[(long)k * L.ncell + c] = stage[(long)k * ncell_h + ch];
+    }
   }
 }
 
@@ -806,6 +879,50 @@ __global__ __launch_bounds__(256) void bnd_store_kernel(BndArgs A) {
   }
 }
 
+// make_boundary_force (poisson/boundary_potential.f90:5-174) on the resident acceleration: the sibling of bnd_compute_kernel for
+// the three components of f (BndArgs with uold = f, nvar = 3; bnd_mark_kernel and bnd_store_kernel serve both).  Same loop, same
+// chunks of NVECTOR octs written in place, hence the same chain of reference cells.  Per link (:118-133): reflexive regions flip the
+// component normal to the wall (gs), free regions copy.  Imposed regions (:135-159) take gravana at the boundary cell's own centre.
+__global__ __launch_bounds__(256) void bndf_compute_kernel(BndArgs A, GravAna G, const double *__restrict__ xg, double dx) {
+  const int dir = A.type % 10, kind = A.type / 10;          // boundary_dir 1..6; 0 reflexive, 1 free, 2 imposed
+  const int axis = (dir - 1) >> 1, high = (dir - 1) & 1;
+  const int inbor = high ? 2 * axis + 1 : 2 * axis + 2;     // :55-61: towards the box
+  const int bit = 1 << axis;
+  const long total = (long)A.n * 8;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const int ind = (int)(t / A.n), i = (int)(t % A.n);
+    int oct = A.list[i];
+    double ff[3];
+    if (kind == 2) {
+      const double og[3] = {xg[oct - 1], xg[A.ngridmax + oct - 1], xg[2 * A.ngridmax + oct - 1]};
+      double x[3];
+      gravana_centre(G, og, ind, dx, x);
+      gravana_cell(G, x, ff);
+    } else {
+      int cind = ind, napply = 0, ref = 0, rind = 0;
+      for (;;) {
+        const int fc = A.nbor[(long)(inbor - 1) * A.ngridmax + oct - 1];
+        ref = fc > 0 ? A.son[fc - 1] : 0;
+        rind = kind == 0 ? (cind ^ bit) : (high ? (cind | bit) : (cind & ~bit));      // ind_ref (:65-77)
+        napply++;
+        if (ref > 0 && napply < 64) {
+          const int pr = A.pos[ref - 1];
+          if (pr != 0) {
+            const int chunk_ref = (pr - 1) / A.nvector, chunk_oct = (A.pos[oct - 1] - 1) / A.nvector;
+            if (chunk_ref < chunk_oct || (chunk_ref == chunk_oct && rind < cind)) { oct = ref; cind = rind; continue; }
+          }
+        }
+        break;
+      }
+      const long cref = A.ncoarse + (long)rind * A.ngridmax + ref;          // 1-based, as the reference computes it
+      for (int v = 0; v < 3; v++) ff[v] = A.uold[(long)v * A.ncell + cref - 1];
+      if (kind == 0)
+        for (int a = 0; a < napply; a++) ff[axis] = ff[axis] * -1.0;
+    }
+    for (int v = 0; v < 3; v++) A.tmp[(long)v * total + t] = ff[v];
+  }
+}
+
 using Buf = DevBuf;
 
 // MPI: the communicators of one level as build_comm left them (amr/amr_commons.f90:170-179, emission(icpu,l)%igrid and
@@ -876,6 +993,12 @@ struct AmrRes {
   std::vector<LevelPlan> plan;
   long tile_sweeps = 0, tree_sweeps = 0;
   int64_t f_up_bytes = 0, f_down_bytes = 0;    // bytes of the acceleration that crossed PCIe (ramses_amd_amrres_f_traffic)
+  long ana_calls = 0;                          // force_fine calls that wrote f on the device (analytic gravity: ramses_amd_amrres_force_ana)
+  // f that went up as part of a load of the WHOLE device image (ramses_amd_amrres_load: the first one, and one after every defrag /
+  // load_balance, which renumber the host's octs and drop the image): from the load until the first level routine
+  int64_t f_up_image = 0;
+  long image_loads = 0;
+  bool image_window = false;
   int64_t rho_down_bytes = 0;                  // bytes of the density deposit that went back to the host vector
   bool rho_keep = false;                       // ramses_amd_amrres_rho_keep: rho_fine's deposit stays on the device
   long relayouts = 0;                          // regrids that had to lay the kept levels out again (tiles in the way of the finer levels)
@@ -892,6 +1015,8 @@ struct AmrRes {
   Buf f;                 // f(1:ncell,1:3), a copy of the host array refreshed after force_fine and after regrids
   bool grav = false;
   Buf bnd_list, bnd_pos, bnd_tmp;   // make_boundary_hydro: the regions' oct lists, oct -> position in its region, the new states
+  Buf fstage, fraw, fflag;          // f across a regrid: parked in the host's numbering, the raw list, the inherit flags
+  Buf leaf, diag;                   // force_fine's diagnostics of an analytic acceleration: leaf flags of the list, launch_force_diag's scratch
   bool bnd_pos_clean = false;
   Buf divu, enew;        // pressure_fix: the reference's divu / enew work vectors (device only: scratch of one step)
   bool pfix = false;
@@ -1111,7 +1236,10 @@ extern "C" int ramses_amd_mgdist_traffic(int64_t *out2);
 static void amrres_report(void) {
   const char *e = getenv("RAMSES_AMD_STATS");
   if (!e || e[0] == '0') return;
-  if (g_ar.f_up_bytes + g_ar.f_down_bytes > 0)
+  if (g_ar.ana_calls > 0)
+    fprintf(stdout, " ramses_amd: analytic gravity: %ld calls of force_fine wrote the resident acceleration on the device; f to the device: %lld bytes in %ld loads of the whole device image, %lld bytes otherwise\n",
+            g_ar.ana_calls, (long long)g_ar.f_up_image, g_ar.image_loads, (long long)(g_ar.f_up_bytes - g_ar.f_up_image));
+  if (g_ar.f_up_bytes + g_ar.f_down_bytes > 0 || g_ar.ana_calls > 0)
     fprintf(stdout, " ramses_amd: acceleration f over PCIe: %lld bytes to the device, %lld bytes back\n", (long long)g_ar.f_up_bytes, (long long)g_ar.f_down_bytes);
   {
     int64_t t[2] = {0, 0};
@@ -1133,6 +1261,7 @@ int ramses_amd_amrres_tree(const int *son, const int *nbor, const int *father) {
   AmrRes &R = g_ar;
   if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state");
   if (!son || !nbor || !father) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  R.image_window = false;      // (a regrid: what goes up from here on is no part of a load of the whole image)
   hipError_t e = R.map.build(son, nbor, father, R.son.as<int>(), R.nbor.as<int>(), R.father.as<int>(), R.stat.as<unsigned char>(), nullptr);
   if (e == hipErrorInvalidValue && R.map.on && R.map.overflow) {
     // A legitimate regrid: the finer levels grew, and the free tile slots of the levels that kept their layout are in the way
@@ -1217,7 +1346,9 @@ int ramses_amd_amrres_load(int nvar, int64_t ngridmax, int64_t ncoarse, const do
   if ((unsigned long)(ncoarse + 8 * ngd) >= (1ul << 31)) ngd = ngridmax;      // cell indices are 32-bit ints
   bool any_oct = false;                                  // (no oct in any coarse cell: nothing to lay out -- the host's numbering)
   for (int64_t c = 0; c < ncoarse && !any_oct; c++) any_oct = son[c] > 0;
-  return amrres_load_as(R, nvar, ngridmax, ngd, ncoarse, cnx, cny, cnz, any_oct && !grid_unknown, uold, son, nbor, father);
+  const int rc = amrres_load_as(R, nvar, ngridmax, ngd, ncoarse, cnx, cny, cnz, any_oct && !grid_unknown, uold, son, nbor, father);
+  if (rc == 0) { R.image_window = true; R.image_loads++; }
+  return rc;
 }
 // (the rest of the load, for a device index space of ngd octs; want: the device's own numbering, if the tree allows it)
 static int amrres_load_as(AmrRes &R, int nvar, int64_t ngridmax, long ngd, int64_t ncoarse, int cnx, int cny, int cnz, bool want, const double *uold,
@@ -1322,6 +1453,7 @@ static int level_entry(const ramses_amd_hydro_params *p, const char *who, int ng
                        const char *what = nullptr) {
   if (int rc = refuse_amr(p, who)) return rc;
   if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  g_ar.image_window = false;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   if (need == NEED_GRAV && !g_ar.grav) return fail(RAMSES_AMD_EINVAL, "%s: no acceleration on the device (ramses_amd_amrres_load_f)", what);
   if (need == NEED_PFIX && !g_ar.pfix) return fail(RAMSES_AMD_EINVAL, "%s: pressure_fix not enabled (ramses_amd_amrres_enable_pfix)", what);
@@ -1370,6 +1502,7 @@ int ramses_amd_amrres_courant(const ramses_amd_hydro_params *p, int ngrid, const
   if (int rc_ = refuse_amr(p, "ramses_amd_amrres_courant")) return rc_;
   if (!p || !out4) return fail(RAMSES_AMD_EINVAL, "NULL argument");
   LvlArgs A;
+  g_ar.image_window = false;
   if (int rc = set_level(g_ar, ngrid, igrid, A)) return rc;
   AmrRes &R = g_ar;
   // (dt is a minimum; the diagnostic sums are added per workgroup in workgroup order either way, not in the reference's)
@@ -1859,6 +1992,7 @@ int ramses_amd_amrres_load_f(int ngrid, const int *igrid, const double *f) {
   if (ngrid == 0) return 0;
   if (int rc = level_from_host(R, R.f.as<double>(), 3, R.cur_ig, ngrid, igrid, f, "f")) return rc;
   R.f_up_bytes += (int64_t)sizeof(double) * 3 * 8 * ngrid;
+  if (R.image_window) R.f_up_image += (int64_t)sizeof(double) * 3 * 8 * ngrid;
   return 0;
 }
 int ramses_amd_amrres_has_gravity(void) { return g_ar.valid && g_ar.grav ? 1 : 0; }
@@ -1938,6 +2072,193 @@ int ramses_amd_amrres_xg(const double *xg) {
     HCHK(hipStreamSynchronize(nullptr), "sync");
   }
   R.xg_valid = true;
+  return 0;
+}
+
+// ---- analytic gravity (gravity_type 1 | 2; poisson/gravana.f90:27-62): the acceleration is a function of the cell centre alone, so
+// force_fine of such a run writes the resident f from the resident oct centres and sends nothing (f goes up only with a load of
+// the whole device image: the first, and one after every defrag / load_balance; across a regrid see ramses_amd_amrres_stash_f)
+
+namespace {
+GravAna g_gravana;
+bool g_gravana_set = false;
+}  // namespace
+extern "C++" {
+namespace ramses_amd {
+const GravAna *capi_gravana() { return g_gravana_set ? &g_gravana : nullptr; }      // (capi_host.hip: the one-level resident brick)
+}  // namespace ramses_amd
+}
+
+// gravity_type, gravity_params(1:10), skip = (icoarse_min, jcoarse_min, kcoarse_min), scale = boxlen / nx_loc
+int ramses_amd_gravana_set(int type, const double *params10, const double *skip3, double scale) {
+  if (type != 1 && type != 2)
+    return fail(RAMSES_AMD_EUNSUPPORTED, "ramses_amd_gravana_set: gravity_type=%d: the device evaluates gravity_type 1 (constant vector) and 2 "
+                "(point mass) only (gravity_type 3 calls the pow of the reference's runtime library)", type);
+  if (!params10 || !skip3) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (!(scale > 0.0)) return fail(RAMSES_AMD_EINVAL, "ramses_amd_gravana_set: scale must be > 0");
+  g_gravana.type = type;
+  for (int k = 0; k < 10; k++) g_gravana.p[k] = params10[k];
+  for (int k = 0; k < 3; k++) g_gravana.skip[k] = skip3[k];
+  g_gravana.scale = scale;
+  g_gravana_set = true;
+  return 0;
+}
+
+// f[3][n] = gravana(x[3][n]) on the device (host arrays; positions in user units, as gravana takes them)
+int ramses_amd_gravana_eval(int64_t n, const double *x, double *f) {
+  if (!g_gravana_set) return fail(RAMSES_AMD_EINVAL, "ramses_amd_gravana_eval: no analytic gravity set (ramses_amd_gravana_set)");
+  if (n < 0 || (n > 0 && (!x || !f))) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (n == 0) return 0;
+  static Buf dx_, df_;
+  const size_t bytes = sizeof(double) * 3 * (size_t)n;
+  HCHK(dx_.ensure(bytes), "hipMalloc"); HCHK(df_.ensure(bytes), "hipMalloc");
+  HCHK(hipMemcpyAsync(dx_.p, x, bytes, hipMemcpyHostToDevice, nullptr), "H2D positions");
+  hipLaunchKernelGGL(gravana_eval_kernel, dim3(grid_for((long)n, GRID_CAP)), dim3(256), 0, nullptr, g_gravana, (long)n, dx_.as<double>(), df_.as<double>());
+  HCHK(hipGetLastError(), "gravana launch");
+  HCHK(hipMemcpy(f, df_.p, bytes, hipMemcpyDeviceToHost), "D2H acceleration");
+  return 0;
+}
+
+// force_fine(ilevel) of a run with analytic gravity on the resident acceleration: f of the ngrid listed octs = gravana at their
+// cell centres.  The list holds the rank's own octs followed by its virtual octs of the level (the value is the same on both, so
+// the reference's make_virtual_fine_dp(f) would copy equal bits: no exchange); how many of them are virtual is what
+// ramses_amd_amrres_comm_set registered for the level (none on one rank).  diag2 (poisson/force_fine.f90:158-190) over the OWN octs:
+// [0] fact * sum f**2 over their leaf cells (launch_force_diag: differs from the reference's serial loop by rounding only),
+// [1] max |rho| where rho_fine's deposit is kept on the device (ramses_amd_amrres_rho_keep), -1 where it is not (the caller's host
+// loop then computes it, :175-177).
+int ramses_amd_amrres_force_ana(int ilevel, int ngrid, const int *igrid, double dx, double fact, double *diag2) {
+  AmrRes &R = g_ar;
+  LvlArgs A;
+  if (!diag2) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  // (the deposit counts as resident where ramses_amd_amrres_rho_keep holds it on the device for the solver and force_fine)
+  const bool rho_dev = R.valid && R.rho_keep && R.rho.p && R.rho.cap >= sizeof(double) * (size_t)R.ncell;
+  diag2[0] = 0.0; diag2[1] = rho_dev ? 0.0 : -1.0;
+  if (!g_gravana_set) return fail(RAMSES_AMD_EINVAL, "force_fine: no analytic gravity set (ramses_amd_gravana_set)");
+  R.image_window = false;
+  if (int rc = set_level(R, ngrid, igrid, A)) return rc;
+  if (!R.xg_valid) return fail(RAMSES_AMD_EINVAL, "force_fine: no oct centres on the device (ramses_amd_amrres_xg)");
+  if (int rc = ensure_f(R)) return rc;
+  if (ngrid == 0) return 0;
+  R.ana_calls++;      // (calls that launch the kernel)
+  int nvirt = 0;
+  if (ilevel >= 1 && (size_t)ilevel < R.comm.size() && R.comm[ilevel].epoch >= 0) nvirt = R.comm[ilevel].rc_first[R.comm[ilevel].ncpu];
+  if (nvirt > ngrid) return fail(RAMSES_AMD_EINVAL, "force_fine: the list of level %d is shorter (%d) than its virtual octs (%d)", ilevel, ngrid, nvirt);
+  const int nown = ngrid - nvirt;
+  hipLaunchKernelGGL(lvl_gravana_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, lvl_list(R, R.cur_ig, ngrid, 3), R.xg.as<double>(), R.f.as<double>(), g_gravana, dx);
+  HCHK(hipGetLastError(), "gravana launch");
+  if (nown > 0) {
+    const long N = (long)nown * 8;
+    HCHK(R.pack.ensure(sizeof(double) * 3 * (size_t)N), "hipMalloc"); HCHK(R.leaf.ensure(sizeof(int) * (size_t)N), "hipMalloc");
+    HCHK(R.diag.ensure(sizeof(double) * (FORCE_DIAG_SCRATCH + 2)), "hipMalloc");
+    const LvlList own = lvl_list(R, R.cur_ig, nown, 3);
+    hipLaunchKernelGGL(lvl_pack_comp_kernel<true>, lvl_grid(nown), dim3(256), 0, nullptr, own, R.f.as<double>(), R.pack.as<double>());
+    hipLaunchKernelGGL(lvl_leaf_kernel, lvl_grid(nown), dim3(256), 0, nullptr, own, R.son.as<int>(), R.leaf.as<int>());
+    HCHK(hipGetLastError(), "force diagnostics launch");
+    // (the maximum of launch_force_diag is taken over the packed f itself and dropped: rho has its own entry below)
+    double *scratch = R.diag.as<double>();
+    HCHK(launch_force_diag(R.pack.as<double>(), R.pack.as<double>(), R.leaf.as<int>(), N, fact, scratch, scratch + FORCE_DIAG_SCRATCH, nullptr), "force diagnostics launch");
+    double out[2];
+    HCHK(hipMemcpy(out, scratch + FORCE_DIAG_SCRATCH, sizeof(out), hipMemcpyDeviceToHost), "D2H diag");
+    diag2[0] = out[0];
+    if (rho_dev)
+      if (int rc = ramses_amd_amrres_rho_absmax(nown, igrid, &diag2[1])) return rc;
+  }
+  return 0;
+}
+
+// f of a level across a regrid, device to device (the kernels above).  _stash_f before refine_fine rebuilds the tree: the listed
+// octs (own, virtual and boundary octs of a level, host numbers) park their f.  _restore_f after ramses_amd_amrres_tree, level by
+// level from the coarsest rebuilt one: inherit[i] != 0 -> oct i takes its father cell's f (a new oct), else what it parked.
+int ramses_amd_amrres_stash_f(int ngrid, const int *igrid) {
+  AmrRes &R = g_ar;
+  LvlArgs A;
+  if (int rc = set_level(R, ngrid, igrid, A)) return rc;
+  if (!R.grav) return fail(RAMSES_AMD_EINVAL, "stash_f: no acceleration on the device");
+  R.image_window = false;
+  if (ngrid == 0) return 0;
+  const size_t sb = sizeof(double) * 3 * (size_t)R.ncell_h;
+  if (R.fstage.cap < sb) { HCHK(R.fstage.ensure(sb), "hipMalloc f staging"); HCHK(hipMemsetAsync(R.fstage.p, 0, sb, nullptr), "memset"); }
+  HCHK(R.fraw.ensure(sizeof(int) * (size_t)ngrid), "hipMalloc");
+  HCHK(hipMemcpyAsync(R.fraw.p, igrid, sizeof(int) * (size_t)ngrid, hipMemcpyHostToDevice, nullptr), "H2D oct list");
+  hipLaunchKernelGGL(lvl_f_stash_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, lvl_list(R, R.cur_ig, ngrid, 3), R.fraw.as<int>(), R.ncell_h, R.ngh,
+                     R.f.as<double>(), R.fstage.as<double>());
+  HCHK(hipGetLastError(), "f stash launch");
+  HCHK(hipStreamSynchronize(nullptr), "sync");      // (the list buffer is reused by the next level)
+  return check_lists(R, "stash_f");
+}
+int ramses_amd_amrres_restore_f(int ngrid, const int *igrid, const int *inherit) {
+  AmrRes &R = g_ar;
+  LvlArgs A;
+  if (ngrid > 0 && !inherit) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (int rc = set_level(R, ngrid, igrid, A)) return rc;
+  if (!R.grav) return fail(RAMSES_AMD_EINVAL, "restore_f: no acceleration on the device");
+  R.image_window = false;
+  if (ngrid == 0) return 0;
+  const size_t sb = sizeof(double) * 3 * (size_t)R.ncell_h;
+  if (R.fstage.cap < sb) { HCHK(R.fstage.ensure(sb), "hipMalloc f staging"); HCHK(hipMemsetAsync(R.fstage.p, 0, sb, nullptr), "memset"); }
+  HCHK(R.fraw.ensure(sizeof(int) * (size_t)ngrid), "hipMalloc"); HCHK(R.fflag.ensure(sizeof(int) * (size_t)ngrid), "hipMalloc");
+  HCHK(hipMemcpyAsync(R.fraw.p, igrid, sizeof(int) * (size_t)ngrid, hipMemcpyHostToDevice, nullptr), "H2D oct list");
+  HCHK(hipMemcpyAsync(R.fflag.p, inherit, sizeof(int) * (size_t)ngrid, hipMemcpyHostToDevice, nullptr), "H2D flags");
+  hipLaunchKernelGGL(lvl_f_restore_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, lvl_list(R, R.cur_ig, ngrid, 3), R.fraw.as<int>(), R.fflag.as<int>(),
+                     R.father.as<int>(), R.ncell_h, R.ngh, R.f.as<double>(), R.fstage.as<double>());
+  HCHK(hipGetLastError(), "f restore launch");
+  HCHK(hipStreamSynchronize(nullptr), "sync");
+  return check_lists(R, "restore_f");
+}
+
+// make_boundary_force(ilevel) on the resident acceleration (poisson/boundary_potential.f90:5-174): the arguments of
+// ramses_amd_amrres_boundary_hydro -- nregion regions in the reference's order, btype = boundary_type (1-6 reflexive, 11-16 free,
+// 21-26 imposed: gravana at the boundary cell's centre), ngrid[r] octs of region r, igrid the lists one after the other, nvector
+// the reference build's NVECTOR -- and dx = 0.5**ilevel for the imposed regions' cell centres.
+int ramses_amd_amrres_boundary_force(int nregion, const int *btype, const int *ngrid, const int *igrid, int nvector, double dx) {
+  AmrRes &R = g_ar;
+  if (!R.valid) return fail(RAMSES_AMD_EINVAL, "no resident AMR state (ramses_amd_amrres_load)");
+  if (nregion < 0 || (nregion > 0 && (!btype || !ngrid))) return fail(RAMSES_AMD_EINVAL, "bad boundary description");
+  if (nvector < 1) return fail(RAMSES_AMD_EINVAL, "nvector must be >= 1");
+  if (!R.grav) return fail(RAMSES_AMD_EINVAL, "make_boundary_force: no acceleration on the device (ramses_amd_amrres_load_f)");
+  long ntot = 0;
+  int nmax = 0;
+  bool imposed = false;
+  for (int r = 0; r < nregion; r++) {
+    const int k = btype[r] / 10, d = btype[r] % 10;
+    if (k < 0 || k > 2 || d < 1 || d > 6) return fail(RAMSES_AMD_EINVAL, "make_boundary_force: bad boundary_type %d", btype[r]);
+    if (ngrid[r] < 0) return fail(RAMSES_AMD_EINVAL, "bad boundary oct count");
+    if (k == 2 && ngrid[r] > 0) imposed = true;
+    ntot += ngrid[r];
+    if (ngrid[r] > nmax) nmax = ngrid[r];
+  }
+  if (imposed && !g_gravana_set) return fail(RAMSES_AMD_EINVAL, "make_boundary_force: an imposed boundary needs the analytic gravity (ramses_amd_gravana_set)");
+  if (imposed && !R.xg_valid) return fail(RAMSES_AMD_EINVAL, "make_boundary_force: no oct centres on the device (ramses_amd_amrres_xg)");
+  if (ntot == 0) return 0;
+  if (!igrid) return fail(RAMSES_AMD_EINVAL, "NULL oct list");
+  HCHK(R.bnd_list.ensure(sizeof(int) * (size_t)ntot), "hipMalloc boundary octs");
+  HCHK(R.bnd_tmp.ensure(sizeof(double) * (size_t)nmax * 8 * 3), "hipMalloc boundary accelerations");
+  if (!R.bnd_pos.p || R.bnd_pos.cap < sizeof(int) * (size_t)R.ngridmax) R.bnd_pos_clean = false;
+  HCHK(R.bnd_pos.ensure(sizeof(int) * (size_t)R.ngridmax), "hipMalloc boundary positions");
+  if (!R.bnd_pos_clean) HCHK(hipMemsetAsync(R.bnd_pos.p, 0, sizeof(int) * (size_t)R.ngridmax, nullptr), "memset");
+  R.bnd_pos_clean = false;      // (as in make_boundary_hydro: clean again after the last region's clear has been queued)
+  if (int rc = upload_list(R, R.bnd_list, igrid, (int)ntot)) return rc;
+  BndArgs A;
+  A.uold = R.f.as<double>(); A.tmp = R.bnd_tmp.as<double>();
+  A.son = R.son.as<int>(); A.nbor = R.nbor.as<int>(); A.pos = R.bnd_pos.as<int>();
+  A.nvar = 3; A.no_inflow = 0; A.nvector = nvector; A.ncell = R.ncell; A.ncoarse = R.ncoarse; A.ngridmax = R.ngridmax; A.smallr = 0.0;
+  const GravAna G = g_gravana_set ? g_gravana : GravAna{};
+  long off = 0;
+  for (int r = 0; r < nregion; r++) {
+    const int n = ngrid[r];
+    if (n > 0) {
+      A.list = R.bnd_list.as<int>() + off; A.n = n; A.type = btype[r];
+      const bool chain = btype[r] / 10 != 2;
+      if (chain) hipLaunchKernelGGL(bnd_mark_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, nullptr, A, 0);
+      hipLaunchKernelGGL(bndf_compute_kernel, lvl_grid(n), dim3(256), 0, nullptr, A, G, R.xg.as<double>(), dx);
+      hipLaunchKernelGGL(bnd_store_kernel, lvl_grid(n), dim3(256), 0, nullptr, A);
+      if (chain) hipLaunchKernelGGL(bnd_mark_kernel, dim3(grid_for(n, GRID_CAP)), dim3(256), 0, nullptr, A, 1);
+    }
+    off += n;
+  }
+  HCHK(hipGetLastError(), "make_boundary_force launch");
+  HCHK(hipStreamSynchronize(nullptr), "sync");      // (the list buffer is reused by the next call)
+  R.bnd_pos_clean = true;
   return 0;
 }
 

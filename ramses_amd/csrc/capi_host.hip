@@ -830,6 +830,30 @@ int ramses_amd_resident_force_fine_f90(int ilevel, double fact, double *diag2) {
   return 0;
 }
 
+// force_fine(ilevel,icount) of a run with analytic gravity (gravity_type 1 | 2, ramses_amd_gravana_set) on the resident level:
+// f = gravana at the cell centres into the acceleration brick; diag2 as above, over the deposit rho_fine left on the device
+int ramses_amd_resident_force_ana_f90(int ilevel, double fact, double *diag2) {
+  HostCtx &H = g_host;
+  if (!diag2) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  if (int rc = resident_level_is(ilevel, "force_fine")) return rc;
+  const GravAna *G = capi_gravana();
+  if (!G) return fail(RAMSES_AMD_EINVAL, "force_fine: no analytic gravity set (ramses_amd_gravana_set)");
+  if (!H.res_rho_valid) return fail(RAMSES_AMD_EINVAL, "force_fine: no density deposit on the device (rho_fine)");
+  const int n = 1 << ilevel;
+  const long N = (long)n * n * n;
+  hipStream_t s = nullptr;
+  HCHK(H.bf.ensure(sizeof(double) * 3 * N), "hipMalloc f brick");
+  HCHK(H.diag.ensure(sizeof(double) * (FORCE_DIAG_SCRATCH + 8)), "hipMalloc");
+  HCHK(launch_gravana_brick(*G, n, std::ldexp(1.0, -ilevel), H.bf.as<double>(), s), "gravana launch");
+  H.res_grav_valid = true;
+  double *scratch = H.diag.as<double>();
+  HCHK(launch_force_diag(H.bf.as<double>(), H.brho.as<double>(), nullptr, N, fact, scratch, scratch + FORCE_DIAG_SCRATCH, s), "force diagnostics launch");
+  HCHK(hipMemcpyAsync(diag2, scratch + FORCE_DIAG_SCRATCH, sizeof(double) * 2, hipMemcpyDeviceToHost, s), "D2H diag");
+  HCHK(hipStreamSynchronize(s), "sync");
+  H.res_pois_host_stale = true;
+  return 0;
+}
+
 // phi, f(1:ncell,1:3) and rho of the resident level back into the host arrays (backup_poisson)
 int ramses_amd_resident_sync_poisson_f90(double *phi, double *f, double *rho) {
   HostCtx &H = g_host;

@@ -87,4 +87,8 @@ static inline int refuse_amr(const ramses_amd_hydro_params *p, const char *who) 
 // the only current copy of the hydro state
 int capi_resident_release(const char *who);
 
+// capi_amr.hip: what ramses_amd_gravana_set stored (csrc/gravana_core.hpp), or null before it
+struct GravAna;
+const GravAna *capi_gravana();
+
 }  // namespace ramses_amd

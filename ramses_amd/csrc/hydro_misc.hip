@@ -425,6 +425,23 @@ hipError_t launch_force_diag(const double *f, const double *rho, const int *leaf
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// force_fine's analytic branch on a level brick (gravity_type 1 | 2, csrc/gravana_core.hpp): cell c = i + n (j + n k) has its
+// centre at (i + 0.5) dx in code units -- exact, so it carries the bits of the reference's xg + xc -- and force_fine's
+// rescaling (x - skip) * scale follows.  One lane per cell.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gravana_brick_kernel(GravAna G, int n, double dx, double *__restrict__ f) {
+  const long N = (long)n * n * n;
+  for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < N; c += (long)gridDim.x * blockDim.x) {
+    const int i = (int)(c % n), j = (int)((c / n) % n), k = (int)(c / ((long)n * n));
+    const double x[3] = {(((double)i + 0.5) * dx - G.skip[0]) * G.scale, (((double)j + 0.5) * dx - G.skip[1]) * G.scale,
+                         (((double)k + 0.5) * dx - G.skip[2]) * G.scale};
+    double ff[3];
+    gravana_cell(G, x, ff);
+    f[c] = ff[0]; f[N + c] = ff[1]; f[2 * N + c] = ff[2];
+  }
+}
+
 static inline int misc_grid(long work) {
   long g = (work + 255) / 256;
   if (g < 1) g = 1;
@@ -438,6 +455,10 @@ hipError_t launch_synchro_hydro(double *u, const double *f, long N, double dteff
 hipError_t launch_add_gravity_source(double *unew, const double *uold, const double *f, long N, double dt, double smallr,
                                      hipStream_t s) {
   hipLaunchKernelGGL(add_gravity_source_kernel, dim3(misc_grid(N)), dim3(256), 0, s, unew, uold, f, N, dt, smallr);
+  return hipGetLastError();
+}
+hipError_t launch_gravana_brick(const GravAna &G, int n, double dx, double *f, hipStream_t s) {
+  hipLaunchKernelGGL(gravana_brick_kernel, dim3(misc_grid((long)n * n * n)), dim3(256), 0, s, G, n, dx, f);
   return hipGetLastError();
 }
 

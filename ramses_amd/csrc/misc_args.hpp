@@ -1,6 +1,7 @@
 // misc_args.hpp -- argument blocks of the streaming kernels.
 #pragma once
 #include "hydro_core.hpp"
+#include "gravana_core.hpp"
 
 namespace ramses_amd {
 
@@ -79,5 +80,9 @@ hipError_t launch_add_gravity_source(double *unew, const double *uold, const dou
 constexpr int FORCE_DIAG_SCRATCH = 1024;
 hipError_t launch_force_diag(const double *f, const double *rho, const int *leaf, long N, double fact, double *partial,
                              double *out, hipStream_t s);
+
+// force_fine's analytic branch (poisson/force_fine.f90:58-103, gravity_type 1 | 2) on an n^3 level brick: f[3][n^3] = gravana at
+// the cell centres ((i + 0.5) dx is exact, so it is the reference's xg + xc)
+hipError_t launch_gravana_brick(const GravAna &G, int n, double dx, double *f, hipStream_t s);
 
 }  // namespace ramses_amd

@@ -5,7 +5,9 @@
 ! reference file is pulled in by the preprocessor with force_fine renamed to
 ! force_fine_reference, so gradient_phi stays the reference's; the new
 ! force_fine(ilevel,icount) keeps the reference's name, arguments and meaning
-! and computes the acceleration of a fully refined periodic level on the MI355X.
+! and computes the acceleration on the MI355X: the gradient of the potential of a fully refined periodic level or of an
+! AMR level, and, with RAMSES_AMD_GRAVANA=1, the analytic acceleration of gravity_type 1 | 2 on the resident levels
+! (ramses_amd_force_fine_ana below); anything else is the reference's routine.
 !==============================================================================
 #define force_fine force_fine_reference
 #include "poisson/force_fine.f90"
@@ -34,6 +36,38 @@ subroutine force_fine_amd(ilevel,icount)
 
   if(numbtot(1,ilevel)==0)return
   nx_loc=(icoarse_max-icoarse_min+1)
+  ! analytic gravity (gravity_type 1 | 2) of a resident run, RAMSES_AMD_GRAVANA=1 and the self-check passed
+  ! (ramses_amd_gravana_on): f is a function of the cell centre alone, the device writes its resident copy and force_fine sends
+  ! nothing (across a regrid: ramses_amd_amr_stash_f / _restore_f; f goes up only with a load of the whole device image).
+  ! Before the time loop arms the residency (the first force_fine of every level) the reference's loop runs.
+  if(gravity_type>0.and.ndim==3)then
+     if(ramses_amd_gravana_on())then
+        if(ramses_amd_amr_resident())then
+           if(verbose)write(*,111)ilevel
+           call ramses_amd_tic(tm)
+           call ramses_amd_force_fine_ana(ilevel)
+           call ramses_amd_toc('force_fine (device, analytic)',ilevel,tm)
+           return
+        end if
+        if(ramses_amd_resident().and.ramses_amd_pois_dev.and.ilevel>=2 &
+             & .and.int(active(ilevel)%ngrid,8)*8_8==(2_8**ilevel)**3*int(nx_loc,8)**3)then
+           ! one uniform level resident as a brick (rho_fine has just left its deposit there)
+           if(verbose)write(*,111)ilevel
+           dx=0.5D0**ilevel
+           scale=boxlen/dble(nx_loc)
+           dx_loc=dx*scale
+           fourpi=2*twopi
+           if(cosmo)fourpi=1.5D0*omega_m*aexp
+           fact=-dx_loc**ndim/fourpi/2.0D0
+           rc=ramses_amd_resident_force_ana_f90(ilevel,fact,diag)
+           if(rc/=0)call ramses_amd_fatal('force_fine (analytic, resident level)')
+           epot_tot=epot_tot+diag(1)
+           rho_max(ilevel)=diag(2)
+           ramses_amd_mgdist_phi_level=0
+           return
+        end if
+     end if
+  end if
   fresh=0
   if(ramses_amd_pois_amr_level==ilevel)fresh=1
   ramses_amd_pois_amr_level=0
@@ -129,6 +163,115 @@ subroutine force_fine_amd(ilevel,icount)
 111 format('   Entering force_fine (MI355X) for level ',I2)
 
 end subroutine force_fine_amd
+
+!------------------------------------------------------------------------------
+! force_fine(ilevel,icount)'s analytic branch (poisson/force_fine.f90:58-109) of an AMR run whose state is resident: f of the
+! rank's own AND virtual octs of the level = gravana at the cell centres, written by the device into its resident copy (the value
+! is the same on both sides, so the reference's three make_virtual_fine_dp(f) would copy equal bits: no exchange);
+! make_boundary_force follows on the device, fed with the regions' lists as make_boundary_hydro's shim builds them.  The host
+! array f is not written: refine_fine, backup_poisson and load_balance fetch it (ramses_amd_f_on_device).  The diagnostics
+! (:143-190): the potential-energy term from the device, max |rho| from the device where the deposit is kept there, else the
+! reference's host loop; their two all-reduces stay the reference's.
+!------------------------------------------------------------------------------
+subroutine ramses_amd_force_fine_ana(ilevel)
+  use amr_commons
+  use pm_commons
+  use poisson_commons
+  use constants, only : twopi
+  use ramses_amd_iface
+  use mpi_mod
+  implicit none
+  integer,intent(in)::ilevel
+  integer::rc,nx_loc,n,nl,i,ib,ind,iskip,icpu
+#ifndef WITHOUTMPI
+  integer::info
+  real(kind=8)::epot_all,rho_all
+#endif
+  integer,allocatable,dimension(:)::list,cnt
+  real(dp)::dx,dx_loc,scale,fact,fourpi
+  real(kind=8),dimension(2)::diag
+  real(kind=8)::epot_loc,rho_loc
+  integer,save::xg_epoch=-1
+  call ramses_amd_amr_ensure()
+  if(xg_epoch/=ramses_amd_tree_epoch)then
+     rc=ramses_amd_amrres_xg(xg)
+     if(rc/=0)call ramses_amd_fatal('force_fine (analytic, oct centres)')
+     xg_epoch=ramses_amd_tree_epoch
+  end if
+  nx_loc=(icoarse_max-icoarse_min+1)
+  dx=0.5D0**ilevel
+  scale=boxlen/dble(nx_loc)
+  dx_loc=dx*scale
+  fourpi=2*twopi
+  if(cosmo)fourpi=1.5D0*omega_m*aexp
+  fact=-dx_loc**ndim/fourpi/2.0D0
+  ! the own octs, then the virtual ones (the device takes their number from the level's communicators)
+  nl=active(ilevel)%ngrid
+  if(ncpu>1)then
+     do icpu=1,ncpu
+        nl=nl+reception(icpu,ilevel)%ngrid
+     end do
+  end if
+  allocate(list(max(nl,1)))
+  n=active(ilevel)%ngrid
+  list(1:n)=active(ilevel)%igrid(1:n)
+  if(ncpu>1)then
+     do icpu=1,ncpu
+        do i=1,reception(icpu,ilevel)%ngrid
+           list(n+i)=reception(icpu,ilevel)%igrid(i)
+        end do
+        n=n+reception(icpu,ilevel)%ngrid
+     end do
+#ifndef WITHOUTMPI
+     call ramses_amd_amr_comm_ensure(ilevel)
+#endif
+  end if
+  diag=0d0
+  rc=ramses_amd_amrres_force_ana(ilevel,nl,list,dx,fact,diag)
+  if(rc/=0)call ramses_amd_fatal('force_fine (analytic)')
+  deallocate(list)
+  ramses_amd_f_on_device(ilevel)=.true.
+  ! make_boundary_force (:109)
+  if(simple_boundary.and.nboundary>0)then
+     n=0
+     do ib=1,nboundary
+        n=n+boundary(ib,ilevel)%ngrid
+     end do
+     if(n>0)then
+        allocate(cnt(nboundary),list(n))
+        n=0
+        do ib=1,nboundary
+           cnt(ib)=boundary(ib,ilevel)%ngrid
+           do i=1,cnt(ib)
+              list(n+i)=boundary(ib,ilevel)%igrid(i)
+           end do
+           n=n+cnt(ib)
+        end do
+        rc=ramses_amd_amrres_boundary_force(nboundary,boundary_type,cnt,list,nvector,dx)
+        if(rc/=0)call ramses_amd_fatal('make_boundary_force')
+        deallocate(cnt,list)
+     end if
+  end if
+  epot_loc=diag(1); rho_loc=diag(2)
+  if(rho_loc<0d0)then
+     ! the deposit lives in the host vector (rho_fine has just written it there): the reference's loop (:175-177)
+     rho_loc=0d0
+     do ind=1,twotondim
+        iskip=ncoarse+(ind-1)*ngridmax
+        do i=1,active(ilevel)%ngrid
+           rho_loc=MAX(rho_loc,dble(abs(rho(iskip+active(ilevel)%igrid(i)))))
+        end do
+     end do
+  end if
+#ifndef WITHOUTMPI
+  call MPI_ALLREDUCE(epot_loc,epot_all,1,MPI_DOUBLE_PRECISION,MPI_SUM,MPI_COMM_WORLD,info)
+  call MPI_ALLREDUCE(rho_loc ,rho_all ,1,MPI_DOUBLE_PRECISION,MPI_MAX,MPI_COMM_WORLD,info)
+  epot_loc=epot_all
+  rho_loc =rho_all
+#endif
+  epot_tot=epot_tot+epot_loc
+  rho_max(ilevel)=rho_loc
+end subroutine ramses_amd_force_fine_ana
 
 #ifndef WITHOUTMPI
 subroutine ramses_amd_force_fine_mpi(ilevel,icount)

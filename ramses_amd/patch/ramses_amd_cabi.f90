@@ -781,6 +781,59 @@ module ramses_amd_cabi
        real(c_double) :: imposed(*)
        integer(c_int) :: rc
      end function ramses_amd_amrres_boundary_hydro
+     ! analytic gravity (gravity_type 1, 2) on the device
+     function ramses_amd_gravana_set(gtype, params10, skip3, scale) bind(C, name='ramses_amd_gravana_set') result(rc)
+       import :: c_int, c_double
+       integer(c_int), value :: gtype
+       real(c_double) :: params10(10), skip3(3)
+       real(c_double), value :: scale
+       integer(c_int) :: rc
+     end function ramses_amd_gravana_set
+     function ramses_amd_gravana_eval(n, x, f) bind(C, name='ramses_amd_gravana_eval') result(rc)
+       import :: c_int, c_int64_t, c_double
+       integer(c_int64_t), value :: n
+       real(c_double) :: x(*), f(*)
+       integer(c_int) :: rc
+     end function ramses_amd_gravana_eval
+     function ramses_amd_amrres_force_ana(ilevel, ngrid, igrid, dx, fact, diag2) bind(C, name='ramses_amd_amrres_force_ana') result(rc)
+       import :: c_int, c_double
+       integer(c_int), value :: ilevel, ngrid
+       integer(c_int) :: igrid(*)
+       real(c_double), value :: dx, fact
+       real(c_double) :: diag2(2)
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_force_ana
+     function ramses_amd_amrres_boundary_force(nregion, btype, ngrid, igrid, nvector, dx) &
+          & bind(C, name='ramses_amd_amrres_boundary_force') result(rc)
+       import :: c_int, c_double
+       integer(c_int), value :: nregion, nvector
+       integer(c_int) :: btype(*), ngrid(*), igrid(*)
+       real(c_double), value :: dx
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_boundary_force
+     function ramses_amd_resident_force_ana_f90(ilevel, fact, diag2) bind(C, name='ramses_amd_resident_force_ana_f90') result(rc)
+       import :: c_int, c_double
+       integer(c_int), value :: ilevel
+       real(c_double), value :: fact
+       real(c_double) :: diag2(2)
+       integer(c_int) :: rc
+     end function ramses_amd_resident_force_ana_f90
+     function ramses_amd_amrres_has_gravity() bind(C, name='ramses_amd_amrres_has_gravity') result(rc)
+       import :: c_int
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_has_gravity
+     function ramses_amd_amrres_stash_f(ngrid, igrid) bind(C, name='ramses_amd_amrres_stash_f') result(rc)
+       import :: c_int
+       integer(c_int), value :: ngrid
+       integer(c_int) :: igrid(*)
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_stash_f
+     function ramses_amd_amrres_restore_f(ngrid, igrid, inherit) bind(C, name='ramses_amd_amrres_restore_f') result(rc)
+       import :: c_int
+       integer(c_int), value :: ngrid
+       integer(c_int) :: igrid(*), inherit(*)
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_restore_f
      function ramses_amd_amrres_sync_all(uold) bind(C, name='ramses_amd_amrres_sync_all') result(rc)
        import :: c_int, c_double
        real(c_double) :: uold(*)

@@ -34,6 +34,8 @@ module ramses_amd_iface
   logical, save :: ramses_amd_amr_ok = .false.
   logical, save :: ramses_amd_amr_armed = .false.
   integer, save :: ramses_amd_amr_reload_from = 1000   ! levels >= this were rebuilt on the host and await their reload
+  ! analytic gravity on the device: levels >= this have parked their f on the device for the regrid under way (ramses_amd_amr_stash_f)
+  integer, save :: ramses_amd_f_stash_from = 1000
   integer, save :: ramses_amd_amr_host_from = 1000     ! levels >= this are current on the host (synced or rebuilt) since the last device routine
   ! advanced whenever the reference may have changed the tree (refine_fine); the device copies of son/nbor/father
   ! are re-sent when their epoch is behind
@@ -346,7 +348,11 @@ contains
           if (stat == 0) then
              if (trim(val) == '0') ramses_amd_res_on = .false.
           end if
-          if (gravity_type > 0 .or. cosmo) ramses_amd_res_on = .false.
+          ! analytic gravity: only with RAMSES_AMD_GRAVANA=1, gravity_type 1 | 2 and the self-check (ramses_amd_gravana_on)
+          if (cosmo) ramses_amd_res_on = .false.
+          if (gravity_type > 0) then
+             if (.not. ramses_amd_gravana_on()) ramses_amd_res_on = .false.
+          end if
        end if
        if (tracer .or. MC_tracer .or. clumpfind .or. lightcone .or. movie .or. aton) ramses_amd_res_on = .false.
        if (static .or. static_gas .or. neq_chem .or. barotropic_eos .or. isothermal .or. metal) ramses_amd_res_on = .false.
@@ -685,7 +691,11 @@ contains
           if (stat == 0) then
              if (trim(val) == '0') ramses_amd_amr_ok = .false.
           end if
-          if (gravity_type > 0 .or. cosmo) ramses_amd_amr_ok = .false.
+          ! analytic gravity: only with RAMSES_AMD_GRAVANA=1, gravity_type 1 | 2 and the self-check (ramses_amd_gravana_on)
+          if (cosmo) ramses_amd_amr_ok = .false.
+          if (gravity_type > 0) then
+             if (.not. ramses_amd_gravana_on()) ramses_amd_amr_ok = .false.
+          end if
        end if
        ! jeans_refine and m_refine are evaluated on the resident state (hydro_flag.f90, flag_utils.f90, rho_fine.f90 of this
        ! directory: ramses_amd_amrres_refine_flag / _mass_map); RAMSES_AMD_RESIDENT_REFINE=0 keeps such runs staged, as they
@@ -751,6 +761,71 @@ contains
     end if
     ramses_amd_f_resident_on = on
   end function ramses_amd_f_resident_on
+
+  !---------------------------------------------------------------------------
+  ! Analytic gravity on the device (RAMSES_AMD_GRAVANA=1, opt-in): force_fine of a run with gravity_type 1 or 2 writes the
+  ! resident acceleration from the resident oct centres (csrc/gravana_core.hpp), so such a run keeps the resident paths.  True
+  ! only if the switch is set, gravity_type is 1 or 2 and the SELF-CHECK passes: whatever gravana is linked into this program --
+  ! the reference's, or a user's patched one -- is called on nvector cell centres spread over the box at the finest dx and
+  ! must return, bit for bit, what the device function returns there (ramses_amd_gravana_eval).  Otherwise rank 1 says why in one
+  ! line and the run stays staged, as without the switch.  gravity_type 3 stays staged: its **0.5 is a pow call of the runtime
+  ! library.  Decided once.
+  !---------------------------------------------------------------------------
+  logical function ramses_amd_gravana_on()
+    use amr_commons
+    use poisson_parameters, only: gravity_type, gravity_params
+    character(len=16) :: val
+    integer :: stat, rc, i, idim, nx_loc, lev, n, nbad
+    logical, save :: first = .true., on = .false.
+    integer, parameter :: prime(3) = (/7919, 104729, 1299709/)
+    external :: gravana
+    real(dp) :: xx(1:nvector, 1:ndim), ff(1:nvector, 1:ndim), scale, dxf
+    real(c_double) :: xdev(1:nvector, 1:3), fdev(1:nvector, 1:3), p10(10), skip3(3)
+    if (first) then
+       first = .false.
+       call get_environment_variable('RAMSES_AMD_GRAVANA', val, status=stat)
+       if (stat /= 0) val = '0'
+       if (trim(val) == '1' .and. ramses_amd_enabled() .and. poisson .and. gravity_type > 0 .and. ndim == 3) then
+          if (gravity_type > 2) then
+             if (myid == 1) write(*,*) 'ramses_amd: RAMSES_AMD_GRAVANA=1 but gravity_type=', gravity_type, &
+                  & ' is not evaluated on the device (types 1 and 2 are): the run stays staged'
+          else
+             nx_loc = icoarse_max - icoarse_min + 1
+             scale = boxlen / dble(nx_loc)
+             skip3 = (/dble(icoarse_min), dble(jcoarse_min), dble(kcoarse_min)/)
+             p10 = 0.0d0
+             p10(1:min(10, size(gravity_params))) = gravity_params(1:min(10, size(gravity_params)))
+             rc = ramses_amd_gravana_set(gravity_type, p10, skip3, scale)
+             if (rc /= 0) call ramses_amd_fatal('analytic gravity (set)')
+             lev = min(nlevelmax, 30)
+             n = 2**lev
+             dxf = 0.5d0**lev
+             xdev = 0.0d0
+             do idim = 1, ndim
+                do i = 1, nvector
+                   xx(i, idim) = ((dble(mod(int(i, 8) * prime(idim) + idim, int(n, 8))) + 0.5d0) * dxf) * scale
+                   xdev(i, idim) = xx(i, idim)
+                end do
+             end do
+             ff = 0.0d0
+             call gravana(xx, ff, dxf * scale, nvector)
+             rc = ramses_amd_gravana_eval(int(nvector, 8), xdev, fdev)
+             if (rc /= 0) call ramses_amd_fatal('analytic gravity (self-check)')
+             nbad = 0
+             do idim = 1, ndim
+                do i = 1, nvector
+                   if (transfer(ff(i, idim), 1_8) /= transfer(fdev(i, idim), 1_8)) nbad = nbad + 1
+                end do
+             end do
+             on = nbad == 0
+             if (.not. on .and. myid == 1) write(*,*) 'ramses_amd: RAMSES_AMD_GRAVANA=1 but the gravana of this program differs from the device''s in ', &
+                  & nbad, ' of ', ndim * nvector, ' sample values (a patched gravana?): the run stays staged'
+             if (on .and. myid == 1) write(*,*) 'ramses_amd: analytic gravity (gravity_type ', gravity_type, ') is evaluated on the GPU'
+          end if
+       end if
+    end if
+    ramses_amd_gravana_on = on
+  end function ramses_amd_gravana_on
 
   ! f of the levels whose acceleration lives on the device only, back into the host array (backup_poisson, load_balance;
   ! one level: refine_fine, whose new octs inherit their father cell's f)
@@ -885,12 +960,73 @@ contains
                 rc = ramses_amd_amrres_load_level(active(l)%ngrid, ramses_amd_octs(l), uold)
              end if
              if (rc /= 0) call ramses_amd_fatal('AMR residency (level reload)')
-             if (poisson) call ramses_amd_amr_load_f(l)
+             if (poisson) then
+                ! analytic gravity on the device: f of the rebuilt level does not come up again -- what the octs parked before
+                ! the regrid, the father cell's f for the new ones (coarsest rebuilt level first: the fathers are complete)
+                if (ramses_amd_gravana_live()) then
+                   call ramses_amd_amr_restore_f(l)
+                else
+                   call ramses_amd_amr_load_f(l)
+                end if
+             end if
           end if
        end do
        ramses_amd_amr_reload_from = 1000
+       ramses_amd_f_stash_from = 1000
     end if
   end subroutine ramses_amd_amr_ensure
+
+  ! analytic gravity evaluated on the device in this run (the gates have asked ramses_amd_gravana_on by the time anything is resident)
+  logical function ramses_amd_gravana_live()
+    use poisson_parameters, only: gravity_type
+    ramses_amd_gravana_live = .false.
+    if (gravity_type > 0) ramses_amd_gravana_live = ramses_amd_gravana_on()
+  end function ramses_amd_gravana_live
+
+  ! refine_fine(ilevel) is about to rebuild the finer levels: f of the levels ilevel .. that still have their lists and have
+  ! not parked it in this regrid stays on the device in the host's numbering (own, virtual and boundary octs)
+  subroutine ramses_amd_amr_stash_f(ilevel)
+    use amr_commons
+    integer, intent(in) :: ilevel
+    integer :: l, rc, nl
+    integer, allocatable :: list(:)
+    if (ramses_amd_amrres_has_gravity() == 0) return
+    do l = ilevel, min(nlevelmax, ramses_amd_amr_reload_from - 1, ramses_amd_f_stash_from - 1)
+       if (numbtot(1, l) > 0) then
+          call ramses_amd_amr_level_octs(l, nl, list)
+          rc = ramses_amd_amrres_stash_f(nl, list)
+          deallocate(list)
+          if (rc /= 0) call ramses_amd_fatal('AMR residency (acceleration parked before refine_fine)')
+       end if
+    end do
+    ramses_amd_f_stash_from = min(ramses_amd_f_stash_from, ilevel)
+  end subroutine ramses_amd_amr_stash_f
+
+  ! f of a rebuilt level on the device without an upload: an oct whose 8 x ndim values equal its father cell's bit for bit (the
+  ! host array, which refine_fine has just completed: make_grid_fine gives a new oct exactly that) takes the father cell's f on
+  ! the device, every other oct what it parked (ramses_amd_amr_stash_f); only the list and one flag per oct go down
+  subroutine ramses_amd_amr_restore_f(ilevel)
+    use amr_commons
+    use poisson_commons, only: f
+    integer, intent(in) :: ilevel
+    integer :: rc, nl, i, ind, idim, g, fc
+    integer, allocatable :: list(:), inherit(:)
+    call ramses_amd_amr_level_octs(ilevel, nl, list)
+    allocate(inherit(max(nl, 1)))
+    do i = 1, nl
+       g = list(i)
+       fc = father(g)
+       inherit(i) = 1
+       do idim = 1, ndim
+          do ind = 1, twotondim
+             if (transfer(f(ncoarse + (ind - 1) * ngridmax + g, idim), 1_8) /= transfer(f(fc, idim), 1_8)) inherit(i) = 0
+          end do
+       end do
+    end do
+    rc = ramses_amd_amrres_restore_f(nl, list, inherit)
+    deallocate(list, inherit)
+    if (rc /= 0) call ramses_amd_fatal('AMR residency (acceleration of a rebuilt level)')
+  end subroutine ramses_amd_amr_restore_f
 
   ! the acceleration of one level from the host array f (force_fine has just written it, or the level was rebuilt)
   subroutine ramses_amd_amr_load_f(ilevel)
@@ -945,6 +1081,7 @@ contains
     ! -- and of every finer level now, while the device's oct numbering still matches the host's lists (refine_fine(ilevel)
     ! rebuilds level ilevel+1 before refine_fine(ilevel+1) asks for it)
     if (poisson) then
+       if (ramses_amd_gravana_live()) call ramses_amd_amr_stash_f(ilevel)
        do l = ilevel, min(nlevelmax, 64)
           if (ramses_amd_f_on_device(l)) call ramses_amd_amr_sync_f_level(l)
        end do
@@ -981,6 +1118,7 @@ contains
     if (rc /= 0) call ramses_amd_fatal('AMR residency (invalidate before '//where//')')
     ramses_amd_amr_reload_from = 1000
     ramses_amd_amr_host_from = 1000
+    ramses_amd_f_stash_from = 1000
   end subroutine ramses_amd_amr_host_takeover
 
   !---------------------------------------------------------------------------
