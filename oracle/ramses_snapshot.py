@@ -258,9 +258,9 @@ def cons_to_prim(u, gamma, smallr=1e-10):
     return q
 
 
-def run_reference(namelist_text, ndim=3, nproc=1, binary=None, keep=False, timeout=3600):
+def run_reference(namelist_text, ndim=3, nproc=1, binary=None, keep=False, timeout=3600, env=None):
     """Run oracle/_ref/ramses{ndim}d on a namelist in a scratch directory.
-    Returns (workdir, stdout).  Caller removes workdir unless keep."""
+    Returns (workdir, stdout).  Caller removes workdir unless keep.  env: the program's environment (None: the caller's)."""
     if binary is None:
         binary = os.path.join(HERE, "_ref", "ramses%dd" % ndim)
     if not os.path.exists(binary):
@@ -272,7 +272,7 @@ def run_reference(namelist_text, ndim=3, nproc=1, binary=None, keep=False, timeo
     if nproc > 1:
         cmd = ["/opt/conda/bin/mpiexec", "-n", str(nproc)] + cmd
     out = subprocess.run(cmd, cwd=work, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
-                         timeout=timeout)
+                         timeout=timeout, env=env)
     if out.returncode != 0 and "Run completed" not in out.stdout:
         if not keep:
             shutil.rmtree(work, ignore_errors=True)

@@ -1,7 +1,22 @@
 """Shared test helpers: seeded synthetic states in the brick layout."""
 import math
+import os
+import shutil
 
 import numpy as np
+
+
+def hip_include(header="hip_runtime_api.h"):
+    """the include directory of the ROCm installation that holds hip/<header>: for the tests that compile with the host compiler"""
+    cands = [os.environ.get("ROCM_PATH"), os.environ.get("HIP_PATH")]
+    hipcc = shutil.which("hipcc")
+    if hipcc:
+        cands.append(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))))
+    cands.append("/opt/rocm")
+    for c in cands:
+        if c and os.path.exists(os.path.join(c, "include", "hip", header)):
+            return os.path.join(c, "include")
+    raise RuntimeError("hip/%s not found" % header)
 
 
 def random_brick(nx, ny, nz, seed, gamma=1.4, contrast=True, nvar=5):
@@ -86,7 +101,7 @@ def shell_mask(nc, lo=0.23, hi=0.36, seam=True):
 
 
 def mild_tree_state(T, seed, nvar=5):
-    """the mild state of the AMR tile tests (their _random_state): density in [1, 2), momenta rho (U - 1/2), internal energy in
+    """the mild state of the AMR tile tests: density in [1, 2), momenta rho (U - 1/2), internal energy in
     [1, 2), passive scalars rho x a fraction -- subsonic, above every floor"""
     rng = np.random.default_rng(seed)
     n = T["ncell"] - 1

@@ -15,43 +15,28 @@ refined cells on the periodic seam (tiles do not exist below level 6).  A case i
 -- set_unew on both levels, godunov_fine of level 7 then 6, set_uold, sync -- compared in all cells of both levels: strict
 arithmetic bit for bit, riemann = 'exact' to 1e-12 of each variable's maximum (the device's pow()), fast arithmetic to the same
 1e-12.  With NVAR > 5 the expectation is the oracle's unew through set_uold's passive-scalar floor fix (numpy, helpers.py)."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
-from helpers import _set_uold_scalar_fix, harsh_tree_state, shell_mask, tree_cell_kind, tree_state_shares
+import resident as R
+from helpers import _set_uold_scalar_fix, harsh_tree_state, oct_cells, tree_cell_kind, tree_state_shares
 
 pytestmark = pytest.mark.gpu
 L = 6
 SEED = 12
 FLOOR = 0.6           # the high density floor: about half of the cells lie below it
 MAX_SHARE_BELOW_ZERO, LOWEST_DENSITY = 1e-4, -0.01   # what the ORACLE may leave with that floor (see _oracle_step); 0 cells with 1e-10
-LAYOUT_VARS = ("RAMSES_AMD_DEVICE_ORDER", "RAMSES_AMD_TILES", "RAMSES_AMD_TILE_DENSE", "RAMSES_AMD_COVERED_DENSE", "RAMSES_AMD_TILE_SWEEP",
-               "RAMSES_AMD_DIFMAG_TILES")
-
-
 @pytest.fixture(autouse=True)
 def _dense_sweep_on_small_levels_too(monkeypatch):
-    """(levels below RAMSES_AMD_TILE_MIN_OCTS octs take the tree-walking sweep in production: the tests force the tiles)"""
-    monkeypatch.setenv("RAMSES_AMD_TILE_MIN_OCTS", "0")
-    for var in LAYOUT_VARS:
-        monkeypatch.delenv(var, raising=False)
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+    R.force_tiles(monkeypatch, clear=R.LAYOUT_VARS + ("RAMSES_AMD_DIFMAG_TILES",))
 
 
 @functools.lru_cache(maxsize=None)
 def _tree(order):
-    from ramses_amd import ic
-    T = ic.uniform_tree(L, order=order, refine_mask=shell_mask(2 ** L), slack=260000)
-    T["all_octs"] = {L: np.ascontiguousarray(np.sort(T["igrid"])), L + 1: np.ascontiguousarray(np.sort(T["igrid_fine"]))}
-    T["lists"] = {L: np.ascontiguousarray(T["igrid"]), L + 1: np.ascontiguousarray(T["igrid_fine"])}
-    T["cells"] = {lev: np.concatenate([T["ncoarse"] + ind * T["ngridmax"] + T["lists"][lev].astype(np.int64) - 1 for ind in range(8)])
-                  for lev in (L, L + 1)}
+    T = R.two_level_tree(L, order)
+    T["cells"] = {lev: oct_cells(T, T["lists"][lev]) for lev in (L, L + 1)}
     T["both"] = np.concatenate([T["cells"][L], T["cells"][L + 1]])
     T["grav"] = np.random.default_rng(5).normal(size=(3, T["ncell"]))
     return T
@@ -86,12 +71,8 @@ def _oracle_step(oracle, po, T, uold, f, interp, pfix0=None):
     reference's own arithmetic a few of the 567 616 cells end below zero: over the floored cases of this file (CPU, oracle alone)
     1 to 3 cells, 11 with the acoustic solver and the 27-point slope, the lowest at -5.8e-3.  Bounded here at one cell in 10 000
     (56 cells) and -0.01 (a sixtieth of the floor); a state or an oracle that drove densities negative at large would not pass."""
-    unew = uold.copy()
     divu, enew = (pfix0[0].copy(), pfix0[1].copy()) if pfix0 else (None, None)
-    for lev in (L + 1, L):
-        dx = 1.0 / 2 ** lev
-        oracle.godunov_fine_amr(po, T["lists"][lev], T["son"], T["nbor"], T["father"], T["ngridmax"], T["ncoarse"], uold, unew, dx, 0.02 * dx, 32,
-                                interp[0], interp[1], f=f, divu=divu, enew=enew)
+    unew = R.oracle_step(oracle, po, T, uold, f, interp, divu, enew)
     cells = T["both"]
     assert np.isfinite(unew[:, cells]).all()
     growth = (np.abs(unew[:, cells]).max(axis=1) / np.abs(uold[:, cells]).max(axis=1)).max()
@@ -147,55 +128,6 @@ def _set_unew_pfix_numpy(T, uold, smallr):
     return divu, enew
 
 
-def _load(Lb, T, u, f, pfix):
-    from ramses_amd._capi import check
-    check(Lb.ramses_amd_amrres_invalidate())
-    check(Lb.ramses_amd_amrres_load(u.shape[0], T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
-    if f is not None:
-        for lev in (L, L + 1):
-            check(Lb.ramses_amd_amrres_load_f(len(T["all_octs"][lev]), _vp(T["all_octs"][lev]), _vp(f)))
-    if pfix:
-        check(Lb.ramses_amd_amrres_enable_pfix())
-
-
-def _set_unew(Lb, p, T, pfix):
-    """set_unew on both levels; with pressure_fix: the divu / enew it leaves (host vectors)"""
-    from ramses_amd._capi import check
-    divu, enew = np.zeros(T["ncell"]), np.zeros(T["ncell"])
-    for lev in (L, L + 1):
-        ig = T["all_octs"][lev]
-        if pfix:
-            check(Lb.ramses_amd_amrres_set_unew_pfix(C.byref(p), len(ig), _vp(ig)))
-            check(Lb.ramses_amd_amrres_sync_pfix(len(ig), _vp(ig), _vp(divu), _vp(enew)))
-        else:
-            check(Lb.ramses_amd_amrres_set_unew(len(ig), _vp(ig)))
-    return (divu, enew) if pfix else None
-
-
-def _sweeps(Lb, p, T, interp):
-    """godunov_fine of level L+1 then L; returns (sweeps through the tiles, sweeps through the tree)"""
-    from ramses_amd._capi import check
-    t0, w0 = Lb.ramses_amd_amrres_tile_sweeps(), Lb.ramses_amd_amrres_tree_sweeps()
-    for lev in (L + 1, L):
-        ig = T["lists"][lev]
-        dx = 1.0 / 2 ** lev
-        check(Lb.ramses_amd_amrres_godunov(C.byref(p), lev, len(ig), _vp(ig), dx, 0.02 * dx, 32, interp[0], interp[1]))
-    return Lb.ramses_amd_amrres_tile_sweeps() - t0, Lb.ramses_amd_amrres_tree_sweeps() - w0
-
-
-def _read_back(Lb, p, T, u, pfix):
-    """set_uold and sync of both levels (u: the array the state was loaded from); with pressure_fix divu and enew before it"""
-    from ramses_amd._capi import check
-    divu, enew = np.zeros(T["ncell"]), np.zeros(T["ncell"])
-    for lev in (L, L + 1):
-        ig = T["all_octs"][lev]
-        if pfix:
-            check(Lb.ramses_amd_amrres_sync_pfix(len(ig), _vp(ig), _vp(divu), _vp(enew)))
-        check(Lb.ramses_amd_amrres_set_uold(C.byref(p), len(ig), _vp(ig)))
-        check(Lb.ramses_amd_amrres_sync_level(len(ig), _vp(ig), _vp(u)))
-    return (u, divu, enew) if pfix else (u,)
-
-
 def _case(gpu_lib, oracle, monkeypatch, nvar, riemann, slope, smallr, grav, order, interp, fast=False, scheme="muscl", difmag=0.0,
           pfix=False, walker=False):
     """one amr_step's worth of calls on the harsh state == the oracle's, through the path the case is about"""
@@ -211,11 +143,11 @@ def _case(gpu_lib, oracle, monkeypatch, nvar, riemann, slope, smallr, grav, orde
     ref = _oracle_step(oracle, po, T, uold, f, interp, pfix0)      # before the device is looked at
     u = uold.copy()
     try:
-        _load(gpu_lib, T, u, f, pfix)
+        R.load(gpu_lib, T, u, f, pfix=pfix)
         assert gpu_lib.ramses_amd_amrres_tiled_levels() == 2
-        dev0 = _set_unew(gpu_lib, p, T, pfix)
-        counts = _sweeps(gpu_lib, p, T, interp)
-        got = _read_back(gpu_lib, p, T, u, pfix)
+        dev0 = R.set_unew(gpu_lib, p, T, pfix)
+        counts = R.sweep_levels(gpu_lib, p, T, interp)
+        got = R.read_back(gpu_lib, p, T, u, pfix)
     finally:
         gpu_lib.ramses_amd_amrres_invalidate()
     assert counts == ((0, 2) if walker else (2, 0)), "sweeps through the tiles / through the tree: %d / %d" % counts

@@ -24,13 +24,12 @@ import numpy as np
 import pytest
 
 import helpers as H
+from resident import ALL_LAYOUT_VARS, force_tiles, load, vp
 
 pytestmark = pytest.mark.gpu
 
 GAMMA, FLOOR, CF, BETA = 1.4, 0.6, 0.8, 0.5
 KINDS = ("full", "sub", "none")
-LAYOUT_VARS = ("RAMSES_AMD_DEVICE_ORDER", "RAMSES_AMD_TILES", "RAMSES_AMD_TILE_DENSE", "RAMSES_AMD_COVERED_DENSE", "RAMSES_AMD_TILE_SWEEP",
-               "RAMSES_AMD_DIFMAG_TILES", "RAMSES_AMD_SORTED_LISTS", "RAMSES_AMD_LIST_CACHE")
 # (L, oct order, RAMSES_AMD_DEVICE_ORDER, smallr)
 CASES = [(4, "scrambled", None, 1e-10), (4, "scrambled", None, FLOOR), (4, "morton", None, 1e-10), (4, "morton", None, FLOOR),
          (6, "scrambled", None, 1e-10), (6, "scrambled", None, FLOOR), (6, "scrambled", "0", FLOOR)]
@@ -39,13 +38,7 @@ IDS = ["L%d-%s%s-smallr%g" % (c[0], c[1], "-hostorder" if c[2] == "0" else "", c
 
 @pytest.fixture(autouse=True)
 def _tiles_on_small_levels_too(monkeypatch):
-    monkeypatch.setenv("RAMSES_AMD_TILE_MIN_OCTS", "0")
-    for var in LAYOUT_VARS:
-        monkeypatch.delenv(var, raising=False)
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+    force_tiles(monkeypatch, clear=ALL_LAYOUT_VARS)
 
 
 def _params(oracle, nvar, smallr, smallc=1e-10, **kw):
@@ -56,19 +49,11 @@ def _params(oracle, nvar, smallr, smallc=1e-10, **kw):
 
 def _load(Lb, monkeypatch, T, u, f, device_order, pfix=False):
     """the state (and the acceleration, both levels) onto the device; u is the array every sync_all writes into"""
-    from ramses_amd._capi import check
     if device_order is not None:
         monkeypatch.setenv("RAMSES_AMD_DEVICE_ORDER", device_order)
     L = T["L"]
-    check(Lb.ramses_amd_amrres_invalidate())
-    check(Lb.ramses_amd_amrres_load(u.shape[0], T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
+    load(Lb, T, u, f, levels=[T["lists"][lev]["sorted"] for lev in (L, L + 1)], pfix=pfix)
     assert Lb.ramses_amd_amrres_tiled_levels() == (2 if L >= 6 and device_order != "0" else 0)
-    if f is not None:
-        for lev in (L, L + 1):
-            ig = T["lists"][lev]["sorted"]
-            check(Lb.ramses_amd_amrres_load_f(len(ig), _vp(ig), _vp(f)))
-    if pfix:
-        check(Lb.ramses_amd_amrres_enable_pfix())
 
 
 def _set_unew(Lb, p, T, pfix=False):
@@ -76,21 +61,21 @@ def _set_unew(Lb, p, T, pfix=False):
     for lev in (T["L"], T["L"] + 1):
         ig = T["lists"][lev]["sorted"]
         if pfix:
-            check(Lb.ramses_amd_amrres_set_unew_pfix(C.byref(p), len(ig), _vp(ig)))
+            check(Lb.ramses_amd_amrres_set_unew_pfix(C.byref(p), len(ig), vp(ig)))
         else:
-            check(Lb.ramses_amd_amrres_set_unew(len(ig), _vp(ig)))
+            check(Lb.ramses_amd_amrres_set_unew(len(ig), vp(ig)))
 
 
 def _sync(Lb, T, u, pfix=False):
     """the whole state back into u; with pressure_fix also (divu, enew) of both levels (zero elsewhere)"""
     from ramses_amd._capi import check
-    check(Lb.ramses_amd_amrres_sync_all(_vp(u)))
+    check(Lb.ramses_amd_amrres_sync_all(vp(u)))
     if not pfix:
         return None
     divu, enew = np.zeros(T["ncell"]), np.zeros(T["ncell"])
     for lev in (T["L"], T["L"] + 1):
         ig = T["lists"][lev]["sorted"]
-        check(Lb.ramses_amd_amrres_sync_pfix(len(ig), _vp(ig), _vp(divu), _vp(enew)))
+        check(Lb.ramses_amd_amrres_sync_pfix(len(ig), vp(ig), vp(divu), vp(enew)))
     return divu, enew
 
 
@@ -150,7 +135,7 @@ def test_courant(gpu_lib, oracle, monkeypatch, L, order, device_order, smallr, n
                     if lev == L and kind in ("full", "sub"):
                         assert H.courant_dt_oracle(oracle, po, u0, f, H.oct_cells(T, octs), dx, CF) < want      # the planted cell
                     out = np.full(4, np.nan)
-                    check(gpu_lib.ramses_amd_amrres_courant(C.byref(p), len(octs), _vp(octs), dx, 1e30, _vp(out)))
+                    check(gpu_lib.ramses_amd_amrres_courant(C.byref(p), len(octs), vp(octs), dx, 1e30, vp(out)))
                     what = "level %d, %s list, smallc %g" % (lev, kind, smallc)
                     assert out[0] == want, (what, out[0], want)
                     for k, (name, terms) in enumerate(zip(("mass", "total energy", "internal energy"), H.courant_sum_terms(u0, leaves, dx, smallr))):
@@ -161,7 +146,7 @@ def test_courant(gpu_lib, oracle, monkeypatch, L, order, device_order, smallr, n
                         assert out[0] == CF * dx / smallc and (out[1:] == 0).all(), out
                     # dt_in below the level's own time step comes back
                     out2 = np.full(4, np.nan)
-                    check(gpu_lib.ramses_amd_amrres_courant(C.byref(p), len(octs), _vp(octs), dx, 0.5 * want, _vp(out2)))
+                    check(gpu_lib.ramses_amd_amrres_courant(C.byref(p), len(octs), vp(octs), dx, 0.5 * want, vp(out2)))
                     assert out2[0] == 0.5 * want and np.array_equal(out2[1:], out[1:]), (what, out2, out)
         _sync(gpu_lib, T, u)
         assert np.array_equal(u, u0)
@@ -190,7 +175,7 @@ def test_synchro(gpu_lib, oracle, monkeypatch, L, order, device_order, smallr):
                     want = H.synchro_oracle(oracle, before, f, H.oct_cells(T, octs), dteff, smallr)
                     if kind != "none":
                         assert (want[1:5] != before[1:5]).any(axis=0).sum() == 8 * len(octs)
-                    check(gpu_lib.ramses_amd_amrres_synchro(C.byref(p), len(octs), _vp(octs), dteff))
+                    check(gpu_lib.ramses_amd_amrres_synchro(C.byref(p), len(octs), vp(octs), dteff))
                     _sync(gpu_lib, T, u)
                     _check(T, u, want, before, octs, "synchro of level %d, %s list, dteff %g" % (lev, kind, dteff))
         finally:
@@ -205,7 +190,7 @@ def _device_sweeps(Lb, p, T, interp):
     for lev in (L + 1, L):
         ig = T["lists"][lev]["full"]
         dx = 1.0 / 2 ** lev
-        check(Lb.ramses_amd_amrres_godunov(C.byref(p), lev, len(ig), _vp(ig), dx, 0.02 * dx, 32, interp[0], interp[1]))
+        check(Lb.ramses_amd_amrres_godunov(C.byref(p), lev, len(ig), vp(ig), dx, 0.02 * dx, 32, interp[0], interp[1]))
 
 
 SWEPT_CASES = [(4, "scrambled", None, "llf-floor"), (4, "morton", None, "llf-floor"), (6, "scrambled", None, "llf-floor"),
@@ -233,7 +218,7 @@ def test_set_uold_grav_without_a_sweep(gpu_lib, oracle, monkeypatch, L, order, d
                 want = H.set_uold_grav_expected(oracle, before, u7, f, H.oct_cells(T, octs), dt, smallr)
                 if kind != "none":
                     assert (want[1:5] != before[1:5]).any(axis=0).sum() == 8 * len(octs)
-                check(gpu_lib.ramses_amd_amrres_set_uold_grav(C.byref(p), len(octs), _vp(octs), dt))
+                check(gpu_lib.ramses_amd_amrres_set_uold_grav(C.byref(p), len(octs), vp(octs), dt))
                 _sync(gpu_lib, T, u)
                 _check(T, u, want, before, octs, "set_uold_grav of level %d, %s list" % (lev, kind))
         finally:
@@ -266,7 +251,7 @@ def test_set_uold_grav_after_a_sweep(gpu_lib, oracle, monkeypatch, L, order, dev
                     fixed = int((want[5:, cells] != unfixed[5:]).any(axis=0).sum())
                     print("level %d: cells whose passive scalars set_uold's floor fix changes: %d of %d" % (lev, fixed, len(cells)))
                     assert fixed > (1000 if L >= 6 else 0)
-                check(gpu_lib.ramses_amd_amrres_set_uold_grav(C.byref(p), len(octs), _vp(octs), dt))
+                check(gpu_lib.ramses_amd_amrres_set_uold_grav(C.byref(p), len(octs), vp(octs), dt))
                 _sync(gpu_lib, T, u)
                 _check(T, u, want, before, octs, "set_uold_grav after a sweep, level %d, %s list" % (lev, kind))
         finally:
@@ -294,7 +279,7 @@ def test_upload_fine(gpu_lib, oracle, monkeypatch, L, order, device_order, small
                 octs = T["lists"][lev][kind]
                 before = u.copy()
                 want, split = H.upl_oracle(oracle, T, before, octs, ivar, smallr)
-                check(gpu_lib.ramses_amd_amrres_upload_fine(C.byref(p), len(octs), _vp(octs), ivar))
+                check(gpu_lib.ramses_amd_amrres_upload_fine(C.byref(p), len(octs), vp(octs), ivar))
                 _sync(gpu_lib, T, u)
                 what = "upload_fine of level %d, %s list, interpol_var %d, NVAR %d" % (lev, kind, ivar, nvar)
                 _check(T, u, want, before, octs, what)
@@ -350,7 +335,7 @@ def test_set_uold_pfix_without_a_sweep(gpu_lib, oracle, monkeypatch, L, order, d
                 before = (uold_c.copy(), divu_c.copy(), enew_c.copy())
                 if kind != "none":
                     H.set_uold_pfix_numpy(oracle, T, octs, uold_c, u7, divu_c, enew_c, f, dx, dt, BETA, hexp, GAMMA, smallr)
-                check(gpu_lib.ramses_amd_amrres_set_uold_pfix(C.byref(p), len(octs), _vp(octs), dt, dx, BETA, hexp))
+                check(gpu_lib.ramses_amd_amrres_set_uold_pfix(C.byref(p), len(octs), vp(octs), dt, dx, BETA, hexp))
                 divu, enew = _sync(gpu_lib, T, u, pfix=True)
                 _check_pfix(T, (u, divu, enew), (uold_c, divu_c, enew_c), before, octs, "set_uold_pfix of level %d, %s list" % (lev, kind))
             assert np.array_equal(uold_c, R["uold"]) and np.array_equal(enew_c, R["enew"])
@@ -383,7 +368,7 @@ def test_set_uold_pfix_after_a_sweep(gpu_lib, oracle, monkeypatch, L, order, dev
                 before = (uold_c.copy(), divu_c.copy(), enew_c.copy())
                 if kind != "none":
                     fired.append(H.set_uold_pfix_numpy(oracle, T, octs, uold_c, unew, divu_c, enew_c, f, dx, dt, BETA, 0.0, GAMMA, smallr)["fired"])
-                check(gpu_lib.ramses_amd_amrres_set_uold_pfix(C.byref(p), len(octs), _vp(octs), dt, dx, BETA, 0.0))
+                check(gpu_lib.ramses_amd_amrres_set_uold_pfix(C.byref(p), len(octs), vp(octs), dt, dx, BETA, 0.0))
                 divu, enew = _sync(gpu_lib, T, u, pfix=True)
                 _check_pfix(T, (u, divu, enew), (uold_c, divu_c, enew_c), before, octs,
                             "set_uold_pfix after a sweep, level %d, %s list" % (lev, kind))

@@ -3,24 +3,18 @@ missing #8): defrag renumbers the octs of every level every nremap coarse steps 
 (amr/amr_step.f90:109-118,153-155, amr/load_balance.f90:993-1608).  The shim of load_balance.f90 in the patch directory hands
 the device's levels back to the host arrays before defrag moves them and drops the device image, which the next device
 routine loads again.  Every snapshot of the patched program must equal the reference's, bit for bit."""
-import importlib.util
 import os
 import shutil
 
 import numpy as np
 import pytest
 
+import live
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "ramses3d")
 PATCHED = os.path.join(ROOT, "oracle", "_ref", "ramses3d_patch")
-
-
-def _mkb():
-    spec = importlib.util.spec_from_file_location("mkb", os.path.join(ROOT, "tests", "golden", "make_golden_baseline.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
 
 
 def _leaves(outdir):
@@ -35,7 +29,7 @@ def test_remaps_and_mid_run_snapshots(gpu_lib, monkeypatch, nremap, poisson):
     if not (os.path.exists(REF) and os.path.exists(PATCHED)):
         pytest.skip("oracle/_ref/ramses3d[_patch] not built")
     from oracle import ramses_snapshot as rs
-    mkb = _mkb()
+    mkb = live.golden_module("baseline")
     if poisson:
         nml = mkb.amr_grav_namelist(lmin=5, lmax=7, nstep=6, foutput=3)
     else:

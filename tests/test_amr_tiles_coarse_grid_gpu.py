@@ -14,6 +14,9 @@ import functools
 import numpy as np
 import pytest
 
+from helpers import oct_cells
+from resident import force_tiles, reset_library, vp
+
 pytestmark = pytest.mark.gpu
 
 L = 6
@@ -25,14 +28,10 @@ MODES = ["tiles", "z_order", "host_order"]
 def _switches(monkeypatch):
     """the dense sweep on small levels too; the grid back to one cell afterwards (the setting holds for every later load of the
     process)"""
-    monkeypatch.setenv("RAMSES_AMD_TILE_MIN_OCTS", "0")
-    for var in ("RAMSES_AMD_COARSE_GRID_TILES", "RAMSES_AMD_DEVICE_ORDER", "RAMSES_AMD_TILES", "RAMSES_AMD_TILE_DENSE", "RAMSES_AMD_COVERED_DENSE", "RAMSES_AMD_DEVICE_OCTS"):
-        monkeypatch.delenv(var, raising=False)
+    force_tiles(monkeypatch, clear=("RAMSES_AMD_COARSE_GRID_TILES", "RAMSES_AMD_DEVICE_ORDER", "RAMSES_AMD_TILES", "RAMSES_AMD_TILE_DENSE",
+                                    "RAMSES_AMD_COVERED_DENSE", "RAMSES_AMD_DEVICE_OCTS"))
     yield
-    import ramses_amd
-    lib = ramses_amd.lib()
-    lib.ramses_amd_amrres_invalidate()
-    lib.ramses_amd_amrres_coarse_grid(1, 1, 1)
+    reset_library()
 
 
 def _mode(monkeypatch, mode):
@@ -40,10 +39,6 @@ def _mode(monkeypatch, mode):
         monkeypatch.setenv("RAMSES_AMD_TILES", "0")
     if mode == "host_order":
         monkeypatch.setenv("RAMSES_AMD_DEVICE_ORDER", "0")
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def _box(mask, xr, yr, zr):
@@ -120,11 +115,9 @@ def _case(grid, active_cell, mask, order, slack=300000):
     return T
 
 
-def _cells(T, octs):
-    return np.concatenate([T["ncoarse"] + ind * T["ngridmax"] + np.asarray(octs, np.int64) - 1 for ind in range(8)])
-
-
 def _random_state(T, seed, nvar=5):
+    """(not helpers.mild_tree_state: this one draws a value for cell 0 as well, which shifts every later draw; the cases of this file
+    were validated on these states)"""
     rng = np.random.default_rng(seed)
     ncell = T["ncell"]
     u = np.zeros((nvar, ncell))
@@ -149,24 +142,24 @@ def _device_step(Lb, p, T, u, f, lists, ivar=0, itype=1, load=True):
     if load:
         check(Lb.ramses_amd_amrres_invalidate())
         check(Lb.ramses_amd_amrres_coarse_grid(*T["grid"]))
-        check(Lb.ramses_amd_amrres_load(u.shape[0], T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
+        check(Lb.ramses_amd_amrres_load(u.shape[0], T["ngridmax"], T["ncoarse"], vp(u), vp(T["son"]), vp(T["nbor"]), vp(T["father"])))
         if f is not None:
             for lev in (L, L + 1):           # (the boundary octs' too: a ghost oct beyond a wall takes its father cell's)
                 ig = T["everything"][lev]
-                check(Lb.ramses_amd_amrres_load_f(len(ig), _vp(ig), _vp(f)))
+                check(Lb.ramses_amd_amrres_load_f(len(ig), vp(ig), vp(f)))
     for lev in (L, L + 1):
         ig = T["active"][lev]
-        check(Lb.ramses_amd_amrres_set_unew(len(ig), _vp(ig)))
+        check(Lb.ramses_amd_amrres_set_unew(len(ig), vp(ig)))
     for lev in (L + 1, L):
         ig = np.ascontiguousarray(lists[lev])
         dx = 1.0 / 2 ** lev
-        check(Lb.ramses_amd_amrres_godunov(C.byref(p), lev, len(ig), _vp(ig), dx, 0.02 * dx, 32, ivar, itype))
+        check(Lb.ramses_amd_amrres_godunov(C.byref(p), lev, len(ig), vp(ig), dx, 0.02 * dx, 32, ivar, itype))
     for lev in (L, L + 1):
         ig = T["active"][lev]
-        check(Lb.ramses_amd_amrres_set_uold(C.byref(p), len(ig), _vp(ig)))
+        check(Lb.ramses_amd_amrres_set_uold(C.byref(p), len(ig), vp(ig)))
     for lev in (L, L + 1):
         ig = T["everything"][lev]
-        check(Lb.ramses_amd_amrres_sync_level(len(ig), _vp(ig), _vp(u)))
+        check(Lb.ramses_amd_amrres_sync_level(len(ig), vp(ig), vp(u)))
     return u
 
 
@@ -235,17 +228,17 @@ def test_levels_of_a_multi_cell_coarse_grid_equal_the_oracle(gpu_lib, monkeypatc
     else:
         assert gpu_lib.ramses_amd_amrres_tiled_levels() == 0 and (dt, dw) == (0, 2)
     assert gpu_lib.ramses_amd_amrres_first_changed() == (0 if mode == "host_order" else 1)
-    cells = _cells(T, np.concatenate([lists[L], lists[L + 1]]))
+    cells = oct_cells(T, np.concatenate([lists[L], lists[L + 1]]))
     assert np.array_equal(got[:, cells].view(np.int64), ref[:, cells].view(np.int64)), np.abs(got[:, cells] - ref[:, cells]).max()
     assert (ref[:, cells] != uold[:, cells]).any(0).mean() > 0.9
     if len(T["boundary_octs"]):
-        b = _cells(T, T["boundary_octs"])
+        b = oct_cells(T, T["boundary_octs"])
         assert np.array_equal(got[:, b].view(np.int64), uold[:, b].view(np.int64))
     # (active octs that are not in the call's list: set_unew / set_uold leave them as they were)
     rest = np.setdiff1d(np.concatenate([T["active"][L], T["active"][L + 1]]), np.concatenate([lists[L], lists[L + 1]]))
     if len(rest):
         # ... except for what a listed level-7 oct owes to a leaf cell of level 6 (hydro/godunov_fine.f90:798-908): the oracle's unew
-        r = _cells(T, rest)
+        r = oct_cells(T, rest)
         assert np.array_equal(got[:, r].view(np.int64), ref[:, r].view(np.int64))
 
 
@@ -256,16 +249,16 @@ def test_load_refuses_an_ncoarse_that_is_not_the_grid(gpu_lib):
     uold = _random_state(T, 3)
     check(gpu_lib.ramses_amd_amrres_invalidate())
     check(gpu_lib.ramses_amd_amrres_coarse_grid(2, 1, 1))
-    rc = gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], _vp(uold), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"]))
+    rc = gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], vp(uold), vp(T["son"]), vp(T["nbor"]), vp(T["father"]))
     assert rc != 0 and b"coarse grid 2 x 1 x 1" in gpu_lib.ramses_amd_last_error()
     assert gpu_lib.ramses_amd_amrres_coarse_grid(0, 1, 1) != 0 and b"coarse_grid" in gpu_lib.ramses_amd_last_error()
     # the right grid: the device's own numbering is in force (levels 1 and 2: Z-order, nothing to store in tiles)
     check(gpu_lib.ramses_amd_amrres_coarse_grid(3, 1, 1))
-    check(gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], _vp(uold), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
+    check(gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], vp(uold), vp(T["son"]), vp(T["nbor"]), vp(T["father"])))
     assert gpu_lib.ramses_amd_amrres_first_changed() == 1 and gpu_lib.ramses_amd_amrres_tiled_levels() == 0
     back = np.zeros_like(uold)
     back[:] = uold
-    check(gpu_lib.ramses_amd_amrres_sync_all(_vp(uold)))
+    check(gpu_lib.ramses_amd_amrres_sync_all(vp(uold)))
     assert np.array_equal(uold, back)
 
 
@@ -285,7 +278,7 @@ def test_a_regrid_of_level_7_keeps_the_layout_of_level_6(gpu_lib, oracle, monkey
     u0 = _random_state(T1, 19)
     h1 = _oracle_step(oracle, po, T1, u0, None, T1["active"])
     # (the oracle's unew -> uold on the active octs only, as set_uold does: boundary octs keep their uold)
-    a1 = _cells(T1, np.concatenate([T1["active"][L], T1["active"][L + 1]]))
+    a1 = oct_cells(T1, np.concatenate([T1["active"][L], T1["active"][L + 1]]))
     s1 = u0.copy()
     s1[:, a1] = h1[:, a1]
 
@@ -302,17 +295,17 @@ def test_a_regrid_of_level_7_keeps_the_layout_of_level_6(gpu_lib, oracle, monkey
     u = _device_step(gpu_lib, p, T1, u0.copy(), None, T1["active"])
     assert gpu_lib.ramses_amd_amrres_tiled_levels() == 2
     u[:] = refill(u)
-    c6 = _cells(T2, T2["everything"][L])
+    c6 = oct_cells(T2, T2["everything"][L])
     u[:, c6] = -7.0                      # if the device read level 6 from the host again, the result would show it
-    check(gpu_lib.ramses_amd_amrres_tree(_vp(T2["son"]), _vp(T2["nbor"]), _vp(T2["father"])))
+    check(gpu_lib.ramses_amd_amrres_tree(vp(T2["son"]), vp(T2["nbor"]), vp(T2["father"])))
     assert gpu_lib.ramses_amd_amrres_first_changed() == L + 1
     igf = T2["everything"][L + 1]
-    check(gpu_lib.ramses_amd_amrres_load_level(len(igf), _vp(igf), _vp(u)))
+    check(gpu_lib.ramses_amd_amrres_load_level(len(igf), vp(igf), vp(u)))
     t0, w0 = gpu_lib.ramses_amd_amrres_tile_sweeps(), gpu_lib.ramses_amd_amrres_tree_sweeps()
     got = _device_step(gpu_lib, p, T2, u, None, T2["active"], load=False)
     assert gpu_lib.ramses_amd_amrres_tile_sweeps() - t0 == 2 and gpu_lib.ramses_amd_amrres_tree_sweeps() == w0
-    cells = _cells(T2, np.concatenate([T2["active"][L], T2["active"][L + 1]]))
+    cells = oct_cells(T2, np.concatenate([T2["active"][L], T2["active"][L + 1]]))
     assert np.array_equal(got[:, cells].view(np.int64), h2[:, cells].view(np.int64)), np.abs(got[:, cells] - h2[:, cells]).max()
     assert (h2[:, cells] != s1r[:, cells]).any(0).mean() > 0.9
-    b6 = _cells(T2, T2["igrid"][T2["is_boundary"][T2["igrid"]]])
+    b6 = oct_cells(T2, T2["igrid"][T2["is_boundary"][T2["igrid"]]])
     assert np.array_equal(got[:, b6].view(np.int64), u0[:, b6].view(np.int64))        # level 6's boundary octs: as loaded, through both steps

@@ -9,40 +9,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import live
+import resident as R
+from helpers import mild_tree_state, shell_mask
+from resident import vp
+
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(autouse=True)
 def _dense_sweep_on_small_levels_too(monkeypatch):
-    """(levels below RAMSES_AMD_TILE_MIN_OCTS octs take the tree-walking sweep in production: the tests force the tiles)"""
-    monkeypatch.setenv("RAMSES_AMD_TILE_MIN_OCTS", "0")
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _shell_mask(nc, lo=0.23, hi=0.36, seam=True):
-    z, y, x = np.meshgrid(np.arange(nc), np.arange(nc), np.arange(nc), indexing="ij")
-    r = np.sqrt((x - nc / 2 + 0.5) ** 2 + (y - nc / 2 + 0.5) ** 2 + (z - nc / 2 + 0.5) ** 2)
-    mask = (r >= lo * nc) & (r <= hi * nc)
-    if seam:
-        mask[0, 0, :5] = True              # refined cells on the periodic seam too (tiles wrap)
-        mask[nc - 1, nc - 1, nc - 3:] = True
-    return mask
-
-
-def _random_state(T, seed, nvar=5):
-    rng = np.random.default_rng(seed)
-    ncell = T["ncell"]
-    uold = np.zeros((nvar, ncell))
-    n = ncell - 1
-    uold[0, 1:] = 1.0 + rng.random(n)
-    for d in (1, 2, 3):
-        uold[d, 1:] = uold[0, 1:] * (rng.random(n) - 0.5)
-    uold[4, 1:] = 1.0 + rng.random(n) + 0.5 * (uold[1, 1:] ** 2 + uold[2, 1:] ** 2 + uold[3, 1:] ** 2) / uold[0, 1:]
-    uold[:, 0] = uold[:, 1]
-    return uold
+    R.force_tiles(monkeypatch, clear=())
 
 
 def _oracle_step(oracle, po, T, L, uold, f, lists, ivar=0, itype=1):
@@ -58,31 +35,19 @@ def _oracle_step(oracle, po, T, L, uold, f, lists, ivar=0, itype=1):
 def _device_step(Lb, p, T, L, u, f, lists, ivar=0, itype=1, load=True):
     from ramses_amd._capi import check
     if load:
-        check(Lb.ramses_amd_amrres_invalidate())
-        check(Lb.ramses_amd_amrres_load(u.shape[0], T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
-        if f is not None:
-            for lev in (L, L + 1):
-                ig = np.ascontiguousarray(T["all_octs"][lev])
-                check(Lb.ramses_amd_amrres_load_f(len(ig), _vp(ig), _vp(f)))
+        R.load(Lb, T, u, f)
     for lev in (L, L + 1):
         ig = np.ascontiguousarray(T["all_octs"][lev])
-        check(Lb.ramses_amd_amrres_set_unew(len(ig), _vp(ig)))
+        check(Lb.ramses_amd_amrres_set_unew(len(ig), vp(ig)))
     for lev in (L + 1, L):
         ig = np.ascontiguousarray(lists[lev])
         dx = 1.0 / 2 ** lev
-        check(Lb.ramses_amd_amrres_godunov(C.byref(p), lev, len(ig), _vp(ig), dx, 0.02 * dx, 32, ivar, itype))
+        check(Lb.ramses_amd_amrres_godunov(C.byref(p), lev, len(ig), vp(ig), dx, 0.02 * dx, 32, ivar, itype))
     for lev in (L, L + 1):
         ig = np.ascontiguousarray(T["all_octs"][lev])
-        check(Lb.ramses_amd_amrres_set_uold(C.byref(p), len(ig), _vp(ig)))
-        check(Lb.ramses_amd_amrres_sync_level(len(ig), _vp(ig), _vp(u)))
+        check(Lb.ramses_amd_amrres_set_uold(C.byref(p), len(ig), vp(ig)))
+        check(Lb.ramses_amd_amrres_sync_level(len(ig), vp(ig), vp(u)))
     return u
-
-
-def _tree(L, mask, order, slack):
-    from ramses_amd import ic
-    T = ic.uniform_tree(L, order=order, refine_mask=mask, slack=slack)
-    T["all_octs"] = {L: np.sort(T["igrid"]), L + 1: np.sort(T["igrid_fine"])}
-    return T
 
 
 @pytest.mark.parametrize("order,riemann,slope,grav,interp", [("morton", "llf", 1, False, (0, 1)), ("scrambled", "hllc", 2, True, (1, 2)),
@@ -92,9 +57,9 @@ def test_levels_in_tiles_equal_the_oracle(gpu_lib, oracle, monkeypatch, order, r
     slots: ghost octs on both surfaces, fluxes owed to level-6 leaf cells): one amr_step's worth of calls == the oracle"""
     import ramses_amd
     L = 6
-    mask = _shell_mask(2 ** L)
-    T = _tree(L, mask, order, slack=260000)
-    uold = _random_state(T, 11)
+    mask = shell_mask(2 ** L)
+    T = R.two_level_tree(L, order, mask, slack=260000)
+    uold = mild_tree_state(T, 11)
     rng = np.random.default_rng(5)
     f = rng.normal(size=(3, T["ncell"])) if grav else None
     kw = dict(riemann=riemann, slope_type=slope)
@@ -127,9 +92,9 @@ def test_passive_scalars_and_the_newton_solver_on_tiles(gpu_lib, oracle, monkeyp
     tree; fast arithmetic: <= 1e-12."""
     import ramses_amd
     L = 6
-    mask = _shell_mask(2 ** L)
-    T = _tree(L, mask, "scrambled", slack=260000)
-    uold = _random_state(T, 17, nvar=nvar)
+    mask = shell_mask(2 ** L)
+    T = R.two_level_tree(L, "scrambled", mask, slack=260000)
+    uold = mild_tree_state(T, 17, nvar=nvar)
     rng = np.random.default_rng(23)
     for n in range(5, nvar):
         uold[n, 1:] = uold[0, 1:] * rng.random(T["ncell"] - 1)          # passive scalars: density x a fraction in [0, 1)
@@ -163,9 +128,9 @@ def test_every_numbering_gives_the_same_result(gpu_lib, oracle, monkeypatch, mod
     partial level falls back to Z-order and the tree-walking sweep), tiles with the tree-walking sweep -- all == the oracle"""
     import ramses_amd
     L = 6
-    mask = _shell_mask(2 ** L, seam=False)
-    T = _tree(L, mask, "scrambled", slack=7 if mode == "no_room" else 260000)
-    uold = _random_state(T, 13)
+    mask = shell_mask(2 ** L, seam=False)
+    T = R.two_level_tree(L, "scrambled", mask, slack=7 if mode == "no_room" else 260000)
+    uold = mild_tree_state(T, 13)
     p, po = ramses_amd.make_params(riemann="llf", slope_type=1), oracle.make_params(riemann="llf", slope_type=1)
     lists = {L: T["igrid"], L + 1: T["igrid_fine"]}
     ref = _oracle_step(oracle, po, T, L, uold, None, lists)
@@ -194,9 +159,9 @@ def test_a_list_that_is_part_of_the_level(gpu_lib, oracle, monkeypatch):
     import ramses_amd
     L = 6
     nc = 2 ** L
-    mask = _shell_mask(nc)
-    T = _tree(L, mask, "scrambled", slack=260000)
-    uold = _random_state(T, 17)
+    mask = shell_mask(nc)
+    T = R.two_level_tree(L, "scrambled", mask, slack=260000)
+    uold = mild_tree_state(T, 17)
     p, po = ramses_amd.make_params(riemann="hllc", slope_type=1), oracle.make_params(riemann="hllc", slope_type=1)
     # own = a fixed subset of each level (by the index of the father cell): the oracle sees the same lists
     fcL, fcF = T["father"][T["igrid"] - 1].astype(np.int64), T["father"][T["igrid_fine"] - 1].astype(np.int64)
@@ -221,16 +186,16 @@ def test_a_regrid_keeps_the_levels_that_did_not_change(gpu_lib, oracle, monkeypa
     from ramses_amd._capi import check
     L = 6
     nc = 2 ** L
-    m1 = _shell_mask(nc, 0.23, 0.36)
-    m2 = _shell_mask(nc, 0.15, 0.30, seam=False)
+    m1 = shell_mask(nc, 0.23, 0.36)
+    m2 = shell_mask(nc, 0.15, 0.30, seam=False)
     n1, n2 = int(m1.sum()), int(m2.sum())
-    T1 = _tree(L, m1, "morton", slack=260000 + max(n1, n2) - n1)
-    T2 = _tree(L, m2, "morton", slack=260000 + max(n1, n2) - n2)
+    T1 = R.two_level_tree(L, "morton", m1, slack=260000 + max(n1, n2) - n1)
+    T2 = R.two_level_tree(L, "morton", m2, slack=260000 + max(n1, n2) - n2)
     assert T1["ngridmax"] == T2["ngridmax"] and np.array_equal(T1["igrid"], T2["igrid"])
     p, po = ramses_amd.make_params(riemann="llf", slope_type=2), oracle.make_params(riemann="llf", slope_type=2)
     for var in ("RAMSES_AMD_DEVICE_ORDER", "RAMSES_AMD_TILES", "RAMSES_AMD_TILE_DENSE", "RAMSES_AMD_COVERED_DENSE"):
         monkeypatch.delenv(var, raising=False)
-    u0 = _random_state(T1, 19)
+    u0 = mild_tree_state(T1, 19)
     # oracle: step 1 on tree 1; the new finer octs take their father cell's state (times a factor per octant); step 2 on tree 2
     l1 = {L: T1["igrid"], L + 1: T1["igrid_fine"]}
     l2 = {L: T2["igrid"], L + 1: T2["igrid_fine"]}
@@ -250,10 +215,10 @@ def test_a_regrid_keeps_the_levels_that_did_not_change(gpu_lib, oracle, monkeypa
     u[:] = refill(u)                     # (the same host array all along: the one the state was loaded from)
     c_l = np.concatenate([T2["ncoarse"] + ind * T2["ngridmax"] + T2["igrid"] - 1 for ind in range(8)])
     u[:, c_l] = -7.0                     # if the device read level L from the host again, the result would show it
-    check(gpu_lib.ramses_amd_amrres_tree(_vp(T2["son"]), _vp(T2["nbor"]), _vp(T2["father"])))
+    check(gpu_lib.ramses_amd_amrres_tree(vp(T2["son"]), vp(T2["nbor"]), vp(T2["father"])))
     assert gpu_lib.ramses_amd_amrres_first_changed() == L + 1      # what the caller has to send again: level L + 1, nothing coarser
     igf = np.ascontiguousarray(np.sort(T2["igrid_fine"]))
-    check(gpu_lib.ramses_amd_amrres_load_level(len(igf), _vp(igf), _vp(u)))
+    check(gpu_lib.ramses_amd_amrres_load_level(len(igf), vp(igf), vp(u)))
     t0 = gpu_lib.ramses_amd_amrres_tile_sweeps()
     got = _device_step(gpu_lib, p, T2, L, u, None, l2, load=False)
     assert gpu_lib.ramses_amd_amrres_tile_sweeps() - t0 == 2
@@ -267,22 +232,22 @@ def test_flagged_cells_come_back_in_host_numbers(gpu_lib, monkeypatch):
     import ramses_amd
     from ramses_amd._capi import check
     L = 6
-    T = _tree(L, _shell_mask(2 ** L, seam=False), "scrambled", slack=260000)
-    u = _random_state(T, 23)
+    T = R.two_level_tree(L, "scrambled", shell_mask(2 ** L, seam=False), slack=260000)
+    u = mild_tree_state(T, 23)
     p = ramses_amd.make_params()
     out = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("RAMSES_AMD_DEVICE_ORDER", mode)
         check(gpu_lib.ramses_amd_amrres_invalidate())
-        check(gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
+        check(gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], vp(u), vp(T["son"]), vp(T["nbor"]), vp(T["father"])))
         ig = np.ascontiguousarray(T["igrid_fine"])
         cells = np.zeros(8 * len(ig), np.int32)
         n = C.c_int(0)
-        check(gpu_lib.ramses_amd_amrres_hydro_flag(C.byref(p), len(ig), _vp(ig), 0.3, -1.0, -1.0, 1e-10, 1e-10, 1e-10, _vp(cells), C.byref(n)))
+        check(gpu_lib.ramses_amd_amrres_hydro_flag(C.byref(p), len(ig), vp(ig), 0.3, -1.0, -1.0, 1e-10, 1e-10, 1e-10, vp(cells), C.byref(n)))
         out[mode] = cells[:n.value].copy()
         v = np.zeros_like(u)
         v[:] = u
-        check(gpu_lib.ramses_amd_amrres_sync_all(_vp(u)))
+        check(gpu_lib.ramses_amd_amrres_sync_all(vp(u)))
         assert np.array_equal(u, v)
     assert len(out["0"]) > 100 and np.array_equal(out["0"], out["1"])
     gpu_lib.ramses_amd_amrres_invalidate()
@@ -331,13 +296,13 @@ def test_a_regrid_whose_finer_level_outgrows_the_room_the_kept_tiles_left(gpu_li
     def device_step(T, u):
         ll = lists(T)
         for lev in levels:
-            check(gpu_lib.ramses_amd_amrres_set_unew(len(ll[lev]), _vp(ll[lev])))
+            check(gpu_lib.ramses_amd_amrres_set_unew(len(ll[lev]), vp(ll[lev])))
         for lev in reversed(levels):
             dx = 1.0 / 2 ** lev
-            check(gpu_lib.ramses_amd_amrres_godunov(C.byref(p), lev, len(ll[lev]), _vp(ll[lev]), dx, 0.02 * dx, 32, 0, 1))
+            check(gpu_lib.ramses_amd_amrres_godunov(C.byref(p), lev, len(ll[lev]), vp(ll[lev]), dx, 0.02 * dx, 32, 0, 1))
         for lev in levels:
-            check(gpu_lib.ramses_amd_amrres_set_uold(C.byref(p), len(ll[lev]), _vp(ll[lev])))
-            check(gpu_lib.ramses_amd_amrres_sync_level(len(ll[lev]), _vp(ll[lev]), _vp(u)))
+            check(gpu_lib.ramses_amd_amrres_set_uold(C.byref(p), len(ll[lev]), vp(ll[lev])))
+            check(gpu_lib.ramses_amd_amrres_sync_level(len(ll[lev]), vp(ll[lev]), vp(u)))
         return u
 
     def refill(T, u):
@@ -347,12 +312,12 @@ def test_a_regrid_whose_finer_level_outgrows_the_room_the_kept_tiles_left(gpu_li
             c = T["ncoarse"] + ind * T["ngridmax"] + ig - 1
             v[:, c] = u[:, T["father"][ig - 1] - 1] * (1.0 + 0.01 * (ind - 3.5))
         return v
-    u0 = _random_state(T1, 29)
+    u0 = mild_tree_state(T1, 29)
     h1 = oracle_step(T1, u0)
     h2 = oracle_step(T2, refill(T2, h1))
     u = u0.copy()
     check(gpu_lib.ramses_amd_amrres_invalidate())
-    check(gpu_lib.ramses_amd_amrres_load(5, T1["ngridmax"], T1["ncoarse"], _vp(u), _vp(T1["son"]), _vp(T1["nbor"]), _vp(T1["father"])))
+    check(gpu_lib.ramses_amd_amrres_load(5, T1["ngridmax"], T1["ncoarse"], vp(u), vp(T1["son"]), vp(T1["nbor"]), vp(T1["father"])))
     assert gpu_lib.ramses_amd_amrres_tiled_levels() >= 2          # level 6 and the shell of level 7 live in tiles
     u = device_step(T1, u)
     u[:] = refill(T2, u)
@@ -360,10 +325,10 @@ def test_a_regrid_whose_finer_level_outgrows_the_room_the_kept_tiles_left(gpu_li
         c = np.concatenate([T2["ncoarse"] + ind * T2["ngridmax"] + ig - 1 for ind in range(8)])
         u[:, c] = -7.0                     # if the device read these levels from the host again, the result would show it
     before = gpu_lib.ramses_amd_amrres_relayouts()
-    check(gpu_lib.ramses_amd_amrres_tree(_vp(T2["son"]), _vp(T2["nbor"]), _vp(T2["father"])))
+    check(gpu_lib.ramses_amd_amrres_tree(vp(T2["son"]), vp(T2["nbor"]), vp(T2["father"])))
     assert gpu_lib.ramses_amd_amrres_relayouts() - before == 1
     ig8 = lists(T2)[L + 2]
-    check(gpu_lib.ramses_amd_amrres_load_level(len(ig8), _vp(ig8), _vp(u)))
+    check(gpu_lib.ramses_amd_amrres_load_level(len(ig8), vp(ig8), vp(u)))
     got = device_step(T2, u)
     cells = np.concatenate([T2["ncoarse"] + ind * T2["ngridmax"] + np.concatenate([T2["igrid"], T2["igrid_fine"], T2["igrid_fine2"]]) - 1 for ind in range(8)])
     assert np.array_equal(got[:, cells], h2[:, cells]), np.abs(got[:, cells] - h2[:, cells]).max()
@@ -375,43 +340,32 @@ def test_patched_program_with_passive_scalars_sweeps_its_levels_in_tiles(gpu_lib
     small levels of the test) against the untouched NVAR = 7 reference (oracle/_ref/ramses3d_v7) on a point explosion next to a
     dense block carrying two scalars, levels 6-7, sub-cycling, regrids -- leaf cell by leaf cell, all seven variables bit for
     bit, and no sweep of a level through the tree (the exit line of RAMSES_AMD_STATS=1)."""
-    import importlib.util
     import os
-    import re
     import shutil
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     patched, ref = (os.path.join(root, "oracle", "_ref", b) for b in ("ramses3d_patch_v7", "ramses3d_v7"))
     if not (os.path.exists(patched) and os.path.exists(ref)):
         pytest.skip("oracle/_ref/ramses3d[_patch]_v7 not built")
     from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mka", os.path.join(root, "tests", "golden", "make_golden_amr.py"))
-    mka = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mka)
-    nml = mka.v7_namelist().replace("levelmin=3", "levelmin=6").replace("levelmax=5", "levelmax=7").replace("ngridtot=8000 !", "ngridtot=400000 !")
+    nml = live.golden_module("amr").v7_namelist().replace("levelmin=3", "levelmin=6").replace("levelmax=5", "levelmax=7").replace("ngridtot=8000 !", "ngridtot=400000 !")
     nml = nml.replace("nsubcycle=1,1,2,2", "nsubcycle=1,1,1,1,1,2,2")
     assert "levelmin=6" in nml and "levelmax=7" in nml and "ngridtot=400000" in nml
-
-    def leaves(work):
-        snap = rs.load_leaf_cells(os.path.join(work, "output_00002"))
-        order = np.lexsort((snap["x"][:, 0], snap["x"][:, 1], snap["x"][:, 2], snap["level"]))
-        return snap["level"][order], snap["prim"][:, order]
 
     for k, v in (("RAMSES_AMD", "1"), ("RAMSES_AMD_STRICT", "1"), ("RAMSES_AMD_STATS", "1"), ("RAMSES_AMD_TILE_MIN_OCTS", "0")):
         monkeypatch.setenv(k, v)
     work, out = rs.run_reference(nml, binary=patched)
     try:
-        got = leaves(work)
+        got = live.leaves(work)
     finally:
         shutil.rmtree(work, ignore_errors=True)
-    m = re.search(r"godunov_fine of AMR levels:\s*(\d+) sweeps through the dense kernel on tiles.*?(\d+) through the tree-walking kernel", out)
-    assert m, out[-2000:]
-    assert int(m.group(1)) >= 10 and int(m.group(2)) == 0, m.group(0)
+    tiles, tree = live.sweep_counts(out)
+    assert tiles >= 10 and tree == 0, (tiles, tree)
     monkeypatch.setenv("RAMSES_AMD", "0")
     work, _ = rs.run_reference(nml, binary=ref)
     try:
-        want = leaves(work)
+        want = live.leaves(work)
     finally:
         shutil.rmtree(work, ignore_errors=True)
-    assert got[1].shape[0] == 7 and (want[0] == 7).sum() > 1000
-    assert np.array_equal(got[0], want[0])
-    assert np.array_equal(got[1], want[1]), np.abs(got[1] - want[1]).max()
+    assert got.prim.shape[0] == 7 and (want.level == 7).sum() > 1000
+    assert np.array_equal(got.level, want.level)
+    assert np.array_equal(got.prim, want.prim), np.abs(got.prim - want.prim).max()

@@ -13,7 +13,8 @@ import os
 import numpy as np
 import pytest
 
-from test_amr_tiles_gpu import _shell_mask
+from helpers import shell_mask
+from resident import bits, load, vp
 
 pytestmark = pytest.mark.gpu
 
@@ -22,21 +23,13 @@ LAYOUT_VARS = ("RAMSES_AMD_DEVICE_ORDER", "RAMSES_AMD_TILES", "RAMSES_AMD_DEVICE
 GOLD_AMR = os.path.join(os.path.dirname(__file__), "golden", "rho_fine_amr_ref.npz")
 
 
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
-
-
 @functools.lru_cache(maxsize=None)
 def _tree(layout):
     """tiles: level 6 complete, level 7 a shell with octs on the periodic seam (the tile tests' tree, the smallest on which a level
     is stored in tiles); host: levels 1-3 complete and a small box of level-4 octs.  Never modified by a test."""
     from ramses_amd import ic
     if layout == "tiles":
-        T = ic.uniform_tree(6, order="scrambled", refine_mask=_shell_mask(64), slack=260000)
+        T = ic.uniform_tree(6, order="scrambled", refine_mask=shell_mask(64), slack=260000)
     else:
         T = ic.uniform_tree(3, refine_box=((2, 5), (1, 4), (3, 6)))
     T["lists"] = (np.ascontiguousarray(T["igrid"]), np.ascontiguousarray(T["igrid_fine"]))
@@ -60,15 +53,13 @@ def _set_layout(monkeypatch, layout):
 
 
 def _load(L, T, u, layout):
-    from ramses_amd._capi import check
-    check(L.ramses_amd_amrres_invalidate())
-    check(L.ramses_amd_amrres_load(u.shape[0], T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
+    load(L, T, u)
     assert L.ramses_amd_amrres_tiled_levels() == (2 if layout == "tiles" else 0)
 
 
 def _f_traffic(L):
     t = np.zeros(2, np.int64)
-    assert L.ramses_amd_amrres_f_traffic(_vp(t)) == 0
+    assert L.ramses_amd_amrres_f_traffic(vp(t)) == 0
     return t
 
 
@@ -91,31 +82,31 @@ def test_uold_of_a_level_goes_home_and_comes_back(gpu_lib, monkeypatch, layout):
             u[:, c] = POISON
             want = u.copy()
             want[:, c] = u0[:, c]
-            check(L.ramses_amd_amrres_sync_level(len(ig), _vp(ig), _vp(u)))
-            assert np.array_equal(_bits(u), _bits(want))
+            check(L.ramses_amd_amrres_sync_level(len(ig), vp(ig), vp(u)))
+            assert np.array_equal(bits(u), bits(want))
         # ... refused for another array than the loaded one (the error it returns today)
         other = u.copy()
         ig = T["lists"][1]
-        assert L.ramses_amd_amrres_sync_level(len(ig), _vp(ig), _vp(other)) == -1
+        assert L.ramses_amd_amrres_sync_level(len(ig), vp(ig), vp(other)) == -1
         assert b"sync_level: not the array the state was loaded from" in L.ramses_amd_last_error()
-        assert np.array_equal(_bits(other), _bits(u))
+        assert np.array_equal(bits(other), bits(u))
         # sync_density: variable 0 of the listed cells, nothing else
         for ig in T["lists"]:
             c = _cells(T, ig)
             u[:, c] = POISON
             want = u.copy()
             want[0, c] = u0[0, c]
-            check(L.ramses_amd_amrres_sync_density(len(ig), _vp(ig), _vp(u)))
-            assert np.array_equal(_bits(u), _bits(want))
+            check(L.ramses_amd_amrres_sync_density(len(ig), vp(ig), vp(u)))
+            assert np.array_equal(bits(u), bits(want))
         # load_level of new values for one level, then the whole state back
         ig = T["lists"][1]
         c = _cells(T, ig)
         u1 = u0.copy()
         u1[:, c] = rng.normal(size=(nvar, len(c)))
         u[:] = u1
-        check(L.ramses_amd_amrres_load_level(len(ig), _vp(ig), _vp(u)))
+        check(L.ramses_amd_amrres_load_level(len(ig), vp(ig), vp(u)))
         u[:] = POISON
-        check(L.ramses_amd_amrres_sync_all(_vp(u)))
+        check(L.ramses_amd_amrres_sync_all(vp(u)))
         if layout == "tiles":
             # the coarse cell and the cells of the tree's octs; the cells of oct indices outside the tree keep what the host holds
             want = np.full((nvar, ncell), POISON)
@@ -123,7 +114,7 @@ def test_uold_of_a_level_goes_home_and_comes_back(gpu_lib, monkeypatch, layout):
             want[:, tc] = u1[:, tc]
         else:
             want = u1            # (the host's numbering: the device vector IS the host's, it comes back whole)
-        assert np.array_equal(_bits(u), _bits(want))
+        assert np.array_equal(bits(u), bits(want))
     finally:
         check(L.ramses_amd_amrres_invalidate())
 
@@ -144,23 +135,23 @@ def test_the_acceleration_of_a_level_goes_down_and_comes_home(gpu_lib, monkeypat
         listed = np.zeros(ncell, bool)
         for ig in T["lists"]:
             t0 = _f_traffic(L)
-            check(L.ramses_amd_amrres_load_f(len(ig), _vp(ig), _vp(f)))
+            check(L.ramses_amd_amrres_load_f(len(ig), vp(ig), vp(f)))
             assert np.array_equal(_f_traffic(L) - t0, [3 * 8 * 8 * len(ig), 0])
             listed[_cells(T, ig)] = True
         assert L.ramses_amd_amrres_has_gravity() == 1
         got = np.full((3, ncell), POISON)
         for ig in T["lists"]:
             t0 = _f_traffic(L)
-            check(L.ramses_amd_amrres_sync_f(len(ig), _vp(ig), _vp(got)))
+            check(L.ramses_amd_amrres_sync_f(len(ig), vp(ig), vp(got)))
             assert np.array_equal(_f_traffic(L) - t0, [0, 3 * 8 * 8 * len(ig)])
         want = np.full((3, ncell), POISON)
         want[:, listed] = f[:, listed]
-        assert np.array_equal(_bits(got), _bits(want))
+        assert np.array_equal(bits(got), bits(want))
         # compare_f: equal; then k cells of listed octs changed by known amounts
         maxdiff, ndiff = C.c_double(-1.0), C.c_int64(-1)
         t0 = _f_traffic(L)
         for ig in T["lists"]:
-            check(L.ramses_amd_amrres_compare_f(len(ig), _vp(ig), _vp(f), C.byref(maxdiff), C.byref(ndiff)))
+            check(L.ramses_amd_amrres_compare_f(len(ig), vp(ig), vp(f), C.byref(maxdiff), C.byref(ndiff)))
             assert (maxdiff.value, ndiff.value) == (0.0, 0)
         ig = T["lists"][1]
         c = _cells(T, ig)
@@ -171,11 +162,11 @@ def test_the_acceleration_of_a_level_goes_down_and_comes_home(gpu_lib, monkeypat
         f2[comp, pick] += 2.0 ** np.arange(-3, k - 3)
         amounts = np.abs(f[comp, pick] - f2[comp, pick])
         assert (amounts > 0).all()
-        check(L.ramses_amd_amrres_compare_f(len(ig), _vp(ig), _vp(f2), C.byref(maxdiff), C.byref(ndiff)))
+        check(L.ramses_amd_amrres_compare_f(len(ig), vp(ig), vp(f2), C.byref(maxdiff), C.byref(ndiff)))
         assert ndiff.value == k and maxdiff.value == amounts.max()
         # ... and the other level's list sees none of them
         ig = T["lists"][0]
-        check(L.ramses_amd_amrres_compare_f(len(ig), _vp(ig), _vp(f2), C.byref(maxdiff), C.byref(ndiff)))
+        check(L.ramses_amd_amrres_compare_f(len(ig), vp(ig), vp(f2), C.byref(maxdiff), C.byref(ndiff)))
         assert (maxdiff.value, ndiff.value) == (0.0, 0)
         assert np.array_equal(_f_traffic(L), t0)              # compare_f is not counted
     finally:
@@ -204,12 +195,12 @@ def test_the_deposit_of_a_level_comes_home(gpu_lib, monkeypatch, layout):
     uold[0] = z[k + "dens"]
     p = ramses_amd.make_params(smallr=smallr)
     check(L.ramses_amd_amrres_invalidate())
-    check(L.ramses_amd_amrres_load(5, ngridmax, ncoarse, _vp(uold), _vp(son), _vp(nbor), _vp(father)))
+    check(L.ramses_amd_amrres_load(5, ngridmax, ncoarse, vp(uold), vp(son), vp(nbor), vp(father)))
     try:
         rho = np.full(ncell, POISON)
         mp = np.zeros(4)
-        check(L.ramses_amd_amrres_xg(_vp(xg)))
-        check(L.ramses_amd_amrres_rho_fine(C.byref(p), ilevel, nlevelmax, levelmin, nvector, _vp(first), _vp(igrid_all), boxlen, _vp(rho), _vp(mp)))
+        check(L.ramses_amd_amrres_xg(vp(xg)))
+        check(L.ramses_amd_amrres_rho_fine(C.byref(p), ilevel, nlevelmax, levelmin, nvector, vp(first), vp(igrid_all), boxlen, vp(rho), vp(mp)))
         nlev = 0
         for li in range(len(first) - 1):
             ig = np.ascontiguousarray(igrid_all[first[li]:first[li + 1]])
@@ -221,17 +212,17 @@ def test_the_deposit_of_a_level_comes_home(gpu_lib, monkeypatch, layout):
             assert (rho[lev] != POISON).all()
             got = np.full(ncell, POISON)
             t0 = L.ramses_amd_amrres_rho_traffic()
-            check(L.ramses_amd_amrres_sync_rho(len(ig), _vp(ig), _vp(got)))
+            check(L.ramses_amd_amrres_sync_rho(len(ig), vp(ig), vp(got)))
             assert L.ramses_amd_amrres_rho_traffic() - t0 == 8 * 8 * len(ig)
             want = np.full(ncell, POISON)
             want[lev] = rho[lev]
-            assert np.array_equal(_bits(got), _bits(want))
+            assert np.array_equal(bits(got), bits(want))
             nlev += 1
         assert nlev >= 2
         # an empty list: nothing moves, nothing is counted
         got = np.full(ncell, POISON)
         t0 = L.ramses_amd_amrres_rho_traffic()
-        assert L.ramses_amd_amrres_sync_rho(0, _vp(igrid_all), _vp(got)) == 0
+        assert L.ramses_amd_amrres_sync_rho(0, vp(igrid_all), vp(got)) == 0
         assert L.ramses_amd_amrres_rho_traffic() == t0 and (got == POISON).all()
     finally:
         check(L.ramses_amd_amrres_invalidate())
@@ -250,13 +241,13 @@ def test_an_empty_list_moves_nothing(gpu_lib, monkeypatch):
     _load(L, T, u, "host")
     try:
         ig = T["lists"][1]
-        check(L.ramses_amd_amrres_load_f(len(ig), _vp(ig), _vp(f)))
+        check(L.ramses_amd_amrres_load_f(len(ig), vp(ig), vp(f)))
         t0 = _f_traffic(L)
         got = np.full((3, ncell), POISON)
-        assert L.ramses_amd_amrres_sync_f(0, _vp(ig), _vp(got)) == 0
+        assert L.ramses_amd_amrres_sync_f(0, vp(ig), vp(got)) == 0
         assert (got == POISON).all() and np.array_equal(_f_traffic(L), t0)
         want = u.copy()
-        assert L.ramses_amd_amrres_sync_density(0, _vp(ig), _vp(u)) == 0
-        assert np.array_equal(_bits(u), _bits(want))
+        assert L.ramses_amd_amrres_sync_density(0, vp(ig), vp(u)) == 0
+        assert np.array_equal(bits(u), bits(want))
     finally:
         check(L.ramses_amd_amrres_invalidate())

@@ -14,7 +14,6 @@
    checksums of the serial reference (tests/golden/baseline_sizes.json, made by
    tests/golden/make_golden_baseline.py).
 """
-import importlib.util
 import json
 import os
 import shutil
@@ -22,19 +21,14 @@ import shutil
 import numpy as np
 import pytest
 
+import live
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi")
 PATCHED = os.path.join(ROOT, "oracle", "_ref", "ramses3d_patch")
 GOLD = os.path.join(ROOT, "tests", "golden", "baseline_sizes.json")
 TOL = 1e-12     # north_star: "results within 1e-12 relative L-infinity of the F90 reference"
-
-
-def _mkb():
-    spec = importlib.util.spec_from_file_location("mkb", os.path.join(ROOT, "tests", "golden", "make_golden_baseline.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
 
 
 def _rel_linf_per_var(a, b):
@@ -177,7 +171,7 @@ def test_c4_standin_128_checksum(gpu_lib):
     if gold is None:
         pytest.skip("no c4_128 checksum")
     from oracle import ramses_snapshot as rs
-    mkb = _mkb()
+    mkb = live.golden_module("baseline")
     os.environ["RAMSES_AMD"] = "1"
     work, out = rs.run_reference(mkb.c4_namelist(), binary=PATCHED)
     try:
@@ -204,7 +198,7 @@ def test_c5_levels_7_9_checksum(gpu_lib, resident):
     if gold is None:
         pytest.skip("no c5_79 checksum")
     from oracle import ramses_snapshot as rs
-    mkb = _mkb()
+    mkb = live.golden_module("baseline")
     os.environ["RAMSES_AMD"] = "1"
     os.environ["RAMSES_AMD_RESIDENT_AMR"] = resident
     os.environ["RAMSES_AMD_STATS"] = "1"
@@ -244,7 +238,7 @@ def test_c5_levels_7_10_on_8_ranks_equals_the_mpi_reference(gpu_lib):
     if not (os.path.exists(ref_mpi) and os.path.exists(pat_mpi)):
         pytest.skip("oracle/_ref/ramses3d_mpi[_patch] not built")
     from oracle import ramses_snapshot as rs
-    mkb = _mkb()
+    mkb = live.golden_module("baseline")
     nml = mkb.c5_namelist(7, 10, 8, 3000000)
     os.environ["RAMSES_AMD"] = "1"
     work, out = rs.run_reference(nml, nproc=8, binary=pat_mpi)
@@ -298,7 +292,7 @@ def test_c5_with_multigrid_equals_the_mpi_reference(gpu_lib, tmp_path, lmin, lma
         pytest.skip("fewer cores than ranks")
     import re
     from oracle import ramses_snapshot as rs
-    mkb = _mkb()
+    mkb = live.golden_module("baseline")
     nml = _c5_gravity_namelist(mkb, lmin, lmax, nstep, 3000000 if lmax == 10 else 1500000, kind)
     pat = r"==> Level=\s*(\d+) Step=\s*(\d+)"
     prof = str(tmp_path / "profile.txt")
@@ -351,7 +345,7 @@ def test_amr_self_gravity_levels_6_8_checksum(gpu_lib, mode):
     if gold is None:
         pytest.skip("no amr_grav_68 checksum")
     from oracle import ramses_snapshot as rs
-    mkb = _mkb()
+    mkb = live.golden_module("baseline")
     env = {"RAMSES_AMD": "1"}
     if mode != "resident":
         env["RAMSES_AMD_RESIDENT_GRAV"] = "0"

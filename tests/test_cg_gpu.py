@@ -3,7 +3,6 @@ kernel level against dumps of the UNMODIFIED reference (tests/golden/cg_ref.npz,
 tests/golden/make_golden_cg.py with oracle/dump_patch/phi_fine_cg.f90), against the C oracle on
 a synthetic partially refined tree, and end to end through the patched reference program."""
 import ctypes as C
-import importlib.util
 import os
 import re
 import shutil
@@ -11,6 +10,8 @@ import sys
 
 import numpy as np
 import pytest
+
+import live
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -123,9 +124,7 @@ def test_patched_program_with_cg_levels_equals_reference(gpu_lib, ordered):
     if not os.path.exists(patched):
         pytest.skip("oracle/_ref/ramses3d_patch not built")
     from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mkcg", os.path.join(ROOT, "tests", "golden", "make_golden_cg.py"))
-    mk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mk)
+    mk = live.golden_module("cg")
     z = np.load(GOLD)
     os.environ.pop("RAMSES_AMD_CG_ORDERED", None)
     if ordered != "default":
@@ -161,9 +160,7 @@ def test_patched_program_with_cg_levels_inside_walls_equals_reference(gpu_lib):
     if not os.path.exists(patched):
         pytest.skip("oracle/_ref/ramses3d_patch not built")
     from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mkcg", os.path.join(ROOT, "tests", "golden", "make_golden_cg.py"))
-    mk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mk)
+    mk = live.golden_module("cg")
     z = np.load(GOLD)
     os.environ["RAMSES_AMD_CG_ORDERED"] = "1"
     try:

@@ -14,6 +14,8 @@ import shutil
 import numpy as np
 import pytest
 
+import live
+
 from helpers import _octree_layout, random_brick
 
 pytestmark = pytest.mark.gpu
@@ -144,11 +146,8 @@ def test_patched_program_self_gravity_reproduces_goldens(gpu_lib, case):
     untouched reference, bit for bit; the hydro sweep then runs with gravity."""
     if not os.path.exists(PATCHED):
         pytest.skip("oracle/_ref/ramses3d_patch not built")
-    import importlib.util
     from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mkp", os.path.join(ROOT, "tests", "golden", "make_golden_poisson.py"))
-    mkp = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mkp)
+    mkp = live.golden_module("poisson")
     key, level, boxlen, eps, blob = mkp.CASES[case]
     z = np.load(os.path.join(ROOT, "tests", "golden", "poisson_ref_runs.npz"))
     nml = rs.sedov3d_namelist(level=level, nstepmax=2, foutput=1, boxlen=boxlen, poisson=True,
@@ -181,12 +180,9 @@ def test_patched_program_self_gravity_three_steps(gpu_lib, resident_grav):
     the density back.  Either way the snapshot equals the untouched reference bit for bit."""
     if not os.path.exists(PATCHED):
         pytest.skip("oracle/_ref/ramses3d_patch not built")
-    import importlib.util
     import re
     from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mkp", os.path.join(ROOT, "tests", "golden", "make_golden_poisson.py"))
-    mkp = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mkp)
+    mkp = live.golden_module("poisson")
     key, level, boxlen, eps, blob = mkp.CASES[-1]
     z = np.load(os.path.join(ROOT, "tests", "golden", "poisson_ref_runs.npz"))
     nml = rs.sedov3d_namelist(level=level, nstepmax=4, foutput=3, boxlen=boxlen, poisson=True,

@@ -19,6 +19,8 @@ import shutil
 import numpy as np
 import pytest
 
+import live
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi")
@@ -195,12 +197,9 @@ def test_default_mode_amr_run_live_ab(gpu_lib, monkeypatch, lmin, lmax, nstep):
     tile kernels too (production keeps the strict tree walker below 32768 octs), and the exit line must say so."""
     if not (os.path.exists(REF_MPI) and os.path.exists(PATCHED)):
         pytest.skip("oracle/_ref/ramses3d_mpi / ramses3d_patch not built")
-    import importlib.util
     import re
     from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mkb", os.path.join(ROOT, "tests", "golden", "make_golden_baseline.py"))
-    mkb = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mkb)
+    mkb = live.golden_module("baseline")
     nml = mkb.c5_namelist(lmin, lmax, nstep, 400000)
     monkeypatch.setenv("RAMSES_AMD", "1")
     monkeypatch.setenv("RAMSES_AMD_STATS", "1")
@@ -249,12 +248,9 @@ def test_fast_mode_amr_self_gravity_live_ab(gpu_lib, monkeypatch):
     solve, rel-Linf <= 1e-12 on the hydro variables and on the acceleration; phi agrees to 1e-12 up to a spatially constant offset."""
     if not (os.path.exists(REF_MPI) and os.path.exists(PATCHED)):
         pytest.skip("oracle/_ref/ramses3d_mpi / ramses3d_patch not built")
-    import importlib.util
     import re
     from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mkb", os.path.join(ROOT, "tests", "golden", "make_golden_baseline.py"))
-    mkb = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mkb)
+    mkb = live.golden_module("baseline")
     nstep = 6
     nml = mkb.amr_grav_namelist(lmin=6, lmax=8, nstep=nstep)
     monkeypatch.setenv("RAMSES_AMD", "1")
@@ -308,7 +304,6 @@ def test_self_gravitating_runs_take_the_strict_build_by_default(gpu_lib, monkeyp
     """poisson=.true. without any switch: the patched program must say 'strict' on its own (phi is part of north_star's tolerance, and
     the fast build leaves a constant offset of ~1e-10 in it: test_fast_mode_amr_self_gravity_live_ab) and then equal the reference
     bit for bit -- the golden checksum of the AMR self-gravity run of tests/test_baseline_sizes_gpu.py."""
-    import importlib.util
     import json
     if not os.path.exists(PATCHED):
         pytest.skip("patched program missing")
@@ -317,9 +312,7 @@ def test_self_gravitating_runs_take_the_strict_build_by_default(gpu_lib, monkeyp
     if gold is None:
         pytest.skip("no amr_grav_68 checksum")
     from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mkb", os.path.join(ROOT, "tests", "golden", "make_golden_baseline.py"))
-    mkb = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mkb)
+    mkb = live.golden_module("baseline")
     monkeypatch.setenv("RAMSES_AMD", "1")
     monkeypatch.delenv("RAMSES_AMD_FAST", raising=False)
     monkeypatch.delenv("RAMSES_AMD_STRICT", raising=False)

@@ -22,7 +22,8 @@ import shutil
 import numpy as np
 import pytest
 
-from test_walls_resident_gpu import CORNER, PATCHED, PATCHED_MPI, REF, REF_MPI, _mka, _run
+import live
+from test_walls_resident_gpu import CORNER
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +47,7 @@ def _gravity(gtype, params):
 
 def _namelist(case):
     from oracle import ramses_snapshot as rs
-    mka = _mka()
+    mka = live.golden_module("amr")
     if case == "a":
         extra = mka.REFINE.format(ivar=0, itype=1) + ZWALLS + _gravity(1, (0.0, 0.0, -1.7))
         nml = rs.sedov3d_namelist(level=4, nstepmax=NSTEP, foutput=NSTEP, riemann="hll", slope_type=1, extra=extra, init=CORNER,
@@ -59,8 +60,7 @@ def _namelist(case):
         extra = _gravity(2, (3.0, 0.02, 0.2, 0.3, 0.1))
         nml = rs.sedov3d_namelist(level=5, nstepmax=NSTEP, foutput=NSTEP, riemann="hll", slope_type=1, extra=extra, poisson=True)
         return nml
-    nml = nml.replace("levelmax=4", "levelmax=6").replace("nsubcycle=10*1", "nsubcycle=1,1,1,2,2")
-    return nml.replace("ngridtot=", "ngridtot=60000 !")
+    return live.replace_keys(nml, ("levelmax=4", "levelmax=6"), ("nsubcycle=10*1", "nsubcycle=1,1,1,2,2"), ("ngridtot=", "ngridtot=60000 !"))
 
 
 def _snapshot(work):
@@ -74,17 +74,15 @@ def _snapshot(work):
 @functools.lru_cache(maxsize=None)
 def _pair(case, nproc, switch):
     """(patched program's output text, its snapshot, the reference program's snapshot)"""
-    ref_bin, pat_bin = (REF, PATCHED) if nproc == 1 else (REF_MPI, PATCHED_MPI)
-    if not (os.path.exists(ref_bin) and os.path.exists(pat_bin)):
-        pytest.skip("oracle/_ref programs not built")
+    pat_bin, ref_bin = live.binaries(nproc > 1)
     nml = _namelist(case)
     env = {"RAMSES_AMD": "1", "RAMSES_AMD_PROFILE": "1", "RAMSES_AMD_STATS": "1", "RAMSES_AMD_GRAVANA": "1" if switch else "0"}
-    workp, outp = _run(nml, pat_bin, nproc, env)
+    workp, outp = live.run(nml, pat_bin, nproc, env)
     try:
         got = _snapshot(workp)
     finally:
         shutil.rmtree(workp, ignore_errors=True)
-    workr, _ = _run(nml, ref_bin, nproc, {})
+    workr, _ = live.run(nml, ref_bin, nproc, {})
     try:
         ref = _snapshot(workr)
     finally:

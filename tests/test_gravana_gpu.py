@@ -20,11 +20,11 @@ import pytest
 
 import gravana_checker as GC
 import helpers as H
+import resident as R
+from resident import vp
 
 pytestmark = pytest.mark.gpu
 
-LAYOUT_VARS = ("RAMSES_AMD_DEVICE_ORDER", "RAMSES_AMD_TILES", "RAMSES_AMD_TILE_DENSE", "RAMSES_AMD_COVERED_DENSE", "RAMSES_AMD_TILE_SWEEP",
-               "RAMSES_AMD_DIFMAG_TILES", "RAMSES_AMD_SORTED_LISTS", "RAMSES_AMD_LIST_CACHE")
 # (gravity_type, gravity_params, boxlen)
 GRAVITY = [(1, (0.3, -0.2, -1.7), 0.5),
            (2, (3.0, 0.02, 0.2, 0.3, 0.1), 0.5),
@@ -37,18 +37,9 @@ IDS = ["L%d-%s%s" % (c[0], c[1], "-hostorder" if c[2] == "0" else "") for c in C
 
 @pytest.fixture(autouse=True)
 def _tiles_on_small_levels_too(monkeypatch):
-    monkeypatch.setenv("RAMSES_AMD_TILE_MIN_OCTS", "0")
-    for var in LAYOUT_VARS:
-        monkeypatch.delenv(var, raising=False)
+    R.force_tiles(monkeypatch, clear=R.ALL_LAYOUT_VARS)
     yield
-    import ramses_amd
-    lib = ramses_amd.lib()
-    lib.ramses_amd_amrres_invalidate()
-    lib.ramses_amd_amrres_coarse_grid(1, 1, 1)
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+    R.reset_library()
 
 
 def _params10(params):
@@ -57,7 +48,7 @@ def _params10(params):
 
 def _set(Lb, gtype, params, skip, scale):
     from ramses_amd._capi import check
-    check(Lb.ramses_amd_gravana_set(gtype, _vp(_params10(params)), _vp(np.array(skip, dtype=np.float64)), float(scale)))
+    check(Lb.ramses_amd_gravana_set(gtype, vp(_params10(params)), vp(np.array(skip, dtype=np.float64)), float(scale)))
 
 
 def tree_levels(T):
@@ -76,21 +67,15 @@ def tree_levels(T):
 
 def _load(Lb, T, levels, xg, f, grid=(1, 1, 1)):
     """the tree (any state), the oct centres and f of every level onto the device"""
-    from ramses_amd._capi import check
     u = np.ones((5, T["ncell"]))
-    check(Lb.ramses_amd_amrres_invalidate())
-    check(Lb.ramses_amd_amrres_coarse_grid(*grid))
-    check(Lb.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
-    check(Lb.ramses_amd_amrres_xg(_vp(xg)))
-    for ig in levels.values():
-        check(Lb.ramses_amd_amrres_load_f(len(ig), _vp(ig), _vp(f)))
+    R.load(Lb, T, u, f, levels=levels.values(), grid=grid, xg=xg)
     return u
 
 
 def _fetch_f(Lb, levels, into):
     from ramses_amd._capi import check
     for ig in levels.values():
-        check(Lb.ramses_amd_amrres_sync_f(len(ig), _vp(ig), _vp(into)))
+        check(Lb.ramses_amd_amrres_sync_f(len(ig), vp(ig), vp(into)))
 
 
 def _same_bits(a, b):
@@ -124,7 +109,7 @@ def test_force_ana_on_resident_levels(gpu_lib, monkeypatch, L, order, device_ord
                     assert (rr > 0).all() and np.isfinite(want).all(), what
                 diag = np.full(2, np.nan)
                 fact = -0.37
-                check(gpu_lib.ramses_amd_amrres_force_ana(lev, len(octs), _vp(octs), dx, fact, _vp(diag)))
+                check(gpu_lib.ramses_amd_amrres_force_ana(lev, len(octs), vp(octs), dx, fact, vp(diag)))
                 _fetch_f(gpu_lib, levels, f)
                 cells = H.oct_cells(T, octs) if len(octs) else np.zeros(0, np.int64)
                 other = np.ones(T["ncell"], bool)
@@ -174,7 +159,7 @@ def test_force_ana_between_walls_uses_the_coarse_grid_offset(gpu_lib, monkeypatc
                 z = GC.cell_centres(xg[:, octs.astype(np.int64) - 1], 0, 0.5 ** L, skip, boxlen)[2]
                 assert z.min() > 0 and z.max() < boxlen
                 diag = np.zeros(2)
-                check(gpu_lib.ramses_amd_amrres_force_ana(L, len(octs), _vp(octs), 0.5 ** L, 1.0, _vp(diag)))
+                check(gpu_lib.ramses_amd_amrres_force_ana(L, len(octs), vp(octs), 0.5 ** L, 1.0, vp(diag)))
                 _fetch_f(gpu_lib, levels, f)
                 assert _same_bits(f, want), (gtype, params, boxlen, len(octs))
                 assert (f != before).any()
@@ -189,7 +174,7 @@ def test_gravana_eval_on_given_positions(gpu_lib):
     for gtype, params, boxlen in GRAVITY:
         _set(gpu_lib, gtype, params, (0.0, 0.0, 0.0), boxlen)
         f = np.full((3, 100), np.nan)
-        check(gpu_lib.ramses_amd_gravana_eval(100, _vp(x), _vp(f)))
+        check(gpu_lib.ramses_amd_gravana_eval(100, vp(x), vp(f)))
         assert _same_bits(f, GC.gravana(gtype, params, x)[0]), (gtype, params)
     check(gpu_lib.ramses_amd_gravana_eval(0, None, None))
 
@@ -197,9 +182,9 @@ def test_gravana_eval_on_given_positions(gpu_lib):
 def test_gravity_type_3_is_refused_by_name(gpu_lib):
     p, s = np.zeros(10), np.zeros(3)
     for gtype in (3, 0, -1, 4):
-        rc = gpu_lib.ramses_amd_gravana_set(gtype, _vp(p), _vp(s), 1.0)
+        rc = gpu_lib.ramses_amd_gravana_set(gtype, vp(p), vp(s), 1.0)
         assert rc == -2 and b"gravity_type" in gpu_lib.ramses_amd_last_error() and b"ramses_amd_gravana_set" in gpu_lib.ramses_amd_last_error()
-    assert gpu_lib.ramses_amd_gravana_set(2, None, _vp(s), 1.0) == -1
+    assert gpu_lib.ramses_amd_gravana_set(2, None, vp(s), 1.0) == -1
 
 
 def test_entries_fail_loudly_without_their_state(gpu_lib):
@@ -207,13 +192,13 @@ def test_entries_fail_loudly_without_their_state(gpu_lib):
     check(gpu_lib.ramses_amd_amrres_invalidate())
     _set(gpu_lib, 1, (0.0, 0.0, -1.0), (0, 0, 0), 1.0)
     ig, d = np.array([1], np.int32), np.zeros(2)
-    assert gpu_lib.ramses_amd_amrres_force_ana(1, 1, _vp(ig), 0.5, 1.0, _vp(d)) == -1
+    assert gpu_lib.ramses_amd_amrres_force_ana(1, 1, vp(ig), 0.5, 1.0, vp(d)) == -1
     assert b"no resident AMR state" in gpu_lib.ramses_amd_last_error()
     one = np.array([1], np.int32)
-    assert gpu_lib.ramses_amd_amrres_boundary_force(1, _vp(one), _vp(one), _vp(ig), 32, 0.5) == -1
+    assert gpu_lib.ramses_amd_amrres_boundary_force(1, vp(one), vp(one), vp(ig), 32, 0.5) == -1
     assert b"no resident AMR state" in gpu_lib.ramses_amd_last_error()
     assert gpu_lib.ramses_amd_resident_invalidate() == 0
-    assert gpu_lib.ramses_amd_resident_force_ana_f90(4, 1.0, _vp(d)) == -1
+    assert gpu_lib.ramses_amd_resident_force_ana_f90(4, 1.0, vp(d)) == -1
     assert b"is not resident" in gpu_lib.ramses_amd_last_error()
 
 
@@ -236,11 +221,11 @@ def test_force_ana_on_the_resident_brick(gpu_lib):
             before = f.copy()
             mp, diag = np.zeros(4), np.zeros(2)
             assert gpu_lib.ramses_amd_resident_invalidate() == 0
-            assert gpu_lib.ramses_amd_resident_rho_fine_f90(C.byref(p), *L.head(), _vp(uold), boxlen, 32, _vp(mp)) == 0, gpu_lib.ramses_amd_last_error()
+            assert gpu_lib.ramses_amd_resident_rho_fine_f90(C.byref(p), *L.head(), vp(uold), boxlen, 32, vp(mp)) == 0, gpu_lib.ramses_amd_last_error()
             _set(gpu_lib, gtype, params, (0.0, 0.0, 0.0), boxlen)
             fact = -0.11
-            assert gpu_lib.ramses_amd_resident_force_ana_f90(level, fact, _vp(diag)) == 0, gpu_lib.ramses_amd_last_error()
-            assert gpu_lib.ramses_amd_resident_sync_poisson_f90(_vp(phi), _vp(f), _vp(rho)) == 0, gpu_lib.ramses_amd_last_error()
+            assert gpu_lib.ramses_amd_resident_force_ana_f90(level, fact, vp(diag)) == 0, gpu_lib.ramses_amd_last_error()
+            assert gpu_lib.ramses_amd_resident_sync_poisson_f90(vp(phi), vp(f), vp(rho)) == 0, gpu_lib.ramses_amd_last_error()
             dx = 0.5 ** level
             x = np.stack([((k + 0.5) * dx - 0.0) * boxlen for k in (kx, ky, kz)]).reshape(3, -1)
             want = GC.gravana(gtype, params, x)[0].reshape(3, n, n, n)
@@ -301,13 +286,13 @@ def test_deep_boundary_regions_of_f_follow_the_references_in_place_loop(gpu_lib,
             got = f0.copy()
             check(gpu_lib.ramses_amd_amrres_invalidate())
             check(gpu_lib.ramses_amd_amrres_coarse_grid(1, 1, 1))
-            check(gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
-            check(gpu_lib.ramses_amd_amrres_xg(_vp(xg)))
-            check(gpu_lib.ramses_amd_amrres_load_f(7, _vp(everything), _vp(got)))
+            check(gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], vp(u), vp(T["son"]), vp(T["nbor"]), vp(T["father"])))
+            check(gpu_lib.ramses_amd_amrres_xg(vp(xg)))
+            check(gpu_lib.ramses_amd_amrres_load_f(7, vp(everything), vp(got)))
             bt, ng, ig = np.array([btype], np.int32), np.array([3], np.int32), np.array(order, np.int32)
-            check(gpu_lib.ramses_amd_amrres_boundary_force(1, _vp(bt), _vp(ng), _vp(ig), nvector, dx))
+            check(gpu_lib.ramses_amd_amrres_boundary_force(1, vp(bt), vp(ng), vp(ig), nvector, dx))
             got[:] = np.nan
-            check(gpu_lib.ramses_amd_amrres_sync_f(7, _vp(everything), _vp(got)))
+            check(gpu_lib.ramses_amd_amrres_sync_f(7, vp(everything), vp(got)))
             assert _same_bits(got[:, T["ncoarse"]:], want[:, T["ncoarse"]:]), (btype, nvector, order)
         if btype < 20:
             assert differ > 0          # (the chunking matters in this input: the case tests something)
@@ -344,7 +329,7 @@ def test_boundary_force_between_z_walls(gpu_lib, monkeypatch, mode, types, nvect
             bt = np.array(types, np.int32)
             ng = np.array([len(r) for r in regions], np.int32)
             ig = np.ascontiguousarray(np.concatenate(regions), dtype=np.int32)
-            check(gpu_lib.ramses_amd_amrres_boundary_force(2, _vp(bt), _vp(ng), _vp(ig), nvector, 0.5 ** level))
+            check(gpu_lib.ramses_amd_amrres_boundary_force(2, vp(bt), vp(ng), vp(ig), nvector, 0.5 ** level))
             _fetch_f(gpu_lib, levels, f)
             assert _same_bits(f, want), (level, types, nvector)
             assert (f != before).any()
@@ -390,14 +375,14 @@ def test_a_corner_region_reads_what_an_earlier_region_wrote(gpu_lib):
             got = f0.copy()
             check(gpu_lib.ramses_amd_amrres_invalidate())
             check(gpu_lib.ramses_amd_amrres_coarse_grid(1, 1, 1))
-            check(gpu_lib.ramses_amd_amrres_load(5, ngridmax, ncoarse, _vp(u), _vp(son), _vp(nbor), _vp(father)))
-            check(gpu_lib.ramses_amd_amrres_xg(_vp(xg)))
-            check(gpu_lib.ramses_amd_amrres_load_f(4, _vp(everything), _vp(got)))
+            check(gpu_lib.ramses_amd_amrres_load(5, ngridmax, ncoarse, vp(u), vp(son), vp(nbor), vp(father)))
+            check(gpu_lib.ramses_amd_amrres_xg(vp(xg)))
+            check(gpu_lib.ramses_amd_amrres_load_f(4, vp(everything), vp(got)))
             bt, ng = np.array([t1, t2], np.int32), np.array([2, 2], np.int32)
             ig = np.ascontiguousarray(np.concatenate(regions), dtype=np.int32)
-            check(gpu_lib.ramses_amd_amrres_boundary_force(2, _vp(bt), _vp(ng), _vp(ig), 32, 0.25))
+            check(gpu_lib.ramses_amd_amrres_boundary_force(2, vp(bt), vp(ng), vp(ig), 32, 0.25))
             got[:] = np.nan
-            check(gpu_lib.ramses_amd_amrres_sync_f(4, _vp(everything), _vp(got)))
+            check(gpu_lib.ramses_amd_amrres_sync_f(4, vp(everything), vp(got)))
             assert _same_bits(got[:, ncoarse:], want[:, ncoarse:]), (t1, t2)
     finally:
         gpu_lib.ramses_amd_amrres_invalidate()
@@ -421,10 +406,10 @@ def test_stash_and_restore_of_f(gpu_lib, monkeypatch, L, order, device_order):
     try:
         for lev in (L, L + 1):
             ig = T["lists"][lev]["full"]
-            check(gpu_lib.ramses_amd_amrres_stash_f(len(ig), _vp(ig)))
+            check(gpu_lib.ramses_amd_amrres_stash_f(len(ig), vp(ig)))
         other = np.random.default_rng(21).normal(size=f.shape)
         for ig in levels.values():
-            check(gpu_lib.ramses_amd_amrres_load_f(len(ig), _vp(ig), _vp(other)))
+            check(gpu_lib.ramses_amd_amrres_load_f(len(ig), vp(ig), vp(other)))
         want = other.copy()
         in_tree = np.zeros(T["ncell"], bool)
         for ig in levels.values():
@@ -438,7 +423,7 @@ def test_stash_and_restore_of_f(gpu_lib, monkeypatch, L, order, device_order):
             for ind in range(8):
                 cells = T["ncoarse"] + ind * T["ngridmax"] + g - 1
                 want[:, cells] = np.where(inherit[None, :] != 0, want[:, fc], f0[:, cells])
-            check(gpu_lib.ramses_amd_amrres_restore_f(len(ig), _vp(ig), _vp(inherit)))
+            check(gpu_lib.ramses_amd_amrres_restore_f(len(ig), vp(ig), vp(inherit)))
             got = f.copy()
             _fetch_f(gpu_lib, levels, got)
             assert _same_bits(got, want), "level %d" % lev

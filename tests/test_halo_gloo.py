@@ -264,7 +264,7 @@ class StencilLevel(FakeLevel):
         tgt = self.unew[:, g:g + n, g:g + n, g:g + n]
         tgt[:, mask] = new[:, mask]
 
-    def _shell_mask(self):
+    def _boundary_shell(self):
         n = self.nx
         i = torch.arange(n)
         near = (i < 2) | (i >= n - 2)
@@ -274,10 +274,10 @@ class StencilLevel(FakeLevel):
         self._update(dt, torch.ones((self.nx,) * 3, dtype=torch.bool))
 
     def godunov_fine_shell(self, dt):
-        self._update(dt, self._shell_mask())
+        self._update(dt, self._boundary_shell())
 
     def godunov_fine_interior(self, dt):
-        self._update(dt, ~self._shell_mask())
+        self._update(dt, ~self._boundary_shell())
 
     def set_uold(self):
         self.uold, self.unew = self.unew, self.uold

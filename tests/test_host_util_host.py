@@ -10,20 +10,10 @@ import os
 import shutil
 import subprocess
 
+from helpers import hip_include
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "host_util_check.cpp")
-
-
-def _hip_include():
-    cands = [os.environ.get("ROCM_PATH"), os.environ.get("HIP_PATH")]
-    hipcc = shutil.which("hipcc")
-    if hipcc:
-        cands.append(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))))
-    cands.append("/opt/rocm")
-    for c in cands:
-        if c and os.path.exists(os.path.join(c, "include", "hip", "hip_runtime_api.h")):
-            return os.path.join(c, "include")
-    raise RuntimeError("hip/hip_runtime_api.h not found")
 
 
 def test_host_util_under_the_sanitizers(tmp_path):
@@ -32,7 +22,7 @@ def test_host_util_under_the_sanitizers(tmp_path):
     exe = str(tmp_path / "host_util_check")
     # (the sanitizers' runtimes linked statically: the program then runs whatever else the environment preloads)
     r = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-isystem", _hip_include(),
+                        "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-isystem", hip_include(),
                         "-I", os.path.join(ROOT, "ramses_amd"), SRC, "-o", exe],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     print(r.stdout)

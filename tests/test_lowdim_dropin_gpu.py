@@ -3,12 +3,13 @@ one uniform level): oracle/_ref/ramses{1,2}d_patch -- the reference program with
 refined level on the GPU as a brick embedded in three dimensions, the boundary octs as its ghost cells
 (csrc/capi_host.hip ramses_amd_godunov_fine_lowdim_f90) -- against the UNMODIFIED reference oracle/_ref/ramses{1,2}d, live, on
 the same namelist: every leaf cell of every snapshot bit for bit (verification arithmetic, tests/conftest.py)."""
-import importlib.util
 import os
 import shutil
 
 import numpy as np
 import pytest
+
+import live
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,18 +54,11 @@ def _ab(nml, ndim, note):
     assert np.abs(last["prim"][1]).max() > 1e-3          # the blast moved
 
 
-def _mk1d():
-    spec = importlib.util.spec_from_file_location("mk1d", os.path.join(ROOT, "tests", "golden", "make_golden_sedov1d.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
 @pytest.mark.parametrize("bt,nstep,slope", [("1, 1", 40, 2), ("2, 2", 60, 2), ("1, 1", 20, 5)])
 def test_c1_sedov1d_through_the_fortran_dropin(gpu_lib, bt, nstep, slope):
     """BASELINE config C1: sedov1d.nml, NDIM=1, levelmin = levelmax = 7 (128 cells), reflexive / outflow walls, a second blast
     at the right wall; slope type 5 (ultrabee) exists in the reference's NDIM=1 branch only"""
-    nml = _mk1d().NML.format(level=7, nstep=nstep, foutput=10, bt=bt, slope=slope)
+    nml = live.golden_module("sedov1d").NML.format(level=7, nstep=nstep, foutput=10, bt=bt, slope=slope)
     _ab(nml, 1, "NDIM=1: level 7 (128 x 1 cells) is swept on the device as a brick embedded in 3-D; x between boundary octs")
 
 

@@ -12,44 +12,15 @@ prolongation -- runs on the rank's GPU, over the rank's own octs followed by the
   RAMSES_AMD_MG_MPI_SYNC were retired in round 6.)
 phi, f, the hydro state of every leaf cell and the V-cycle counts must equal the untouched MPI reference
 (oracle/_ref/ramses3d_mpi, same rank count) bit for bit."""
-import importlib.util
-import os
 import re
 import shutil
 
 import numpy as np
 import pytest
 
+import live
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi")
-PATCHED_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi_patch")
-
-
-def _mka():
-    spec = importlib.util.spec_from_file_location("mka", os.path.join(ROOT, "tests", "golden", "make_golden_amr.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _run(nml, binary, nproc, env):
-    from oracle import ramses_snapshot as rs
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return rs.run_reference(nml, binary=binary, nproc=nproc)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _sorted(snap):
-    order = np.lexsort((snap["x"][:, 0], snap["x"][:, 1], snap["x"][:, 2], snap["level"]))
-    return snap["level"][order], snap["x"][order], snap["prim"][:, order], snap["grav"][:, order]
 
 
 @pytest.mark.parametrize("nproc,resident,mgsync", [(2, "1", "0"), (4, "1", "0"), (8, "1", "0"), (2, "0", "0")])
@@ -58,14 +29,11 @@ def test_amr_multigrid_under_mpi_equals_the_mpi_reference(gpu_lib, nproc, reside
     exchanges of uold / unew on the device, the acceleration mirrored incl. the virtual octs, density back for
     rho_fine); resident=0 (RAMSES_AMD_RESIDENT_AMR_MPI=0): hydro arrays staged around every call.
     The multigrid levels stay on the device during a solve (mgsync is always "0" since round 6)."""
-    if not (os.path.exists(REF_MPI) and os.path.exists(PATCHED_MPI)):
-        pytest.skip("oracle/_ref/ramses3d_mpi[_patch] not built")
-    if nproc > (os.cpu_count() or 1):
-        pytest.skip("fewer cores than ranks")
-    from oracle import ramses_snapshot as rs
-    nml = _mka().selfgrav_namelist().replace("ngridtot=6000 !", "ngridtot=60000 !")
+    PATCHED_MPI, REF_MPI = live.binaries(True)
+    live.enough_cores(nproc)
+    nml = live.golden_module("amr").selfgrav_namelist().replace("ngridtot=6000 !", "ngridtot=60000 !")
     env = {"RAMSES_AMD": "1", "RAMSES_AMD_RESIDENT_AMR_MPI": resident, "RAMSES_AMD_MG_STATS": "1"}
-    workp, outp = _run(nml, PATCHED_MPI, nproc, env)
+    workp, outp = live.run(nml, PATCHED_MPI, nproc, env)
     try:
         assert ("AMR levels stay resident on the GPU" in outp) == (resident == "1"), outp[-1500:]
         stats = [[int(v) for v in m] for m in re.findall(
@@ -78,19 +46,19 @@ def test_amr_multigrid_under_mpi_equals_the_mpi_reference(gpu_lib, nproc, reside
             assert "multigrid under MPI: levels resident on the GPUs" in outp, outp[-1500:]
             assert all(s[0] == 0 and s[1] == 0 for s in stats), stats[:4]      # no level array crossed PCIe after the upload
             assert sum(s[3] for s in stats) > 100 and sum(s[2] for s in stats) > 0      # the exchanges ran on the device arrays
-        sol_p = re.findall(r"==> Level=\s*(\d+) Step=\s*(\d+)", outp)
-        got = _sorted(rs.load_leaf_cells(os.path.join(workp, "output_00002"), with_grav=True))
+        sol_p = live.poisson_solves(outp)
+        got = live.leaves(workp, with_grav=True)
     finally:
         shutil.rmtree(workp, ignore_errors=True)
-    workr, outr = _run(nml, REF_MPI, nproc, {})
+    workr, outr = live.run(nml, REF_MPI, nproc, {})
     try:
-        sol_r = re.findall(r"==> Level=\s*(\d+) Step=\s*(\d+)", outr)
-        ref = _sorted(rs.load_leaf_cells(os.path.join(workr, "output_00002"), with_grav=True))
+        sol_r = live.poisson_solves(outr)
+        ref = live.leaves(workr, with_grav=True)
     finally:
         shutil.rmtree(workr, ignore_errors=True)
     assert sol_p == sol_r
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
-    assert np.array_equal(got[3], ref[3]), np.abs(got[3] - ref[3]).max()     # phi, f
+    assert np.array_equal(got.grav, ref.grav), np.abs(got.grav - ref.grav).max()     # phi, f
     assert np.array_equal(got[2], ref[2]), np.abs(got[2] - ref[2]).max()     # hydro state
 
 
@@ -101,31 +69,28 @@ def test_force_fine_under_mpi_leaves_the_acceleration_on_the_device(gpu_lib):
     backup_poisson.  Counters of the library's exit line: what still goes up is the first load and the levels a regrid
     rebuilt; RAMSES_AMD_F_RESIDENT=0 (f back to the host, the reference's three exchanges, the whole level up again) moves
     several times that.  Both equal the MPI reference bit for bit."""
-    if not (os.path.exists(REF_MPI) and os.path.exists(PATCHED_MPI)):
-        pytest.skip("oracle/_ref/ramses3d_mpi[_patch] not built")
-    from oracle import ramses_snapshot as rs
+    PATCHED_MPI, REF_MPI = live.binaries(True)
     nproc = 2
-    nml = _mka().selfgrav_namelist().replace("ngridtot=6000 !", "ngridtot=60000 !")
-    pat = r"acceleration f over PCIe:\s*(\d+) bytes to the device,\s*(\d+) bytes back"
+    nml = live.golden_module("amr").selfgrav_namelist().replace("ngridtot=6000 !", "ngridtot=60000 !")
     res = {}
     for mode in ("1", "0"):
-        work, out = _run(nml, PATCHED_MPI, nproc, {"RAMSES_AMD": "1", "RAMSES_AMD_STATS": "1", "RAMSES_AMD_F_RESIDENT": mode})
+        work, out = live.run(nml, PATCHED_MPI, nproc, {"RAMSES_AMD": "1", "RAMSES_AMD_STATS": "1", "RAMSES_AMD_F_RESIDENT": mode})
         try:
             assert "AMR levels stay resident on the GPU" in out, out[-1500:]
-            traffic = [[int(a), int(b)] for a, b in re.findall(pat, out)]
+            traffic = live.f_traffic(out)
             assert len(traffic) == nproc, out[-2000:]
-            res[mode] = (traffic, _sorted(rs.load_leaf_cells(os.path.join(work, "output_00002"), with_grav=True)))
+            res[mode] = (traffic, live.leaves(work, with_grav=True))
         finally:
             shutil.rmtree(work, ignore_errors=True)
-    workr, _ = _run(nml, REF_MPI, nproc, {})
+    workr, _ = live.run(nml, REF_MPI, nproc, {})
     try:
-        ref = _sorted(rs.load_leaf_cells(os.path.join(workr, "output_00002"), with_grav=True))
+        ref = live.leaves(workr, with_grav=True)
     finally:
         shutil.rmtree(workr, ignore_errors=True)
     for mode in ("1", "0"):
         got = res[mode][1]
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
-        assert np.array_equal(got[3], ref[3]), (mode, np.abs(got[3] - ref[3]).max())     # phi, f
+        assert np.array_equal(got.grav, ref.grav), (mode, np.abs(got.grav - ref.grav).max())     # phi, f
         assert np.array_equal(got[2], ref[2]), (mode, np.abs(got[2] - ref[2]).max())     # hydro state
     up_new, up_old = sum(t[0] for t in res["1"][0]), sum(t[0] for t in res["0"][0])
     down_old = sum(t[1] for t in res["0"][0])
@@ -141,41 +106,34 @@ def test_cg_levels_under_mpi_equal_the_mpi_reference(gpu_lib, nproc, ordered):
     MPI_ALLREDUCEs per iteration (poisson/phi_fine_cg.f90:108,154) and the halo of p (:134) in the shim.  Ordered
     local sums: iteration counts, phi, f and the hydro state equal the MPI reference bit for bit; parallel sums:
     equal to rounding with the same iteration counts (+-1)."""
-    if not (os.path.exists(REF_MPI) and os.path.exists(PATCHED_MPI)):
-        pytest.skip("oracle/_ref/ramses3d_mpi[_patch] not built")
-    from oracle import ramses_snapshot as rs
-    spec = importlib.util.spec_from_file_location("mkcg", os.path.join(ROOT, "tests", "golden", "make_golden_cg.py"))
-    mk = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mk)
-    nml = mk.cg_namelist().replace("ngridtot=6000 !", "ngridtot=60000 !")
-    pat = r"==> Level=\s*(\d+) Step=\s*(\d+)"
+    PATCHED_MPI, REF_MPI = live.binaries(True)
+    nml = live.golden_module("cg").cg_namelist().replace("ngridtot=6000 !", "ngridtot=60000 !")
     # default: dot products in the reference's order (parity scan), the halo of p exchanged from the device vector;
     # "0": parallel-tree sums (equal to rounding)
-    if nproc > (os.cpu_count() or 1):
-        pytest.skip("fewer cores than ranks")
+    live.enough_cores(nproc)
     env = {"RAMSES_AMD": "1"}
     if ordered == "0":
         env["RAMSES_AMD_CG_ORDERED"] = "0"
-    workp, outp = _run(nml, PATCHED_MPI, nproc, env)
+    workp, outp = live.run(nml, PATCHED_MPI, nproc, env)
     try:
         assert "Entering phi_fine_cg" not in outp or "MI355X" in outp
-        sol_p = np.array([[int(a), int(b)] for a, b in re.findall(pat, outp)])
-        got = _sorted(rs.load_leaf_cells(os.path.join(workp, "output_00002"), with_grav=True))
+        sol_p = np.array([[int(a), int(b)] for a, b in live.poisson_solves(outp)])
+        got = live.leaves(workp, with_grav=True)
     finally:
         shutil.rmtree(workp, ignore_errors=True)
-    workr, outr = _run(nml, REF_MPI, nproc, {})
+    workr, outr = live.run(nml, REF_MPI, nproc, {})
     try:
-        sol_r = np.array([[int(a), int(b)] for a, b in re.findall(pat, outr)])
-        ref = _sorted(rs.load_leaf_cells(os.path.join(workr, "output_00002"), with_grav=True))
+        sol_r = np.array([[int(a), int(b)] for a, b in live.poisson_solves(outr)])
+        ref = live.leaves(workr, with_grav=True)
     finally:
         shutil.rmtree(workr, ignore_errors=True)
     assert len(sol_r) > 0 and {4, 5} <= set(int(l) for l in sol_r[:, 0])
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
     if ordered != "0":
         assert np.array_equal(sol_p, sol_r)
-        assert np.array_equal(got[3], ref[3]), np.abs(got[3] - ref[3]).max()     # phi, f
+        assert np.array_equal(got.grav, ref.grav), np.abs(got.grav - ref.grav).max()     # phi, f
         assert np.array_equal(got[2], ref[2]), np.abs(got[2] - ref[2]).max()     # hydro state
     else:
         assert sol_p.shape == sol_r.shape and np.abs(sol_p - sol_r).max() <= 1
-        assert np.abs(got[3] - ref[3]).max() <= 1e-9 * np.abs(ref[3]).max()
+        assert np.abs(got.grav - ref.grav).max() <= 1e-9 * np.abs(ref.grav).max()
         assert np.abs(got[2] - ref[2]).max() <= 1e-11 * np.abs(ref[2]).max()

@@ -7,38 +7,16 @@ layers, one deep-halo exchange per smoother launch instead of one per colour pas
 messages through the program's own MPI on the library's pinned buffers (the ranks share the test box's one GPU).
 V-cycle counts, phi, f and the hydro state must equal the untouched MPI reference on the same number of ranks; with
 RAMSES_AMD_MG_DIST=0 the same run takes the multigrid of AMR levels (round 3's path) and must give the same."""
-import importlib.util
 import os
+import re
 import shutil
 
 import numpy as np
 import pytest
 
+import live
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi")
-PATCHED_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi_patch")
-
-
-def _mkb():
-    spec = importlib.util.spec_from_file_location("mkb", os.path.join(ROOT, "tests", "golden", "make_golden_baseline.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _run(nml, binary, nproc, env):
-    from oracle import ramses_snapshot as rs
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return rs.run_reference(nml, binary=binary, nproc=nproc)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 _REF = {}
@@ -48,9 +26,9 @@ def _reference(nml, nproc, level):
     """the MPI reference on nproc ranks (once per rank count)"""
     from oracle import ramses_snapshot as rs
     if (level, nproc) not in _REF:
-        work, out = _run(nml, REF_MPI, nproc, {"RAMSES_AMD": "0"})
+        work, out = live.run(nml, live.binaries(True)[1], nproc, {"RAMSES_AMD": "0"})
         try:
-            _REF[(level, nproc)] = (rs.load_uniform_level(os.path.join(work, "output_00002"), level, with_grav=True), _mkb().solves(out))
+            _REF[(level, nproc)] = (rs.load_uniform_level(os.path.join(work, "output_00002"), level, with_grav=True), live.golden_module("baseline").solves(out))
         finally:
             shutil.rmtree(work, ignore_errors=True)
     return _REF[(level, nproc)]
@@ -60,15 +38,13 @@ def _reference(nml, nproc, level):
 def test_uniform_self_gravity_under_mpi_equals_the_mpi_reference(gpu_lib, level, nproc, dist):
     """level 7: 128^3 (one distributed level above the replicated ones on 8 ranks); level 8 on 8 ranks: BASELINE config C4
     as stated (256^3) under MPI, 128^3 bricks, two distributed levels."""
-    if not (os.path.exists(REF_MPI) and os.path.exists(PATCHED_MPI)):
-        pytest.skip("oracle/_ref/ramses3d_mpi[_patch] not built")
-    if nproc > (os.cpu_count() or 1):
-        pytest.skip("fewer cores than ranks")
+    PATCHED_MPI, REF_MPI = live.binaries(True)
+    live.enough_cores(nproc)
     from oracle import ramses_snapshot as rs
-    mkb = _mkb()
+    mkb = live.golden_module("baseline")
     nml = mkb.c4_namelist(level=level).replace("ngridtot=", "ngridtot=%d !" % (3 * sum(8 ** l for l in range(level)) + 1000))
     ref, ref_solves = _reference(nml, nproc, level)
-    work, out = _run(nml, PATCHED_MPI, nproc, {"RAMSES_AMD": "1", "RAMSES_AMD_MG_DIST": dist, "RAMSES_AMD_STATS": "1"})
+    work, out = live.run(nml, PATCHED_MPI, nproc, {"RAMSES_AMD": "1", "RAMSES_AMD_MG_DIST": dist, "RAMSES_AMD_STATS": "1"})
     try:
         got = rs.load_uniform_level(os.path.join(work, "output_00002"), level, with_grav=True)
         got_solves = mkb.solves(out)
@@ -77,8 +53,7 @@ def test_uniform_self_gravity_under_mpi_equals_the_mpi_reference(gpu_lib, level,
     # round 6: the acceleration of a uniform self-gravitating run never crosses PCIe after the
     # first load -- force_fine files it from the brick (or from the force kernel's buffer) into the resident array, the
     # virtual octs are exchanged there; what goes down is backup_poisson's fetch for the snapshot, once per oct and output
-    import re
-    traffic = [[int(a), int(b)] for a, b in re.findall(r"acceleration f over PCIe:\s*(\d+) bytes to the device,\s*(\d+) bytes back", out)]
+    traffic = live.f_traffic(out)
     assert len(traffic) == nproc, out[-2000:]
     octs = 8 ** (level - 1)
     up, down = sum(t[0] for t in traffic), sum(t[1] for t in traffic)
@@ -101,15 +76,15 @@ def test_uniform_self_gravity_under_mpi_equals_the_mpi_reference(gpu_lib, level,
         assert rho_down <= 3 * 1.6 * 8 * cells, (rho_down, cells)
     if (level, nproc, dist) == (7, 2, "1"):
         # ... whatever the number of steps: twice as many steps, the same bytes
-        work2, out2 = _run(nml.replace("nstepmax=3", "nstepmax=6").replace("foutput=3", "foutput=6"), PATCHED_MPI, nproc,
+        work2, out2 = live.run(nml.replace("nstepmax=3", "nstepmax=6").replace("foutput=3", "foutput=6"), PATCHED_MPI, nproc,
                            {"RAMSES_AMD": "1", "RAMSES_AMD_MG_DIST": dist, "RAMSES_AMD_STATS": "1"})
         shutil.rmtree(work2, ignore_errors=True)
         assert "nstepmax=3" in nml and "Main step=      6" in out2, out2[-1500:]
-        traffic2 = [[int(a), int(b)] for a, b in re.findall(r"acceleration f over PCIe:\s*(\d+) bytes to the device,\s*(\d+) bytes back", out2)]
+        traffic2 = live.f_traffic(out2)
         assert sum(t[0] for t in traffic2) == up, (traffic2, traffic)
         assert poisson_traffic(out2) == poisson_traffic(out), (poisson_traffic(out2), poisson_traffic(out))
         # and the switch gives the path before round 6 back: a brick of rho up and one of phi back per solve
-        work3, out3 = _run(nml, PATCHED_MPI, nproc, {"RAMSES_AMD": "1", "RAMSES_AMD_MG_DIST": dist, "RAMSES_AMD_STATS": "1", "RAMSES_AMD_PHI_RESIDENT": "0"})
+        work3, out3 = live.run(nml, PATCHED_MPI, nproc, {"RAMSES_AMD": "1", "RAMSES_AMD_MG_DIST": dist, "RAMSES_AMD_STATS": "1", "RAMSES_AMD_PHI_RESIDENT": "0"})
         try:
             got3 = rs.load_uniform_level(os.path.join(work3, "output_00002"), level, with_grav=True)
         finally:
@@ -135,33 +110,25 @@ def test_amr_run_with_a_fully_refined_levelmin_under_mpi(gpu_lib):
     driver, device operators, first guess and boundary values interpolated from the level-7 phi the dense solve left on
     the host), the hydro state stays resident on the GPUs -- leaf cells, phi, f and the V-cycle counts of every level must
     equal the MPI reference."""
-    if not (os.path.exists(REF_MPI) and os.path.exists(PATCHED_MPI)):
-        pytest.skip("oracle/_ref/ramses3d_mpi[_patch] not built")
-    if (os.cpu_count() or 1) < 2:
-        pytest.skip("fewer cores than ranks")
-    import re
+    PATCHED_MPI, REF_MPI = live.binaries(True)
+    live.enough_cores(2)
     from oracle import ramses_snapshot as rs
-    nml = _mkb().amr_grav_namelist(lmin=7, lmax=8, nstep=2)
+    nml = live.golden_module("baseline").amr_grav_namelist(lmin=7, lmax=8, nstep=2)
 
-    def leaves(work):
-        snap = rs.load_leaf_cells(os.path.join(work, "output_00002"), with_grav=True)
-        order = np.lexsort((snap["x"][:, 0], snap["x"][:, 1], snap["x"][:, 2], snap["level"]))
-        return snap["level"][order], snap["x"][order], snap["prim"][:, order], snap["grav"][:, order]
-
-    work, out = _run(nml, PATCHED_MPI, 2, {"RAMSES_AMD": "1"})
+    work, out = live.run(nml, PATCHED_MPI, 2, {"RAMSES_AMD": "1"})
     try:
         assert "distributed over" in out, out[-2000:]
-        got = leaves(work)
-        sol_p = re.findall(r"==> Level=\s*(\d+) Step=\s*(\d+)", out)
+        got = live.leaves(work, with_grav=True)
+        sol_p = live.poisson_solves(out)
     finally:
         shutil.rmtree(work, ignore_errors=True)
-    work, out = _run(nml, REF_MPI, 2, {"RAMSES_AMD": "0"})
+    work, out = live.run(nml, REF_MPI, 2, {"RAMSES_AMD": "0"})
     try:
-        ref = leaves(work)
-        sol_r = re.findall(r"==> Level=\s*(\d+) Step=\s*(\d+)", out)
+        ref = live.leaves(work, with_grav=True)
+        sol_r = live.poisson_solves(out)
     finally:
         shutil.rmtree(work, ignore_errors=True)
     assert (got[0] == 8).any() and sol_p == sol_r, (sol_p, sol_r)
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
-    assert np.array_equal(got[3], ref[3]), np.abs(got[3] - ref[3]).max()     # phi, f
+    assert np.array_equal(got.grav, ref.grav), np.abs(got.grav - ref.grav).max()     # phi, f
     assert np.array_equal(got[2], ref[2]), np.abs(got[2] - ref[2]).max()     # hydro state

@@ -3,7 +3,6 @@ ramses_amd/patch as its PATCH= directory) must run the untouched reference routi
 shim (godunov_fine, set_unew/set_uold, courant_fine, synchro_hydro_fine, rho_fine, multigrid_fine and
 its compute routines, phi_fine_cg, force_fine, backup_hydro) -- the A/B switch of INTEGRATION.md.
 No GPU is touched, so this runs in the CPU suite: snapshots must equal the reference's goldens."""
-import importlib.util
 import os
 import re
 import shutil
@@ -12,34 +11,20 @@ import sys
 import numpy as np
 import pytest
 
+import live
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATCHED = os.path.join(ROOT, "oracle", "_ref", "ramses3d_patch")
 
 
-def _load(path, name):
-    spec = importlib.util.spec_from_file_location(name, path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def _run(nml):
-    sys.path.insert(0, ROOT)
     from oracle import ramses_snapshot as rs
-    old = os.environ.get("RAMSES_AMD")
-    os.environ["RAMSES_AMD"] = "0"
-    try:
-        return rs, rs.run_reference(nml, binary=PATCHED)
-    finally:
-        if old is None:
-            os.environ.pop("RAMSES_AMD", None)
-        else:
-            os.environ["RAMSES_AMD"] = old
+    return rs, live.run(nml, PATCHED, 1, {"RAMSES_AMD": "0"})
 
 
 @pytest.mark.skipif(not os.path.exists(PATCHED), reason="oracle/_ref/ramses3d_patch not built")
 def test_uniform_self_gravity_three_steps_through_the_reference_routines():
-    mkp = _load(os.path.join(ROOT, "tests", "golden", "make_golden_poisson.py"), "mkp")
+    mkp = live.load_module(os.path.join(ROOT, "tests", "golden", "make_golden_poisson.py"), "mkp")
     key, level, boxlen, eps, blob = mkp.CASES[-1]
     z = np.load(os.path.join(ROOT, "tests", "golden", "poisson_ref_runs.npz"))
     sys.path.insert(0, ROOT)
@@ -61,7 +46,7 @@ def test_uniform_self_gravity_three_steps_through_the_reference_routines():
 
 @pytest.mark.skipif(not os.path.exists(PATCHED), reason="oracle/_ref/ramses3d_patch not built")
 def test_amr_self_gravity_with_cg_levels_through_the_reference_routines():
-    mk = _load(os.path.join(ROOT, "tests", "golden", "make_golden_cg.py"), "mkcg")
+    mk = live.load_module(os.path.join(ROOT, "tests", "golden", "make_golden_cg.py"), "mkcg")
     z = np.load(os.path.join(ROOT, "tests", "golden", "cg_ref.npz"))
     rs, (work, out) = _run(mk.cg_namelist())
     try:
@@ -84,7 +69,7 @@ MPI_PATCHED = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi_patch")
 def test_mpi_build_through_the_reference_routines():
     """The MPI build of the patched program on two ranks with RAMSES_AMD=0 (AMR run): the snapshot of
     the unmodified MPI reference."""
-    mka = _load(os.path.join(ROOT, "tests", "golden", "make_golden_amr.py"), "mka")
+    mka = live.load_module(os.path.join(ROOT, "tests", "golden", "make_golden_amr.py"), "mka")
     tag, nproc, nml, nstep = [c for c in mka.MPI_CASES() if c[1] == 2][0]
     z = np.load(os.path.join(ROOT, "tests", "golden", "amr_godunov_ref.npz"))
     sys.path.insert(0, ROOT)
@@ -113,17 +98,18 @@ def test_mpi_amr_run_with_load_balancing_through_the_reference_routines():
     """RAMSES_AMD=0 under MPI on an AMR run with nremap=1: the shims of load_balance, build_comm,
     make_virtual_fine_dp / make_virtual_reverse_dp, refine_fine, set_unew and courant_fine all take their
     reference branch -- leaf cells equal the untouched MPI reference (live, 2 ranks)."""
-    t = _load(os.path.join(ROOT, "tests", "test_mpi_amr_resident_gpu.py"), "tmpi")
+    t = live.load_module(os.path.join(ROOT, "tests", "test_mpi_amr_resident_gpu.py"), "tmpi")
     nml = t._namelist(3, 5, "1,1,2,2", "llf", 1, 5, t.OFF_CENTRE, nremap=1)
-    workp, outp = t._run(nml, t.PATCHED_MPI, 2, {"RAMSES_AMD": "0"})
+    patched_mpi, ref_mpi = live.binaries(True)
+    workp, outp = live.run(nml, patched_mpi, 2, {"RAMSES_AMD": "0"})
     try:
         assert "resident on the GPU" not in outp and "Load balancing" in outp
-        got = t._leaves(workp, 2)
+        got = live.leaves(workp)
     finally:
         shutil.rmtree(workp, ignore_errors=True)
-    workr, outr = t._run(nml, t.REF_MPI, 2, {})
+    workr, outr = live.run(nml, ref_mpi, 2, {})
     try:
-        ref = t._leaves(workr, 2)
+        ref = live.leaves(workr)
     finally:
         shutil.rmtree(workr, ignore_errors=True)
     assert got[3] == ref[3] and len(set(int(l) for l in ref[0])) >= 2
@@ -164,7 +150,7 @@ def test_mhd_patch_with_the_switch_off_is_the_reference_program():
 def test_amr_run_between_walls_through_the_reference_routines():
     """RAMSES_AMD=0 behind the round-4 shims too: hydro_boundary.f90 (make_boundary_hydro) and the boundary octs in the
     level lists -- the walls golden of tests/golden/make_golden_amr.py"""
-    mka = _load(os.path.join(ROOT, "tests", "golden", "make_golden_amr.py"), "mka")
+    mka = live.load_module(os.path.join(ROOT, "tests", "golden", "make_golden_amr.py"), "mka")
     z = np.load(os.path.join(ROOT, "tests", "golden", "amr_godunov_ref.npz"))
     rs, (work, out) = _run(mka.walls_namelist())
     try:

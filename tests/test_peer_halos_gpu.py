@@ -11,19 +11,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from resident import bits, i32, vp
+
 pytestmark = pytest.mark.gpu
 
 NGRIDMAX, NCOARSE = 64, 1
 NCELL = NCOARSE + 8 * NGRIDMAX
 BIG = 1e16
-
-
-def _i32(*v):
-    return (C.c_int * len(v))(*v)
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _tree():
@@ -33,10 +27,6 @@ def _tree():
 def _cells(octs):
     """cell indices (0-based) of the 8 cells of each oct, [8, n]"""
     return NCOARSE + np.arange(8)[:, None] * NGRIDMAX + (np.asarray(octs)[None, :] - 1)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
 
 
 class _Staged:
@@ -76,21 +66,21 @@ def test_amrres_halo_three_peers(gpu_lib):
     u0 = u.copy()
     allocts = np.arange(1, NGRIDMAX + 1, dtype=np.int32)
     em_all, rc_all = np.concatenate(em).astype(np.int32), np.concatenate(rc).astype(np.int32)
-    check(L.ramses_amd_amrres_load(nvar, NGRIDMAX, NCOARSE, _vp(u), _vp(son), _vp(nbor), _vp(father)))
+    check(L.ramses_amd_amrres_load(nvar, NGRIDMAX, NCOARSE, vp(u), vp(son), vp(nbor), vp(father)))
     try:
-        check(L.ramses_amd_amrres_comm_set(lvl, 1, 3, _i32(*[len(e) for e in em]), _vp(em_all), _i32(*[len(r) for r in rc]), _vp(rc_all)))
+        check(L.ramses_amd_amrres_comm_set(lvl, 1, 3, i32(*[len(e) for e in em]), vp(em_all), i32(*[len(r) for r in rc]), vp(rc_all)))
         exp = u0.copy()
 
         def message(vec, octs):      # buf[(v*8 + ind)*n + i] = vec(cell(ind, oct i), v)
             return vec[:, _cells(octs)].reshape(-1)
 
         # reverse on unew (= uold after set_unew): the reception octs go out, what arrives is added to the emission octs
-        check(L.ramses_amd_amrres_set_unew(NGRIDMAX, _vp(allocts)))
+        check(L.ramses_amd_amrres_set_unew(NGRIDMAX, vp(allocts)))
         S = _Staged()
         check(L.ramses_amd_amrres_halo_stage_out(lvl, 1, 3, *S.args()))
         assert list(S.so) == [0, 40 * 7, 40 * 7, 40 * 11] and list(S.ro) == [0, 40 * 6, 40 * 6, 40 * 12]
         for c in range(3):
-            assert np.array_equal(_bits(S.sent(c)), _bits(message(exp, rc[c])))
+            assert np.array_equal(bits(S.sent(c)), bits(message(exp, rc[c])))
         for c, big in ((0, BIG), (2, -BIG)):
             m = rng.standard_normal((nvar, 8, len(em[c])))
             m[:, :, list(em[c]).index(shared)] = big
@@ -103,25 +93,25 @@ def test_amrres_halo_three_peers(gpu_lib):
         check(L.ramses_amd_amrres_halo_stage_in(lvl, 1))
         assert L.ramses_amd_amrres_halo_stage_in(lvl, 1) != 0
         p = ramses_amd.make_params(nvar=nvar)
-        check(L.ramses_amd_amrres_set_uold(C.byref(p), NGRIDMAX, _vp(allocts)))       # uold = unew
+        check(L.ramses_amd_amrres_set_uold(C.byref(p), NGRIDMAX, vp(allocts)))       # uold = unew
 
         # forward on uold: the emission octs go out, what arrives replaces the reception octs
         S = _Staged()
         check(L.ramses_amd_amrres_halo_stage_out(lvl, 0, 3, *S.args()))
         assert list(S.so) == [0, 40 * 6, 40 * 6, 40 * 12] and list(S.ro) == [0, 40 * 7, 40 * 7, 40 * 11]
         for c in range(3):
-            assert np.array_equal(_bits(S.sent(c)), _bits(message(exp, em[c])))
+            assert np.array_equal(bits(S.sent(c)), bits(message(exp, em[c])))
         for c in (0, 2):
             m = rng.standard_normal((nvar, 8, len(rc[c])))
             S.arrive(c, m)
             exp[:, _cells(rc[c])] = m
         check(L.ramses_amd_amrres_halo_stage_in(lvl, 0))
-        check(L.ramses_amd_amrres_sync_all(_vp(u)))
+        check(L.ramses_amd_amrres_sync_all(vp(u)))
         got = u.copy()
     finally:
         check(L.ramses_amd_amrres_invalidate())
-    assert np.array_equal(_bits(got), _bits(exp))
-    assert not np.array_equal(_bits(got), _bits(u0))
+    assert np.array_equal(bits(got), bits(exp))
+    assert not np.array_equal(bits(got), bits(u0))
 
 
 @pytest.mark.parametrize("list_is_octs", [0, 1])
@@ -147,12 +137,12 @@ def test_mgamr_halo_three_peers(gpu_lib, list_is_octs):
     blocks = [(nact, 10), (0, 0), (nact + 10, 6)]                          # (first position, octs) of each peer's reception block
     st0, st1 = (C.c_int64 * 4)(), (C.c_int64 * 4)()
     check(L.ramses_amd_mgamr_force_sync(0))
-    check(L.ramses_amd_mgamr_begin(ilevel, NGRIDMAX, NCOARSE, _vp(son), _vp(nbor), _vp(father), _vp(lookup), _vp(flag2), _vp(phi), _vp(f),
-                                   ngrid, _vp(igrid)))
+    check(L.ramses_amd_mgamr_begin(ilevel, NGRIDMAX, NCOARSE, vp(son), vp(nbor), vp(father), vp(lookup), vp(flag2), vp(phi), vp(f),
+                                   ngrid, vp(igrid)))
     try:
         check(L.ramses_amd_mgamr_fine_active(nact))
         # (the own rank's entry of rc_n is not a reception block: whatever it says is ignored)
-        check(L.ramses_amd_mgamr_comm_set(ilevel, 3, 2, _i32(*[len(p) for p in pos]), _vp(em_list), list_is_octs, _i32(10, 24, 6)))
+        check(L.ramses_amd_mgamr_comm_set(ilevel, 3, 2, i32(*[len(p) for p in pos]), vp(em_list), list_is_octs, i32(10, 24, 6)))
         uu = phi0[cells]                                                   # the component on the device: u(i + (ind-1)*ngrid)
 
         def stage_out(d):
@@ -167,7 +157,7 @@ def test_mgamr_halo_three_peers(gpu_lib, list_is_octs):
         S = stage_out(0)
         assert list(S.so) == [0, 40, 40, 72] and list(S.ro) == [0, 80, 80, 128]
         for c in range(3):
-            assert np.array_equal(_bits(S.sent(c)), _bits(uu[:, pos[c] - 1].reshape(-1)))      # u(i + (ind-1)*n)
+            assert np.array_equal(bits(S.sent(c)), bits(uu[:, pos[c] - 1].reshape(-1)))      # u(i + (ind-1)*n)
         for c in (0, 2):
             m = rng.standard_normal((8, blocks[c][1]))
             S.arrive(c, m)
@@ -180,7 +170,7 @@ def test_mgamr_halo_three_peers(gpu_lib, list_is_octs):
         S = stage_out(1)
         assert list(S.so) == [0, 80, 80, 128] and list(S.ro) == [0, 40, 40, 72]
         for c in range(3):
-            assert np.array_equal(_bits(S.sent(c)), _bits(uu[:, blocks[c][0]:blocks[c][0] + blocks[c][1]].reshape(-1)))
+            assert np.array_equal(bits(S.sent(c)), bits(uu[:, blocks[c][0]:blocks[c][0] + blocks[c][1]].reshape(-1)))
         for c, big in ((0, BIG), (2, -BIG)):
             m = rng.standard_normal((8, len(pos[c])))
             m[:, list(pos[c]).index(shared)] = big
@@ -193,9 +183,9 @@ def test_mgamr_halo_three_peers(gpu_lib, list_is_octs):
         check(L.ramses_amd_mgamr_end())       # phi of the whole layout goes home
     exp = phi0.copy()
     exp[cells] = uu
-    assert np.array_equal(_bits(phi), _bits(exp))
-    assert not np.array_equal(_bits(phi), _bits(phi0))
-    assert np.array_equal(_bits(f), _bits(f0))
+    assert np.array_equal(bits(phi), bits(exp))
+    assert not np.array_equal(bits(phi), bits(phi0))
+    assert np.array_equal(bits(f), bits(f0))
 
 
 def test_cgmpi_comm_set_between_the_stages_closes_the_exchange(gpu_lib):
@@ -209,17 +199,17 @@ def test_cgmpi_comm_set_between_the_stages_closes_the_exchange(gpu_lib):
     phi, f, out2 = rng.standard_normal(NCELL), rng.standard_normal((3, NCELL)), np.zeros(2)
     f0 = f.copy()
     em, rc = np.array([1, 2, 3, 2], np.int32), np.array([30, 31, 32], np.int32)
-    check(L.ramses_amd_cgmpi_begin(2, 20, _vp(igrid), _vp(son), _vp(nbor), NGRIDMAX, NCOARSE, _vp(phi), _vp(f), None, 0.0, 1.0, 0, _vp(out2)))
+    check(L.ramses_amd_cgmpi_begin(2, 20, vp(igrid), vp(son), vp(nbor), NGRIDMAX, NCOARSE, vp(phi), vp(f), None, 0.0, 1.0, 0, vp(out2)))
     try:
-        check(L.ramses_amd_cgmpi_comm_set(3, _i32(3, 0, 1), _vp(em), _i32(2, 0, 1), _vp(rc)))
+        check(L.ramses_amd_cgmpi_comm_set(3, i32(3, 0, 1), vp(em), i32(2, 0, 1), vp(rc)))
         S = _Staged()
         check(L.ramses_amd_cgmpi_p_halo_stage_out(3, *S.args()))
-        check(L.ramses_amd_cgmpi_comm_set(5, _i32(1, 0, 1, 1, 1), _vp(em), _i32(1, 0, 1, 0, 1), _vp(rc)))
+        check(L.ramses_amd_cgmpi_comm_set(5, i32(1, 0, 1, 1, 1), vp(em), i32(1, 0, 1, 0, 1), vp(rc)))
         assert L.ramses_amd_cgmpi_p_halo_stage_in() != 0
         assert b"cgmpi_p_halo_stage_in without cgmpi_p_halo_stage_out" in L.ramses_amd_last_error()
     finally:
-        check(L.ramses_amd_cgmpi_end(_vp(phi), _vp(f)))
-    assert np.array_equal(_bits(f), _bits(f0))
+        check(L.ramses_amd_cgmpi_end(vp(phi), vp(f)))
+    assert np.array_equal(bits(f), bits(f0))
 
 
 def test_cgmpi_p_halo_three_peers(gpu_lib):
@@ -238,16 +228,16 @@ def test_cgmpi_p_halo_three_peers(gpu_lib):
     phi0, f0 = phi.copy(), f.copy()
     out2 = np.zeros(2)
     em_all, rc_all = np.concatenate(em).astype(np.int32), np.concatenate(rc).astype(np.int32)
-    check(L.ramses_amd_cgmpi_begin(2, ngrid, _vp(igrid), _vp(son), _vp(nbor), NGRIDMAX, NCOARSE, _vp(phi), _vp(f), None, 0.0, 1.0, 0, _vp(out2)))
+    check(L.ramses_amd_cgmpi_begin(2, ngrid, vp(igrid), vp(son), vp(nbor), NGRIDMAX, NCOARSE, vp(phi), vp(f), None, 0.0, 1.0, 0, vp(out2)))
     ended = False
     try:
-        check(L.ramses_amd_cgmpi_comm_set(3, _i32(7, 0, 5), _vp(em_all), _i32(6, 0, 4), _vp(rc_all)))
+        check(L.ramses_amd_cgmpi_comm_set(3, i32(7, 0, 5), vp(em_all), i32(6, 0, 4), vp(rc_all)))
         S = _Staged()
         check(L.ramses_amd_cgmpi_p_halo_stage_out(3, *S.args()))
         assert list(S.so) == [0, 56, 56, 96] and list(S.ro) == [0, 48, 48, 80]
         exp = f0.copy()
         for c in range(3):
-            assert np.array_equal(_bits(S.sent(c)), _bits(f0[1][_cells(em[c])].reshape(-1)))      # f(:,2) = p at the emission cells
+            assert np.array_equal(bits(S.sent(c)), bits(f0[1][_cells(em[c])].reshape(-1)))      # f(:,2) = p at the emission cells
         for c in (0, 2):
             m = rng.standard_normal((8, len(rc[c])))
             S.arrive(c, m)
@@ -256,12 +246,12 @@ def test_cgmpi_p_halo_three_peers(gpu_lib):
         rc2 = L.ramses_amd_cgmpi_p_halo_stage_in()
         assert rc2 != 0 and b"cgmpi_p_halo_stage_in without cgmpi_p_halo_stage_out" in L.ramses_amd_last_error()
         ended = True
-        check(L.ramses_amd_cgmpi_end(_vp(phi), _vp(f)))
+        check(L.ramses_amd_cgmpi_end(vp(phi), vp(f)))
     finally:
         if not ended:
-            L.ramses_amd_cgmpi_end(_vp(phi), _vp(f))
-    assert np.array_equal(_bits(f[1]), _bits(exp[1]))
+            L.ramses_amd_cgmpi_end(vp(phi), vp(f))
+    assert np.array_equal(bits(f[1]), bits(exp[1]))
     changed = np.zeros(NCELL, bool)
     changed[_cells(rc_all).reshape(-1)] = True
-    assert np.all(_bits(f[1])[changed] != _bits(f0[1])[changed]) and np.array_equal(_bits(f[1])[~changed], _bits(f0[1])[~changed])
-    assert np.array_equal(_bits(phi), _bits(phi0)) and np.array_equal(_bits(f[0]), _bits(f0[0])) and np.array_equal(_bits(f[2]), _bits(f0[2]))
+    assert np.all(bits(f[1])[changed] != bits(f0[1])[changed]) and np.array_equal(bits(f[1])[~changed], bits(f0[1])[~changed])
+    assert np.array_equal(bits(phi), bits(phi0)) and np.array_equal(bits(f[0]), bits(f0[0])) and np.array_equal(bits(f[2]), bits(f0[2]))

@@ -5,131 +5,35 @@ hydro/godunov_fine.f90:720-747 (the two face quantities reset at refined interfa
 ADDED to what the vectors hold), :798-908 (what the level owes to the leaf cells of the coarser one).  Built like
 tests/test_amr_tiles_gpu.py: level 6 complete, level 7 a spherical shell with refined cells on the periodic seam, both in tiles."""
 import ctypes as C
-import importlib.util
-import os
-import re
-import shutil
 
 import numpy as np
 import pytest
 
+import live
+import resident as R
+from helpers import mild_tree_state, oct_cells
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 L = 6
-LAYOUT_VARS = ("RAMSES_AMD_DEVICE_ORDER", "RAMSES_AMD_TILES", "RAMSES_AMD_TILE_DENSE", "RAMSES_AMD_COVERED_DENSE", "RAMSES_AMD_TILE_SWEEP")
 
 
 @pytest.fixture(autouse=True)
 def _dense_sweep_on_small_levels_too(monkeypatch):
-    """(levels below RAMSES_AMD_TILE_MIN_OCTS octs take the tree-walking sweep in production: the tests force the tiles)"""
-    monkeypatch.setenv("RAMSES_AMD_TILE_MIN_OCTS", "0")
-    for var in LAYOUT_VARS:
-        monkeypatch.delenv(var, raising=False)
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _shell_mask(nc, lo=0.23, hi=0.36, seam=True):
-    z, y, x = np.meshgrid(np.arange(nc), np.arange(nc), np.arange(nc), indexing="ij")
-    r = np.sqrt((x - nc / 2 + 0.5) ** 2 + (y - nc / 2 + 0.5) ** 2 + (z - nc / 2 + 0.5) ** 2)
-    mask = (r >= lo * nc) & (r <= hi * nc)
-    if seam:
-        mask[0, 0, :5] = True              # refined cells on the periodic seam too (tiles wrap)
-        mask[nc - 1, nc - 1, nc - 3:] = True
-    return mask
+    R.force_tiles(monkeypatch)
 
 
 def _tree(order):
-    from ramses_amd import ic
-    T = ic.uniform_tree(L, order=order, refine_mask=_shell_mask(2 ** L), slack=260000)
-    T["all_octs"] = {L: np.ascontiguousarray(np.sort(T["igrid"])), L + 1: np.ascontiguousarray(np.sort(T["igrid_fine"]))}
-    T["lists"] = {L: np.ascontiguousarray(T["igrid"]), L + 1: np.ascontiguousarray(T["igrid_fine"])}
-    return T
+    return R.two_level_tree(L, order)
 
 
 def _cells(T, lev):
-    return np.concatenate([T["ncoarse"] + ind * T["ngridmax"] + T["lists"][lev] - 1 for ind in range(8)])
-
-
-def _random_state(T, seed, nvar=5):
-    rng = np.random.default_rng(seed)
-    ncell = T["ncell"]
-    uold = np.zeros((nvar, ncell))
-    n = ncell - 1
-    uold[0, 1:] = 1.0 + rng.random(n)
-    for d in (1, 2, 3):
-        uold[d, 1:] = uold[0, 1:] * (rng.random(n) - 0.5)
-    uold[4, 1:] = 1.0 + rng.random(n) + 0.5 * (uold[1, 1:] ** 2 + uold[2, 1:] ** 2 + uold[3, 1:] ** 2) / uold[0, 1:]
-    for v in range(5, nvar):
-        uold[v, 1:] = uold[0, 1:] * rng.random(n)          # passive scalars: density x a fraction in [0, 1)
-    uold[:, 0] = uold[:, 1]
-    return uold
+    return oct_cells(T, T["lists"][lev])
 
 
 def _load(Lb, p, T, u, f):
     """load, enable_pfix, set_unew_pfix on both levels; returns the device's divu / enew after it (host vectors)"""
-    from ramses_amd._capi import check
-    check(Lb.ramses_amd_amrres_invalidate())
-    check(Lb.ramses_amd_amrres_load(u.shape[0], T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
-    if f is not None:
-        for lev in (L, L + 1):
-            check(Lb.ramses_amd_amrres_load_f(len(T["all_octs"][lev]), _vp(T["all_octs"][lev]), _vp(f)))
-    check(Lb.ramses_amd_amrres_enable_pfix())
-    T["host_u"] = u                       # (ramses_amd_amrres_sync_level writes into the array the state was loaded from)
-    return _set_unew(Lb, p, T)
-
-
-def _set_unew(Lb, p, T):
-    from ramses_amd._capi import check
-    divu, enew = np.zeros(T["ncell"]), np.zeros(T["ncell"])
-    for lev in (L, L + 1):
-        ig = T["all_octs"][lev]
-        check(Lb.ramses_amd_amrres_set_unew_pfix(C.byref(p), len(ig), _vp(ig)))
-        check(Lb.ramses_amd_amrres_sync_pfix(len(ig), _vp(ig), _vp(divu), _vp(enew)))
-    return divu, enew
-
-
-def _sweep(Lb, p, T, lev, ivar, itype, dtfac=0.02):
-    from ramses_amd._capi import check
-    ig = T["lists"][lev]
-    dx = 1.0 / 2 ** lev
-    check(Lb.ramses_amd_amrres_godunov(C.byref(p), lev, len(ig), _vp(ig), dx, dtfac * dx, 32, ivar, itype))
-
-
-def _read_back(Lb, p, T, nvar):
-    """unew (through the plain set_uold = a copy, and sync_level), divu, enew of both levels"""
-    from ramses_amd._capi import check
-    u, divu, enew = T["host_u"], np.zeros(T["ncell"]), np.zeros(T["ncell"])
-    assert u.shape[0] == nvar
-    for lev in (L, L + 1):
-        ig = T["all_octs"][lev]
-        check(Lb.ramses_amd_amrres_sync_pfix(len(ig), _vp(ig), _vp(divu), _vp(enew)))
-        check(Lb.ramses_amd_amrres_set_uold(C.byref(p), len(ig), _vp(ig)))
-        check(Lb.ramses_amd_amrres_sync_level(len(ig), _vp(ig), _vp(u)))
-    return u, divu, enew
-
-
-def _oracle_sweep(oracle, po, T, lev, uold, unew, divu, enew, f, ivar, itype, dtfac=0.02):
-    dx = 1.0 / 2 ** lev
-    oracle.godunov_fine_amr(po, T["lists"][lev], T["son"], T["nbor"], T["father"], T["ngridmax"], T["ncoarse"], uold, unew, dx, dtfac * dx, 32,
-                            ivar, itype, f=f, divu=divu, enew=enew)
-
-
-def _compare(got, ref, cells, exact_solver):
-    """bit for bit; riemann = 'exact' calls pow(), whose last ulp is the device's: relative 1e-12, as the tile tests without
-    pressure_fix do"""
-    for name, g, r in zip(("unew", "divu", "enew"), got, ref):
-        g, r = g[..., cells], r[..., cells]
-        if exact_solver:
-            scale = np.abs(r).max(axis=-1, keepdims=True)
-            err = (np.abs(g - r) / scale).max()
-            print(name, "max relative difference", err)
-            assert err <= 1e-12, (name, err)
-        else:
-            print(name, "cells that differ", int((g != r).sum()), "max abs difference", np.abs(g - r).max())
-            assert np.array_equal(g, r), (name, np.abs(g - r).max())
+    R.load(Lb, T, u, f, pfix=True)
+    return R.set_unew(Lb, p, T, pfix=True)
 
 
 CASES = [
@@ -155,27 +59,24 @@ def test_pressure_fix_levels_in_tiles_equal_the_oracle(gpu_lib, oracle, nvar, ri
     commit both walked the tree: that assertion failed there)"""
     import ramses_amd
     T = _tree(order)
-    uold = _random_state(T, 11, nvar=nvar)
+    uold = mild_tree_state(T, 11, nvar=nvar)
     f = np.random.default_rng(5).normal(size=(3, T["ncell"])) if grav else None
     kw = dict(riemann=riemann, slope_type=slope, nvar=nvar)
     p, po = ramses_amd.make_params(fast_math=fast, **kw), oracle.make_params(**kw)
-    divu0, enew0 = _load(gpu_lib, p, T, uold.copy(), f)
+    u = uold.copy()
+    divu0, enew0 = _load(gpu_lib, p, T, u, f)
     assert gpu_lib.ramses_amd_amrres_tiled_levels() == 2
-    unew, divu, enew = uold.copy(), divu0.copy(), enew0.copy()
-    for lev in (L + 1, L):
-        _oracle_sweep(oracle, po, T, lev, uold, unew, divu, enew, f, *interp)
-    t0, w0 = gpu_lib.ramses_amd_amrres_tile_sweeps(), gpu_lib.ramses_amd_amrres_tree_sweeps()
-    for lev in (L + 1, L):
-        _sweep(gpu_lib, p, T, lev, *interp)
-    dt_, dw_ = gpu_lib.ramses_amd_amrres_tile_sweeps() - t0, gpu_lib.ramses_amd_amrres_tree_sweeps() - w0
-    got = _read_back(gpu_lib, p, T, nvar)
+    divu, enew = divu0.copy(), enew0.copy()
+    unew = R.oracle_step(oracle, po, T, uold, f, interp, divu, enew)
+    counts = R.sweep_levels(gpu_lib, p, T, interp)
+    got = R.read_back(gpu_lib, p, T, u, pfix=True)
     gpu_lib.ramses_amd_amrres_invalidate()
-    assert (dt_, dw_) == (2, 0), "sweeps through the tiles / through the tree: %d / %d" % (dt_, dw_)
+    assert counts == (2, 0), "sweeps through the tiles / through the tree: %d / %d" % counts
     c7, c6 = _cells(T, L + 1), _cells(T, L)
     # not vacuous (from the oracle alone): the vectors are populated; refined level-6 cells keep 0 (their interfaces are reset)
     assert (divu[c7] != 0).mean() > 0.9 and (divu[c6] != 0).mean() > 0.7
     assert (enew[c7] != enew0[c7]).mean() > 0.9
-    _compare(got, (unew, divu, enew), np.concatenate([c6, c7]), riemann == "exact")
+    R.compare(got, (unew, divu, enew), np.concatenate([c6, c7]), riemann == "exact")
 
 
 def test_the_oracle_case_is_not_vacuous(gpu_lib, oracle):
@@ -184,39 +85,39 @@ def test_the_oracle_case_is_not_vacuous(gpu_lib, oracle):
     instead of accumulating cannot equal the oracle.  Then the device, on the same case, cell by cell in those cells."""
     import ramses_amd
     T = _tree("scrambled")
-    uold = _random_state(T, 11)
+    uold = mild_tree_state(T, 11)
     kw = dict(riemann="hllc", slope_type=1)
     p, po = ramses_amd.make_params(**kw), oracle.make_params(**kw)
-    divu0, enew0 = _load(gpu_lib, p, T, uold.copy(), None)
+    u = uold.copy()
+    divu0, enew0 = _load(gpu_lib, p, T, u, None)
     c7, c6 = _cells(T, L + 1), _cells(T, L)
     leaf6 = c6[T["son"][c6] == 0]
     # level 7 alone
     u7, d7, e7 = uold.copy(), divu0.copy(), enew0.copy()
-    _oracle_sweep(oracle, po, T, L + 1, uold, u7, d7, e7, None, 0, 1)
+    R.oracle_sweep(oracle, po, T, L + 1, uold, u7, 0, 1, divu=d7, enew=e7)
     corrected = leaf6[(d7[leaf6] != divu0[leaf6]) & (e7[leaf6] != enew0[leaf6])]
     print("level-6 leaf cells corrected by the level-7 call:", len(corrected))
     assert len(corrected) > 1000
     # 7 then 6 against 6 alone
     u76, d76, e76 = u7.copy(), d7.copy(), e7.copy()
-    _oracle_sweep(oracle, po, T, L, uold, u76, d76, e76, None, 0, 1)
+    R.oracle_sweep(oracle, po, T, L, uold, u76, 0, 1, divu=d76, enew=e76)
     u6, d6, e6 = uold.copy(), divu0.copy(), enew0.copy()
-    _oracle_sweep(oracle, po, T, L, uold, u6, d6, e6, None, 0, 1)
+    R.oracle_sweep(oracle, po, T, L, uold, u6, 0, 1, divu=d6, enew=e6)
     differ = (d76[corrected] != d6[corrected]) & (e76[corrected] != e6[corrected])
     print("of them order-dependent:", int(differ.sum()))
     assert differ.sum() > 1000
     print("divu != 0: level 7 %.4f, level 6 %.4f" % ((d76[c7] != 0).mean(), (d76[c6] != 0).mean()))
     assert (d76[c7] != 0).mean() > 0.9 and (d76[c6] != 0).mean() > 0.7
-    for lev in (L + 1, L):
-        _sweep(gpu_lib, p, T, lev, 0, 1)
-    got = _read_back(gpu_lib, p, T, 5)
+    R.sweep_levels(gpu_lib, p, T, (0, 1))
+    got = R.read_back(gpu_lib, p, T, u, pfix=True)
     gpu_lib.ramses_amd_amrres_invalidate()
-    _compare(got, (u76, d76, e76), corrected, False)
-    _compare(got, (u76, d76, e76), np.concatenate([c6, c7]), False)
+    R.compare(got, (u76, d76, e76), corrected, False)
+    R.compare(got, (u76, d76, e76), np.concatenate([c6, c7]), False)
 
 
 def _cold_supersonic_state(T, seed):
     """the random state with a cold, supersonic region (thermal energy 1e-6 of the kinetic): where set_uold's energy switch fires"""
-    u = _random_state(T, seed)
+    u = mild_tree_state(T, seed)
     n = T["ncell"]
     cold = np.zeros(n, bool)
     cold[1:] = np.random.default_rng(seed + 1).random(n - 1) < 0.3
@@ -239,16 +140,13 @@ def _two_steps(Lb, p, T, u0, beta_fix, tile_sweep, monkeypatch):
     dtfac = 0.002
     for step in range(2):
         if step:
-            _set_unew(Lb, p, T)
-        for lev in (L + 1, L):
-            _sweep(Lb, p, T, lev, 0, 1, dtfac)
+            R.set_unew(Lb, p, T, pfix=True)
+        R.sweep_levels(Lb, p, T, (0, 1), dtfac)
         for lev in (L, L + 1):
             ig = T["all_octs"][lev]
             dx = 1.0 / 2 ** lev
-            check(Lb.ramses_amd_amrres_set_uold_pfix(C.byref(p), len(ig), _vp(ig), dtfac * dx, dx, beta_fix, 0.0))
-    for lev in (L, L + 1):
-        ig = T["all_octs"][lev]
-        check(Lb.ramses_amd_amrres_sync_level(len(ig), _vp(ig), _vp(u)))
+            check(Lb.ramses_amd_amrres_set_uold_pfix(C.byref(p), len(ig), R.vp(ig), dtfac * dx, dx, beta_fix, 0.0))
+    R.sync(Lb, T, u)
     counts = (Lb.ramses_amd_amrres_tile_sweeps() - t0, Lb.ramses_amd_amrres_tree_sweeps() - w0)
     Lb.ramses_amd_amrres_invalidate()
     monkeypatch.delenv("RAMSES_AMD_TILE_SWEEP", raising=False)
@@ -281,12 +179,12 @@ def test_sync_pfix_is_refused_before_pressure_fix_is_enabled(gpu_lib):
     import ramses_amd
     from ramses_amd._capi import check
     T = _tree("morton")
-    u = _random_state(T, 3)
+    u = mild_tree_state(T, 3)
     check(gpu_lib.ramses_amd_amrres_invalidate())
-    check(gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
+    check(gpu_lib.ramses_amd_amrres_load(5, T["ngridmax"], T["ncoarse"], R.vp(u), R.vp(T["son"]), R.vp(T["nbor"]), R.vp(T["father"])))
     ig = T["all_octs"][L]
     divu, enew = np.zeros(T["ncell"]), np.zeros(T["ncell"])
-    rc = gpu_lib.ramses_amd_amrres_sync_pfix(len(ig), _vp(ig), _vp(divu), _vp(enew))
+    rc = gpu_lib.ramses_amd_amrres_sync_pfix(len(ig), R.vp(ig), R.vp(divu), R.vp(enew))
     assert rc == -1 and b"pressure_fix not enabled" in gpu_lib.ramses_amd_last_error()
     gpu_lib.ramses_amd_amrres_invalidate()
 
@@ -297,105 +195,32 @@ def test_what_stays_on_the_tree_walker(gpu_lib, oracle, what):
     tree, results equal the oracle"""
     import ramses_amd
     T = _tree("scrambled")
-    uold = _random_state(T, 11)
+    uold = mild_tree_state(T, 11)
     kw = dict(riemann="llf", slope_type=1)
     kw.update({"scheme": "plmde"} if what == "plmde" else {"difmag": 0.05})
     p, po = ramses_amd.make_params(**kw), oracle.make_params(**kw)
-    divu0, enew0 = _load(gpu_lib, p, T, uold.copy(), None)
-    unew, divu, enew = uold.copy(), divu0.copy(), enew0.copy()
-    for lev in (L + 1, L):
-        _oracle_sweep(oracle, po, T, lev, uold, unew, divu, enew, None, 0, 1)
-    t0, w0 = gpu_lib.ramses_amd_amrres_tile_sweeps(), gpu_lib.ramses_amd_amrres_tree_sweeps()
-    for lev in (L + 1, L):
-        _sweep(gpu_lib, p, T, lev, 0, 1)
-    counts = (gpu_lib.ramses_amd_amrres_tile_sweeps() - t0, gpu_lib.ramses_amd_amrres_tree_sweeps() - w0)
-    got = _read_back(gpu_lib, p, T, 5)
+    u = uold.copy()
+    divu0, enew0 = _load(gpu_lib, p, T, u, None)
+    divu, enew = divu0.copy(), enew0.copy()
+    unew = R.oracle_step(oracle, po, T, uold, None, (0, 1), divu, enew)
+    counts = R.sweep_levels(gpu_lib, p, T, (0, 1))
+    got = R.read_back(gpu_lib, p, T, u, pfix=True)
     gpu_lib.ramses_amd_amrres_invalidate()
     assert counts == (0, 2), counts
-    _compare(got, (unew, divu, enew), np.concatenate([_cells(T, L), _cells(T, L + 1)]), False)
+    R.compare(got, (unew, divu, enew), np.concatenate([_cells(T, L), _cells(T, L + 1)]), False)
 
 
 # ---- live, end to end: the patched program against the untouched one -------------------------------------------------------
 
-def _mka():
-    spec = importlib.util.spec_from_file_location("mka", os.path.join(ROOT, "tests", "golden", "make_golden_amr.py"))
-    mka = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mka)
-    return mka
-
-
 def _namelist(lmin, lmax, riemann="hllc", nstep=4, poisson=False, ngridtot=400000):
-    from oracle import ramses_snapshot as rs
     riemann = riemann + "'\npressure_fix=.true.\nbeta_fix=0.5\n!'"
-    mka = _mka()
-    extra = mka.REFINE.format(ivar=0, itype=2) if lmax > lmin else ""
-    kw = {}
-    if poisson:
-        kw["init"] = mka.SELFGRAV_INIT
-        extra += "&POISSON_PARAMS\nepsilon=1e-5\n/\n"
-    nml = rs.sedov3d_namelist(level=lmin, nstepmax=nstep, foutput=nstep, riemann=riemann, slope_type=1, extra=extra, mem_factor=1.0, poisson=poisson, **kw)
-    nml = nml.replace("levelmax=%d" % lmin, "levelmax=%d" % lmax).replace("nsubcycle=10*1", "nsubcycle=1,1,1,1,1,2,2")
-    assert "pressure_fix=.true." in nml and "ngridtot=" in nml
-    return nml.replace("ngridtot=", "ngridtot=%d !" % ngridtot)
-
-
-def _run(nml, binary, nproc, env):
-    from oracle import ramses_snapshot as rs
-    old = {k: os.environ.get(k) for k in env}
-    for k, v in env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
-    try:
-        return rs.run_reference(nml, binary=binary, nproc=nproc)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _leaves(work):
-    from oracle import ramses_snapshot as rs
-    snap = rs.load_leaf_cells(os.path.join(work, "output_00002"))
-    order = np.lexsort((snap["x"][:, 0], snap["x"][:, 1], snap["x"][:, 2], snap["level"]))
-    return snap["level"][order], snap["prim"][:, order]
-
-
-def _sweep_counts(out):
-    m = re.search(r"godunov_fine of AMR levels:\s*(\d+) sweeps through the dense kernel on tiles.*?(\d+) through the tree-walking kernel", out)
-    assert m, out[-2000:]
-    return int(m.group(1)), int(m.group(2))
-
-
-def _binaries(mpi):
-    names = ("ramses3d_mpi_patch", "ramses3d_mpi") if mpi else ("ramses3d_patch", "ramses3d")
-    patched, ref = (os.path.join(ROOT, "oracle", "_ref", b) for b in names)
-    if not (os.path.exists(patched) and os.path.exists(ref)):
-        pytest.skip("oracle/_ref/%s, %s not built" % names)
-    return patched, ref
+    nml = live.amr_namelist(lmin, lmax, nstep, riemann, 1, "1,1,1,1,1,2,2", ngridtot, poisson=poisson)
+    assert "pressure_fix=.true." in nml
+    return nml
 
 
 def _live(nml, nproc, env, min_octs="0"):
-    patched, ref = _binaries(nproc > 1)
-    e = {"RAMSES_AMD": "1", "RAMSES_AMD_STRICT": "1", "RAMSES_AMD_STATS": "1", "RAMSES_AMD_TILE_MIN_OCTS": min_octs}
-    e.update(env)
-    work, out = _run(nml, patched, nproc, e)
-    try:
-        got = _leaves(work)
-    finally:
-        shutil.rmtree(work, ignore_errors=True)
-    work, _ = _run(nml, ref, nproc, {"RAMSES_AMD": "0"})
-    try:
-        want = _leaves(work)
-    finally:
-        shutil.rmtree(work, ignore_errors=True)
-    assert np.array_equal(got[0], want[0])
-    assert np.array_equal(got[1], want[1]), np.abs(got[1] - want[1]).max()
-    assert np.array_equal(got[1].view(np.int64), want[1].view(np.int64))
-    return out, want
+    return live.ab(nml, nproc, dict({"RAMSES_AMD_STRICT": "1", "RAMSES_AMD_STATS": "1"}, **env), ref_env={"RAMSES_AMD": "0"}, min_octs=min_octs)
 
 
 @pytest.mark.parametrize("nproc,poisson", [(1, False), (2, False), (1, True)], ids=["1rank", "2ranks", "self-gravity"])
@@ -404,15 +229,15 @@ def test_patched_program_with_pressure_fix_sweeps_its_levels_in_tiles(gpu_lib, n
     of the last snapshot bit-identical to the unpatched program, every sweep of a level through the dense kernel on tiles"""
     out, want = _live(_namelist(6, 7, poisson=poisson), nproc, {})
     assert "AMR levels stay resident on the GPU" in out, out[-3000:]
-    assert (want[0] == 7).sum() >= 64, "the run must have refined (eight octs of level 7 at least)"
-    tiles, tree = _sweep_counts(out)
+    assert (want.level == 7).sum() >= 64, "the run must have refined (eight octs of level 7 at least)"
+    tiles, tree = live.sweep_counts(out)
     assert tiles > 0 and tree == 0, (tiles, tree)
 
 
 def test_a_uniform_64_cubed_level_with_pressure_fix_takes_the_tiles_at_the_production_threshold(gpu_lib):
     """no override of RAMSES_AMD_TILE_MIN_OCTS: a uniform 64^3 level (32768 octs, the production crossover) with pressure_fix"""
     out, _ = _live(_namelist(6, 6, nstep=3, ngridtot=80000), 1, {}, min_octs=None)
-    tiles, tree = _sweep_counts(out)
+    tiles, tree = live.sweep_counts(out)
     assert tiles > 0, (tiles, tree)
 
 
@@ -421,5 +246,5 @@ def test_default_arithmetic_run_with_pressure_fix_is_bit_identical_and_says_so(g
     out, _ = _live(_namelist(6, 7), 1, {"RAMSES_AMD_STRICT": None})
     assert "dense sweep arithmetic = fast" in out, out[-3000:]
     assert "pressure_fix: AMR levels in tiles are swept in strict arithmetic" in out, out[-3000:]
-    tiles, tree = _sweep_counts(out)
+    tiles, tree = live.sweep_counts(out)
     assert tiles > 0 and tree == 0, (tiles, tree)

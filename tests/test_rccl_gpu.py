@@ -11,6 +11,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from resident import i32
+
 pytestmark = pytest.mark.gpu
 
 
@@ -34,10 +36,6 @@ def _i64(*v):
     return (C.c_int64 * len(v))(*v)
 
 
-def _i32(*v):
-    return (C.c_int * len(v))(*v)
-
-
 def test_grouped_exchange_with_self_peer(rccl):
     """ramses_amd_rccl_exchange: two messages to self at different offsets inside ONE group, on a side stream."""
     import torch
@@ -50,7 +48,7 @@ def test_grouped_exchange_with_self_peer(rccl):
     st.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(st):
         # message 0: send[100:1100] -> recv[2000:3000]; message 1: send[3000:5000] -> recv[10:2010)... kept disjoint
-        check(L.ramses_amd_rccl_exchange(2, _i32(0, 0), C.c_void_p(send.data_ptr()), _i64(100, 3000), _i64(1000, 2000),
+        check(L.ramses_amd_rccl_exchange(2, i32(0, 0), C.c_void_p(send.data_ptr()), _i64(100, 3000), _i64(1000, 2000),
                                          C.c_void_p(recv.data_ptr()), _i64(4000, 10), _i64(1000, 2000), C.c_void_p(st.cuda_stream)))
         # ordered after the exchange on the same stream: a kernel that reads what arrived
         twice = recv * 2.0
@@ -62,13 +60,13 @@ def test_grouped_exchange_with_self_peer(rccl):
     assert np.array_equal(recv.cpu().numpy(), exp)
     assert np.array_equal(twice.cpu().numpy(), exp * 2.0)
     # a message to self whose two ends disagree is refused, and the group is closed again (the next exchange works)
-    rc = L.ramses_amd_rccl_exchange(1, _i32(0), C.c_void_p(send.data_ptr()), _i64(0), _i64(10), C.c_void_p(recv.data_ptr()),
+    rc = L.ramses_amd_rccl_exchange(1, i32(0), C.c_void_p(send.data_ptr()), _i64(0), _i64(10), C.c_void_p(recv.data_ptr()),
                                     _i64(0), _i64(12), None)
     assert rc != 0 and b"message to self" in L.ramses_amd_last_error()
-    rc = L.ramses_amd_rccl_exchange(1, _i32(3), C.c_void_p(send.data_ptr()), _i64(0), _i64(10), C.c_void_p(recv.data_ptr()),
+    rc = L.ramses_amd_rccl_exchange(1, i32(3), C.c_void_p(send.data_ptr()), _i64(0), _i64(10), C.c_void_p(recv.data_ptr()),
                                     _i64(0), _i64(10), None)
     assert rc != 0 and b"bad peer rank" in L.ramses_amd_last_error()
-    check(L.ramses_amd_rccl_exchange(1, _i32(0), C.c_void_p(send.data_ptr()), _i64(0), _i64(10), C.c_void_p(recv.data_ptr()),
+    check(L.ramses_amd_rccl_exchange(1, i32(0), C.c_void_p(send.data_ptr()), _i64(0), _i64(10), C.c_void_p(recv.data_ptr()),
                                      _i64(0), _i64(10), None))
     torch.cuda.synchronize()
     assert np.array_equal(recv[:10].cpu().numpy(), s[:10])
@@ -88,7 +86,7 @@ def test_pointer_per_message_and_allreduce(rccl):
     rp = (C.c_void_p * 2)(ra.data_ptr(), rb.data_ptr())
     cnt = _i64(300, 200)
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    check(L.ramses_amd_rccl_sendrecv(2, sp, cnt, _i32(0, 0), 2, rp, cnt, _i32(0, 0), stream))
+    check(L.ramses_amd_rccl_sendrecv(2, sp, cnt, i32(0, 0), 2, rp, cnt, i32(0, 0), stream))
     torch.cuda.synchronize()
     assert torch.equal(ra, a) and torch.equal(rb, b)     # per peer, messages match in posting order
     for op in (0, 1, 2):                                 # sum / min / max over one rank: the identity, executed by RCCL
@@ -134,7 +132,7 @@ def test_amr_virtual_boundaries_over_rccl_equal_host_transport(rccl, nvar):
     def run(transport):
         u = uold0.copy()
         check(L.ramses_amd_amrres_load(nvar, ngridmax, ncoarse, vp(u), vp(son), vp(nbor), vp(father)))
-        check(L.ramses_amd_amrres_comm_set(lvl, 1, 1, _i32(len(em)), vp(em), _i32(len(rc_)), vp(rc_)))
+        check(L.ramses_amd_amrres_comm_set(lvl, 1, 1, i32(len(em)), vp(em), i32(len(rc_)), vp(rc_)))
         assert L.ramses_amd_amrres_comm_epoch(lvl) == 1
 
         def halo(d):
@@ -195,7 +193,7 @@ def test_distributed_multigrid_in_library_rccl_leg_equals_the_callback_transport
     # the in-library RCCL leg
     monkeypatch.setenv("RAMSES_AMD_MGDIST_RCCL_SELF", "1")
     ctx = C.c_void_p()
-    check(L.ramses_amd_mgdist_create(level, _i32(1, 1, 1), 0, None, None, C.byref(ctx)))
+    check(L.ramses_amd_mgdist_create(level, i32(1, 1, 1), 0, None, None, C.byref(ctx)))
     try:
         d_rho = torch.from_numpy(rho).cuda()
         phi = torch.zeros(n, n, n, dtype=torch.float64, device="cuda")

@@ -25,13 +25,13 @@ and a level-5 patch of 205 octs (5 %) is at least 6 level-4 cells wide, which en
 flag_fine (amr/flag_utils.f90) widen to the whole box at level 3 -- an elongated cube (tried: 0.44 x 0.09 x 0.09) ends the same
 way.  So level 4 is complete but built by the criterion, and the coarse-fine boundary the criterion draws lies between levels 4
 and 5."""
-import importlib.util
 import os
-import re
 import shutil
 
 import numpy as np
 import pytest
+
+import live
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,9 +52,7 @@ CASES = {
 
 
 def _namelist(crit, gravity=True, nproc=1, v7=False):
-    spec = importlib.util.spec_from_file_location("mka", os.path.join(ROOT, "tests", "golden", "make_golden_amr.py"))
-    mka = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mka)
+    mka = live.golden_module("amr")
     nml = mka.selfgrav_namelist()
     for old, new in (("err_grad_p=0.1\n", ""), ("err_grad_d=0.2\n", ""), ("p_region=1e-5,0.4,1e-3", "p_region=0.1,0.4,0.1"),
                      ("&REFINE_PARAMS\n", "&REFINE_PARAMS\n" + crit)):
@@ -70,27 +68,6 @@ def _namelist(crit, gravity=True, nproc=1, v7=False):
     return nml
 
 
-def _run(nml, binary, nproc, env):
-    from oracle import ramses_snapshot as rs
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return rs.run_reference(nml, binary=binary, nproc=nproc)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _snapshot(work, gravity):
-    from oracle import ramses_snapshot as rs
-    snap = rs.load_leaf_cells(os.path.join(work, "output_00002"), with_grav=gravity)
-    order = np.lexsort((snap["x"][:, 0], snap["x"][:, 1], snap["x"][:, 2], snap["level"]))
-    return snap["level"][order], snap["x"][order], snap["prim"][:, order], (snap["grav"][:, order] if gravity else None)
-
-
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_resident_run_with_refinement_criteria_equals_the_reference(gpu_lib, case):
     cfg = CASES[case]
@@ -99,23 +76,21 @@ def test_resident_run_with_refinement_criteria_equals_the_reference(gpu_lib, cas
     ref, patched = (os.path.join(REF_DIR, tag + s + ("_v7" if cfg.get("v7") else "")) for s in ("", "_patch"))
     if not (os.path.exists(ref) and os.path.exists(patched)):
         pytest.skip("%s / %s not built" % (os.path.basename(ref), os.path.basename(patched)))
-    if nproc > (os.cpu_count() or 1):
-        pytest.skip("fewer cores than ranks")
+    live.enough_cores(nproc)
     nml = _namelist(cfg["crit"], gravity, nproc, cfg.get("v7", False))
-    pat = r"==> Level=\s*(\d+) Step=\s*(\d+)"
-    workp, outp = _run(nml, patched, nproc, {"RAMSES_AMD": "1", "RAMSES_AMD_PROFILE": "1"})
+    workp, outp = live.run(nml, patched, nproc, {"RAMSES_AMD": "1", "RAMSES_AMD_PROFILE": "1"})
     try:
         assert RESIDENT in outp, outp[-1500:]
         for row in cfg["shims"]:         # the criterion ran on the device: the shim's row in the wall-clock table
             assert row in outp, (row, outp[-3000:])
-        sol_p = re.findall(pat, outp)
-        got = _snapshot(workp, gravity)
+        sol_p = live.poisson_solves(outp)
+        got = live.leaves(workp, with_grav=gravity)
     finally:
         shutil.rmtree(workp, ignore_errors=True)
-    workr, outr = _run(nml, ref, nproc, {})
+    workr, outr = live.run(nml, ref, nproc, {})
     try:
-        sol_r = re.findall(pat, outr)
-        want = _snapshot(workr, gravity)
+        sol_r = live.poisson_solves(outr)
+        want = live.leaves(workr, with_grav=gravity)
     finally:
         shutil.rmtree(workr, ignore_errors=True)
     assert {4, 5} <= set(int(l) for l in np.unique(want[0])), np.unique(want[0])      # the criterion built both levels
@@ -123,7 +98,7 @@ def test_resident_run_with_refinement_criteria_equals_the_reference(gpu_lib, cas
     assert np.array_equal(got[2], want[2]), np.abs(got[2] - want[2]).max()     # hydro state
     if gravity:
         assert len(sol_r) > 0 and sol_p == sol_r
-        assert np.array_equal(got[3], want[3]), np.abs(got[3] - want[3]).max()     # phi, f
+        assert np.array_equal(got.grav, want.grav), np.abs(got.grav - want.grav).max()     # phi, f
 
 
 def test_the_old_gating_comes_back_with_the_switch(gpu_lib):
@@ -132,15 +107,15 @@ def test_the_old_gating_comes_back_with_the_switch(gpu_lib):
     if not (os.path.exists(ref) and os.path.exists(patched)):
         pytest.skip("ramses3d / ramses3d_patch not built")
     nml = _namelist(JEANS)
-    workp, outp = _run(nml, patched, 1, {"RAMSES_AMD": "1", "RAMSES_AMD_RESIDENT_REFINE": "0"})
+    workp, outp = live.run(nml, patched, 1, {"RAMSES_AMD": "1", "RAMSES_AMD_RESIDENT_REFINE": "0"})
     try:
         assert RESIDENT not in outp
-        got = _snapshot(workp, True)
+        got = live.leaves(workp, with_grav=True)
     finally:
         shutil.rmtree(workp, ignore_errors=True)
-    workr, _ = _run(nml, ref, 1, {})
+    workr, _ = live.run(nml, ref, 1, {})
     try:
-        want = _snapshot(workr, True)
+        want = live.leaves(workr, with_grav=True)
     finally:
         shutil.rmtree(workr, ignore_errors=True)
     for a, b in zip(got, want):

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from helpers import harsh_tree_state, level_case, shell_mask
+from resident import force_tiles, load, vp
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +31,7 @@ FLOOR = 1e-10
 
 @pytest.fixture(autouse=True)
 def _tiles_on_small_levels_too(monkeypatch):
-    monkeypatch.setenv("RAMSES_AMD_TILE_MIN_OCTS", "0")
-
-
-def _vp(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+    force_tiles(monkeypatch, clear=())
 
 
 def _prim(u, c):
@@ -128,10 +125,8 @@ def _cells(K, mask):
 
 
 def _load(gpu_lib, K):
-    from ramses_amd._capi import check
-    T, u = K["T"], K["u"]
-    check(gpu_lib.ramses_amd_amrres_invalidate())
-    check(gpu_lib.ramses_amd_amrres_load(NVAR, T["ngridmax"], T["ncoarse"], _vp(u), _vp(T["son"]), _vp(T["nbor"]), _vp(T["father"])))
+    assert K["u"].shape[0] == NVAR
+    load(gpu_lib, K["T"], K["u"])
 
 
 def _params(K):
@@ -146,7 +141,7 @@ def _flag(gpu_lib, K, ig=None, **kw):
     n = C.c_int(-1)
     crit = make_refine_crit(floor_d=FLOOR, floor_p=FLOOR, floor_u=FLOOR, **kw)
     p = _params(K)
-    check(gpu_lib.ramses_amd_amrres_refine_flag(C.byref(p), len(ig), _vp(ig), C.byref(crit), _vp(cells), C.byref(n)))
+    check(gpu_lib.ramses_amd_amrres_refine_flag(C.byref(p), len(ig), vp(ig), C.byref(crit), vp(cells), C.byref(n)))
     return cells[:n.value].copy()
 
 
@@ -157,7 +152,7 @@ def _hydro_flag(gpu_lib, K, egd, egp, egu, ig=None):
     cells = np.zeros(8 * len(ig), np.int32)
     n = C.c_int(-1)
     p = _params(K)
-    check(gpu_lib.ramses_amd_amrres_hydro_flag(C.byref(p), len(ig), _vp(ig), egd, egp, egu, FLOOR, FLOOR, FLOOR, _vp(cells), C.byref(n)))
+    check(gpu_lib.ramses_amd_amrres_hydro_flag(C.byref(p), len(ig), vp(ig), egd, egp, egu, FLOOR, FLOOR, FLOOR, vp(cells), C.byref(n)))
     return cells[:n.value].copy()
 
 
@@ -306,11 +301,11 @@ def test_every_criterion_equals_the_restated_reference(gpu_lib, monkeypatch, L, 
         for rho in (K["rho"], None):
             cells = np.zeros(8 * len(ig), np.int32)
             n = C.c_int(-1)
-            check(gpu_lib.ramses_amd_amrres_mass_map(C.byref(p), len(ig), _vp(ig), K["d_scale"], K["m_refine"], ivar, K["cut"], _vp(rho),
-                                                     _vp(cells), C.byref(n)))
+            check(gpu_lib.ramses_amd_amrres_mass_map(C.byref(p), len(ig), vp(ig), K["d_scale"], K["m_refine"], ivar, K["cut"], vp(rho),
+                                                     vp(cells), C.byref(n)))
             assert np.array_equal(cells[:n.value], want), (ivar, rho is None, n.value, len(want))
     # the state did not move
     v = K["u"].copy()
-    check(gpu_lib.ramses_amd_amrres_sync_all(_vp(K["u"])))
+    check(gpu_lib.ramses_amd_amrres_sync_all(vp(K["u"])))
     assert np.array_equal(v, K["u"])
     gpu_lib.ramses_amd_amrres_invalidate()

@@ -18,7 +18,6 @@ weak #2: the largest MPI run compared so far was 128^3 on 8 ranks, i.e. 64^3 bri
 
 All ranks share the box's one GPU (host-MPI transport; the run says so); the RCCL entry points themselves are executed by
 tests/test_rccl_gpu.py."""
-import importlib.util
 import json
 import os
 import shutil
@@ -27,6 +26,8 @@ import time
 import numpy as np
 import pytest
 
+import live
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi")
@@ -34,13 +35,6 @@ PATCHED = os.path.join(ROOT, "oracle", "_ref", "ramses3d_patch")
 PATCHED_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi_patch")
 GOLD = os.path.join(ROOT, "tests", "golden", "baseline_sizes.json")
 TOL = 1e-12
-
-
-def _mkb():
-    spec = importlib.util.spec_from_file_location("mkb", os.path.join(ROOT, "tests", "golden", "make_golden_baseline.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
 
 
 def _cores():
@@ -68,19 +62,9 @@ def _ram_gb():
         return 0.0
 
 
-def _run(nml, binary, nproc, env, timeout=1500):
-    from oracle import ramses_snapshot as rs
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
+def _timed_run(nml, binary, nproc, env, timeout=1500):
     t0 = time.time()
-    try:
-        work, out = rs.run_reference(nml, binary=binary, nproc=nproc, timeout=timeout)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    work, out = live.run(nml, binary, nproc, env, timeout=timeout)
     return work, out, time.time() - t0
 
 
@@ -93,13 +77,13 @@ def _need(*paths):
 def _uniform_ab(level, nstep, nref, overlaps):
     from oracle import ramses_snapshot as rs
     nml = rs.sedov3d_namelist(level=level, nstepmax=nstep, foutput=nstep, mem_factor=3.0)
-    workr, outr, tr = _run(nml, REF_MPI, nref, {"RAMSES_AMD": "0"})
+    workr, outr, tr = _timed_run(nml, REF_MPI, nref, {"RAMSES_AMD": "0"})
     try:
         ref = rs.load_uniform_level(os.path.join(workr, "output_00002"), level)
     finally:
         shutil.rmtree(workr, ignore_errors=True)
     for ov in overlaps:
-        workp, outp, tp = _run(nml, PATCHED_MPI, 8, {"RAMSES_AMD": "1", "RAMSES_AMD_OVERLAP": ov})
+        workp, outp, tp = _timed_run(nml, PATCHED_MPI, 8, {"RAMSES_AMD": "1", "RAMSES_AMD_OVERLAP": ov})
         try:
             assert "stays resident on the GPUs" in outp, outp[-2000:]
             assert ("halo exchange over RCCL" in outp) or ("staged through host MPI" in outp)
@@ -141,10 +125,10 @@ def test_c4_as_stated_256_serial_checksum_and_live_mpi_reference(gpu_lib):
     """BASELINE config C4: uniform 256^3 hydro + self-gravity on one MI355X, three coarse steps."""
     _need(REF_MPI, PATCHED)
     from oracle import ramses_snapshot as rs
-    mkb = _mkb()
+    mkb = live.golden_module("baseline")
     gold = json.load(open(GOLD)).get("c4_256") if os.path.exists(GOLD) else None
     nml = mkb.c4_namelist(level=8)
-    workp, outp, tp = _run(nml, PATCHED, 1, {"RAMSES_AMD": "1"})
+    workp, outp, tp = _timed_run(nml, PATCHED, 1, {"RAMSES_AMD": "1"})
     try:
         assert "stays resident on the GPU" in outp
         got = rs.load_uniform_level(os.path.join(workp, "output_00002"), 8, with_grav=True)
@@ -160,7 +144,7 @@ def test_c4_as_stated_256_serial_checksum_and_live_mpi_reference(gpu_lib):
     # the MPI reference, live: another summation order of the multipoles and norms -> rounding-level differences
     nref = _pow2_ranks(32)
     nml_mpi = nml.replace("ngridtot=", "ngridtot=%d !" % (3 * sum(8 ** l for l in range(8)) + 1000))
-    workr, outr, tr = _run(nml_mpi, REF_MPI, nref, {"RAMSES_AMD": "0"})
+    workr, outr, tr = _timed_run(nml_mpi, REF_MPI, nref, {"RAMSES_AMD": "0"})
     try:
         ref = rs.load_uniform_level(os.path.join(workr, "output_00002"), 8, with_grav=True)
         ref_solves = mkb.solves(outr)

@@ -15,6 +15,8 @@ import json
 import os
 import shutil
 import subprocess
+
+from helpers import hip_include
 import sys
 
 import pytest
@@ -48,18 +50,6 @@ VALUES = {
 }
 
 
-def _hip_include():
-    cands = [os.environ.get("ROCM_PATH"), os.environ.get("HIP_PATH")]
-    hipcc = shutil.which("hipcc")
-    if hipcc:
-        cands.append(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))))
-    cands.append("/opt/rocm")
-    for c in cands:
-        if c and os.path.exists(os.path.join(c, "include", "hip", "hip_runtime.h")):
-            return os.path.join(c, "include")
-    raise RuntimeError("hip/hip_runtime.h not found")
-
-
 def dump(objdir, workdir):
     """link the sweep objects with the stub and the dump program, run it: the lines it wrote"""
     objs = sorted(glob.glob(os.path.join(objdir, "hydro_sweep_*.o")))
@@ -67,7 +57,7 @@ def dump(objdir, workdir):
     cxx = shutil.which("g++") or shutil.which("c++")
     assert cxx, "no host C++ compiler"
     exe = os.path.join(workdir, "sweep_dispatch_dump")
-    subprocess.run([cxx, "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", _hip_include(), "-I", os.path.join(ROOT, "ramses_amd"),
+    subprocess.run([cxx, "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I", hip_include("hip_runtime.h"), "-I", os.path.join(ROOT, "ramses_amd"),
                     os.path.join(NATIVE, "sweep_dispatch_dump.cpp"), os.path.join(NATIVE, "hip_stub.cpp")] + objs + ["-o", exe],
                    check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     return subprocess.run([exe], check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()

@@ -4,19 +4,15 @@ callers amr/amr_step.f90:70,293,514) fills the boundary octs on the device (csrc
 ramses_amd_amrres_boundary_hydro) -- reflexive walls, free boundaries, the no_inflow clamp, imposed states, regions processed in the
 reference's order (corners read what an earlier region wrote).  Live against the untouched reference program: leaf cells
 bit for bit, on one rank and under MPI, on AMR levels and on a single uniform level."""
-import importlib.util
 import os
 import shutil
 
 import numpy as np
 import pytest
 
+import live
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref", "ramses3d")
-PATCHED = os.path.join(ROOT, "oracle", "_ref", "ramses3d_patch")
-REF_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi")
-PATCHED_MPI = os.path.join(ROOT, "oracle", "_ref", "ramses3d_mpi_patch")
 
 # the blast three cells off the corner x = y = z = 0: the shock meets three boundaries within a few steps, the refined
 # patch leans on them (boundary octs on every level)
@@ -49,66 +45,13 @@ no_inflow=%s
 """
 
 
-def _mka():
-    spec = importlib.util.spec_from_file_location("mka", os.path.join(ROOT, "tests", "golden", "make_golden_amr.py"))
-    mka = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mka)
-    return mka
-
-
 def _namelist(lmin, lmax, nsub, riemann, slope, nstep, types, no_inflow):
-    from oracle import ramses_snapshot as rs
-    mka = _mka()
-    extra = mka.REFINE.format(ivar=0, itype=2) + BOUNDS % (types, ".true." if no_inflow else ".false.")
-    nml = rs.sedov3d_namelist(level=lmin, nstepmax=nstep, foutput=nstep, riemann=riemann, slope_type=slope, extra=extra,
-                              init=CORNER, mem_factor=1.0)
-    nml = nml.replace("levelmax=%d" % lmin, "levelmax=%d" % lmax).replace("nsubcycle=10*1", "nsubcycle=" + nsub)
-    return nml.replace("ngridtot=", "ngridtot=30000 !")
-
-
-def _run(nml, binary, nproc, env):
-    from oracle import ramses_snapshot as rs
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return rs.run_reference(nml, binary=binary, nproc=nproc)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _leaves(work, k=2):
-    from oracle import ramses_snapshot as rs
-    snap = rs.load_leaf_cells(os.path.join(work, "output_%05d" % k))
-    order = np.lexsort((snap["x"][:, 0], snap["x"][:, 1], snap["x"][:, 2], snap["level"]))
-    return snap["level"][order], snap["x"][order], snap["prim"][:, order], snap["info"]["t"]
+    extra = live.golden_module("amr").REFINE.format(ivar=0, itype=2) + BOUNDS % (types, ".true." if no_inflow else ".false.")
+    return live.amr_namelist(lmin, lmax, nstep, riemann, slope, nsub, 30000, extra=extra, init=CORNER)
 
 
 def _ab(nml, nproc, env, expect_resident=True, min_levels=2):
-    ref_bin, pat_bin = (REF, PATCHED) if nproc == 1 else (REF_MPI, PATCHED_MPI)
-    if not (os.path.exists(ref_bin) and os.path.exists(pat_bin)):
-        pytest.skip("oracle/_ref programs not built")
-    e = {"RAMSES_AMD": "1", "RAMSES_AMD_PROFILE": "1"}
-    e.update(env)
-    workp, outp = _run(nml, pat_bin, nproc, e)
-    try:
-        assert ("AMR levels stay resident on the GPU" in outp) == expect_resident, outp[-3000:]
-        assert ("make_boundary_hydro (device)" in outp) == expect_resident, outp[-3000:]
-        got = _leaves(workp)
-    finally:
-        shutil.rmtree(workp, ignore_errors=True)
-    workr, outr = _run(nml, ref_bin, nproc, {})
-    try:
-        ref = _leaves(workr)
-    finally:
-        shutil.rmtree(workr, ignore_errors=True)
-    assert got[3] == ref[3]
-    assert len(set(int(l) for l in ref[0])) >= min_levels, "the run must have refined"
-    assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
-    assert np.array_equal(got[2].view(np.int64), ref[2].view(np.int64)), np.abs(got[2] - ref[2]).max()
+    live.ab(nml, nproc, dict({"RAMSES_AMD_PROFILE": "1"}, **env), expect_resident=expect_resident, min_levels=min_levels)
 
 
 @pytest.mark.parametrize("types,no_inflow,riemann,slope,nsub", [
@@ -233,17 +176,16 @@ def test_self_gravity_between_walls_stays_resident(gpu_lib):
     there, f of the boundary octs mirrored after make_boundary_force), the Dirichlet solve keeps the reference's driver;
     leaf cells, phi and f equal the reference program bit for bit"""
     from oracle import ramses_snapshot as rs
-    if not (os.path.exists(REF) and os.path.exists(PATCHED)):
-        pytest.skip("oracle/_ref programs not built")
-    nml = _mka().walls_selfgrav_namelist()
-    workp, outp = _run(nml, PATCHED, 1, {"RAMSES_AMD": "1", "RAMSES_AMD_PROFILE": "1"})
+    patched, unpatched = live.binaries(False)
+    nml = live.golden_module("amr").walls_selfgrav_namelist()
+    workp, outp = live.run(nml, patched, 1, {"RAMSES_AMD": "1", "RAMSES_AMD_PROFILE": "1"})
     try:
         assert "AMR levels stay resident on the GPU" in outp, outp[-3000:]
         assert "make_boundary_hydro (device)" in outp, outp[-3000:]
         got = rs.load_leaf_cells(os.path.join(workp, "output_00002"))
     finally:
         shutil.rmtree(workp, ignore_errors=True)
-    workr, outr = _run(nml, REF, 1, {})
+    workr, outr = live.run(nml, unpatched, 1, {})
     try:
         ref = rs.load_leaf_cells(os.path.join(workr, "output_00002"))
     finally:
@@ -257,23 +199,5 @@ def test_self_gravity_between_walls_stays_resident(gpu_lib):
 def test_self_gravity_between_walls_under_mpi_stays_resident(gpu_lib):
     """the same on 2 ranks: hydro state, tree and communicators resident on every rank, make_boundary_hydro on the device; the
     Dirichlet solves, rho_fine and force_fine + make_boundary_force keep the reference's MPI routines"""
-    from oracle import ramses_snapshot as rs
-    if not (os.path.exists(REF_MPI) and os.path.exists(PATCHED_MPI)):
-        pytest.skip("oracle/_ref MPI programs not built")
-    nml = _mka().walls_selfgrav_namelist().replace("ngridtot=20000 !", "ngridtot=60000 !")
-    workp, outp = _run(nml, PATCHED_MPI, 2, {"RAMSES_AMD": "1", "RAMSES_AMD_PROFILE": "1"})
-    try:
-        assert "AMR levels stay resident on the GPU" in outp, outp[-3000:]
-        assert "make_boundary_hydro (device)" in outp, outp[-3000:]
-        got = rs.load_leaf_cells(os.path.join(workp, "output_00002"))
-    finally:
-        shutil.rmtree(workp, ignore_errors=True)
-    workr, outr = _run(nml, REF_MPI, 2, {})
-    try:
-        ref = rs.load_leaf_cells(os.path.join(workr, "output_00002"))
-    finally:
-        shutil.rmtree(workr, ignore_errors=True)
-    og = np.lexsort((got["x"][:, 0], got["x"][:, 1], got["x"][:, 2], got["level"]))
-    orf = np.lexsort((ref["x"][:, 0], ref["x"][:, 1], ref["x"][:, 2], ref["level"]))
-    assert np.array_equal(got["level"][og], ref["level"][orf]) and np.array_equal(got["x"][og], ref["x"][orf])
-    assert np.array_equal(got["prim"][:, og].view(np.int64), ref["prim"][:, orf].view(np.int64))
+    nml = live.golden_module("amr").walls_selfgrav_namelist().replace("ngridtot=20000 !", "ngridtot=60000 !")
+    live.ab(nml, 2, {"RAMSES_AMD_PROFILE": "1"}, expect_resident=True)

@@ -3,13 +3,13 @@ cells, ramses_amd_amrres_coarse_grid from patch/ramses_amd_iface.f90) against th
 three cells off a corner, walls of mixed type with the no_inflow clamp, levels 6-7 (the coarsest levels whose 3 * 2^(l-1) octs
 per side are whole tiles), sub-cycling and regrids -- leaf cells bit for bit, every godunov_fine of a level through the dense
 kernel.  The namelist and the run helpers are those of tests/test_walls_resident_gpu.py."""
-import os
 import re
 import shutil
 
 import numpy as np
 import pytest
 
+import live
 import test_walls_resident_gpu as W
 
 pytestmark = pytest.mark.gpu
@@ -20,25 +20,23 @@ STATS = re.compile(r"godunov_fine of AMR levels:\s*(\d+) sweeps through the dens
 
 @pytest.mark.parametrize("nproc", [1, 2])
 def test_sedov_between_six_walls_sweeps_its_levels_in_tiles(gpu_lib, nproc):
-    ref_bin, pat_bin = (W.REF, W.PATCHED) if nproc == 1 else (W.REF_MPI, W.PATCHED_MPI)
-    if not (os.path.exists(ref_bin) and os.path.exists(pat_bin)):
-        pytest.skip("oracle/_ref programs not built")
+    pat_bin, ref_bin = live.binaries(nproc > 1)
     nml = W._namelist(6, 7, "1,1,1,1,1,2,2", "hllc", 1, 3, "1, 2, 2, 1, 1, 2", True)
     nml = nml.replace("ngridtot=30000 !", "ngridtot=%d !" % (500000 * nproc))
     assert "levelmin=6" in nml and "levelmax=7" in nml and "ngridtot=%d" % (500000 * nproc) in nml and "no_inflow=.true." in nml
-    workp, outp = W._run(nml, pat_bin, nproc, ENV)
+    workp, outp = live.run(nml, pat_bin, nproc, ENV)
     try:
         assert "AMR levels stay resident on the GPU" in outp and "make_boundary_hydro (device)" in outp, outp[-3000:]
-        got = W._leaves(workp)
+        got = live.leaves(workp)
     finally:
         shutil.rmtree(workp, ignore_errors=True)
     lines = STATS.findall(outp)
     assert len(lines) == nproc, outp[-3000:]
     for tiles, tree, ntiled in lines:          # (levelmin = 6: every level of the run is a level >= 6)
         assert int(tiles) > 0 and int(tree) == 0 and int(ntiled) >= 1, lines
-    workr, _ = W._run(nml, ref_bin, nproc, {})
+    workr, _ = live.run(nml, ref_bin, nproc, {})
     try:
-        ref = W._leaves(workr)
+        ref = live.leaves(workr)
     finally:
         shutil.rmtree(workr, ignore_errors=True)
     assert got[3] == ref[3]
