@@ -1053,6 +1053,26 @@ int ramses_amd_resident_force_ana_f90(int ilevel, double fact, double *diag2);
  * RAMSES_AMD_EINVAL without a resident state or acceleration. */
 int ramses_amd_amrres_stash_f(int ngrid, const int *igrid);
 int ramses_amd_amrres_restore_f(int ngrid, const int *igrid, const int *inherit);
+/* The barotropic equation of state with a CONSTANT temperature on the device: cooling_fine(ilevel) of a run with barotropic_eos
+ * and without cooling (amr/amr_step.f90:470-473) rewrites the total energy of the level's leaf cells from their density and momenta
+ * (hydro/cooling_fine.f90:162-181 leaf cells and nH, :264-308 ekk, err, emag and nH in H/cc, :331-347 T2min, :537-540 nH back, :563-566
+ * the polytrope's internal energy, :576-579 the new total energy) and nothing else.  Strict IEEE arithmetic in the reference's
+ * operation order (csrc/eos_core.hpp): the reference's bits.  NDIM = 3, NENER = 0, SOLVER=hydro.
+ *   ramses_amd_eos_set: T2c = T2_eos of barotropic_eos_form='isothermal' (hydro/eos.f90:14-15), or T2_star of the 'legacy' form with
+ *       g_star = 1 and jeans_ncells <= 0 (hydro/cooling_fine.f90:344, exponent +0.0); scale_nH and scale_T2 of the program's units().
+ *       Every other form raises the density to a power through the pow of the reference's runtime library and is not offered.
+ *   ramses_amd_eos_eval: E[n] from u5[5][n] = (rho, mx, my, mz, E_old; E_old is not read) with p->smallr and p->gamma, evaluated on
+ *       the HOST by the same header (no device needed: the checks that hold it to records of the reference).
+ *   ramses_amd_amrres_cooling_fine: on the resident AMR state, the leaf cells (resident son == 0) of the ngrid listed own octs.
+ *   ramses_amd_resident_cooling_fine_f90: on the one-level resident brick (ramses_amd_resident_*): every cell is a leaf.
+ *   ramses_amd_mpires_cooling_fine: on a rank's brick of the MPI-resident level: the interior cells; the ghost layers are not
+ *       written (make_virtual_fine_dp follows, amr/amr_step.f90:505) and a halo sent ahead of this call is dropped.
+ * RAMSES_AMD_EINVAL without their state (no ramses_amd_eos_set, no resident state, a godunov_fine result pending). */
+int ramses_amd_eos_set(double T2c, double scale_nH, double scale_T2);
+int ramses_amd_eos_eval(const ramses_amd_hydro_params *p, int64_t n, const double *u5, double *E);
+int ramses_amd_amrres_cooling_fine(const ramses_amd_hydro_params *p, int ngrid, const int *igrid);
+int ramses_amd_resident_cooling_fine_f90(const ramses_amd_hydro_params *p, int ilevel);
+int ramses_amd_mpires_cooling_fine(const ramses_amd_hydro_params *p);
 /* Several MPI ranks (one per GPU): the virtual-boundary exchanges of amr_step on the resident cell vectors.
  *   make_virtual_fine_dp(uold(1,ivar),ilevel)     amr/virtual_boundaries.f90:373-528, callers amr/amr_step.f90:61,287,505
  *   make_virtual_reverse_dp(unew(1,ivar),ilevel)  amr/virtual_boundaries.f90:693-983, caller amr/amr_step.f90:397

@@ -264,6 +264,12 @@ SYMBOLS = [
     ("ramses_amd_resident_force_ana_f90", _i, [_i, _d, _vp]),
     ("ramses_amd_amrres_stash_f", _i, [_i, _vp]),
     ("ramses_amd_amrres_restore_f", _i, [_i, _vp, _vp]),
+    # barotropic EOS with a constant temperature: cooling_fine on the device
+    ("ramses_amd_eos_set", _i, [_d, _d, _d]),
+    ("ramses_amd_eos_eval", _i, [_PP, _i64, _vp, _vp]),
+    ("ramses_amd_amrres_cooling_fine", _i, [_PP, _i, _vp]),
+    ("ramses_amd_resident_cooling_fine_f90", _i, [_PP, _i]),
+    ("ramses_amd_mpires_cooling_fine", _i, [_PP]),
     ("ramses_amd_mhd_workspace_bytes", _i64, [_i, _i, _i]),
     ("ramses_amd_mhd_godunov_brick", _i, [_vp, _i, _i, _i, _vp, _vp, _d, _d, _vp, _i64, _vp]),
     ("ramses_amd_mhd_godunov_brick_fast", _i, [_vp, _i, _i, _i, _vp, _vp, _d, _d, _vp, _i64, _vp]),

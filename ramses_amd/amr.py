@@ -69,3 +69,11 @@ def phi_fine_cg(tree, ilevel, igrid, phi, f, epsilon, itermax=10000, ordered=Fal
                                          float(8 * len(igrid) if ncell_level is None else ncell_level), float(epsilon),
                                          int(itermax), int(ordered), C.byref(it), err))
     return it.value, err[0], err[1], err[2]
+
+
+def cooling_fine_resident(params, igrid):
+    """cooling_fine(ilevel) of a barotropic run of constant temperature without cooling (hydro/cooling_fine.f90:1-45,576-579) on
+    the RESIDENT AMR state (ramses_amd_amrres_load): the total energy of the leaf cells of the octs `igrid` of a level is
+    rewritten on the device with the constants of hydro.eos_set; nothing crosses PCIe but the list."""
+    igrid = _i32(igrid)
+    check(lib().ramses_amd_amrres_cooling_fine(C.byref(params), len(igrid), _vp(igrid)))

@@ -408,6 +408,18 @@ __global__ __launch_bounds__(256) void gravana_eval_kernel(GravAna G, long n, co
   }
 }
 
+// cooling_fine of a barotropic run without cooling (hydro/cooling_fine.f90:162-181,264-308,537-540,563-579; csrc/eos_core.hpp): the
+// total energy of the LEAF cells (son == 0) of the listed octs is rewritten from their density and momenta.  One lane per cell; the
+// density, the momenta, the passive scalars and every split cell are left alone.
+__global__ __launch_bounds__(256) void lvl_eos_kernel(LvlArgs A, EosConst C, double smallr, double gamma) {
+  const long total = (long)A.ngrid * 8;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const long c = lvl_cell(A, t);
+    if (A.son[c] != 0) continue;
+    A.uold[c + 4 * A.ncell] = eos_energy(C, A.uold[c], A.uold[c + A.ncell], A.uold[c + 2 * A.ncell], A.uold[c + 3 * A.ncell], smallr, gamma);
+  }
+}
+
 // The acceleration of a level across a regrid without a trip to the host.  The host's oct numbers survive refine_fine, the
 // device's do not: before the tree changes f of the listed octs is parked in the HOST's numbering (stage[3][ncell_h], device
 // memory; hraw = the list as the host wrote it, L.igrid = the same octs in device numbers) ...
@@ -2448,6 +2460,59 @@ int ramses_amd_amrres_synchro(const ramses_amd_hydro_params *p, int ngrid, const
   if (ngrid == 0) return 0;
   hipLaunchKernelGGL(lvl_synchro_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, A, g_ar.f.as<double>(), dteff, p->smallr);
   HCHK(hipGetLastError(), "synchro launch");
+  return 0;
+}
+
+// ---- the barotropic equation of state with a constant temperature (csrc/eos_core.hpp): cooling_fine of such a run without cooling
+// rewrites the total energy of the leaf cells and nothing else, so it runs on the resident state
+
+namespace {
+EosConst g_eos;
+bool g_eos_set = false;
+long g_eos_calls = 0;      // cooling_fine calls that launched a kernel (AMR levels and the level bricks)
+}  // namespace
+extern "C++" {
+namespace ramses_amd {
+const EosConst *capi_eos() { return g_eos_set ? &g_eos : nullptr; }      // (capi_host.hip, capi_mpi.hip: the level bricks)
+// one more cooling_fine ran on the device; RAMSES_AMD_STATS: the count in an exit line
+void capi_eos_called() {
+  if (g_eos_calls++ == 0) {
+    const char *e = getenv("RAMSES_AMD_STATS");
+    if (e && e[0] != '0') atexit([] { fprintf(stdout, " ramses_amd: cooling_fine (device, barotropic): %ld calls\n", g_eos_calls); });
+  }
+}
+}  // namespace ramses_amd
+}
+
+// T2c: T2_eos of barotropic_eos_form = 'isothermal', T2_star of the legacy form with g_star = 1; scale_nH, scale_T2 of units()
+int ramses_amd_eos_set(double T2c, double scale_nH, double scale_T2) {
+  if (!(T2c >= 0.0) || !(scale_nH > 0.0) || !(scale_T2 > 0.0))
+    return fail(RAMSES_AMD_EINVAL, "ramses_amd_eos_set: T2c must be >= 0, scale_nH and scale_T2 > 0 (got %g, %g, %g)", T2c, scale_nH, scale_T2);
+  g_eos.T2c = T2c; g_eos.scale_nH = scale_nH; g_eos.scale_T2 = scale_T2;
+  g_eos_set = true;
+  return 0;
+}
+
+// E[n] = eos_energy of u5[5][n] (rho, the three momenta, the old total energy -- which the result does not depend on) on the HOST:
+// the header's host side, for the checks that hold it to the reference's records
+int ramses_amd_eos_eval(const ramses_amd_hydro_params *p, int64_t n, const double *u5, double *E) {
+  if (!g_eos_set) return fail(RAMSES_AMD_EINVAL, "ramses_amd_eos_eval: no equation of state set (ramses_amd_eos_set)");
+  if (!p || n < 0 || (n > 0 && (!u5 || !E))) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  for (int64_t i = 0; i < n; i++) E[i] = eos_energy(g_eos, u5[i], u5[n + i], u5[2 * n + i], u5[3 * n + i], p->smallr, p->gamma);
+  return 0;
+}
+
+// cooling_fine(ilevel) of a barotropic run without cooling on the resident AMR state: uold(ndim+2) of the leaf cells of the listed
+// (own) octs
+int ramses_amd_amrres_cooling_fine(const ramses_amd_hydro_params *p, int ngrid, const int *igrid) {
+  LvlArgs A;
+  if (!g_eos_set) return fail(RAMSES_AMD_EINVAL, "cooling_fine: no equation of state set (ramses_amd_eos_set)");
+  if (int rc = level_entry(p, "ramses_amd_amrres_cooling_fine", ngrid, igrid, A)) return rc;
+  if (p->ndim != 3 || p->nvar < 5) return fail(RAMSES_AMD_EUNSUPPORTED, "ramses_amd_amrres_cooling_fine: NDIM=%d NVAR=%d (needs NDIM=3, NVAR>=5)", p->ndim, p->nvar);
+  if (ngrid == 0) return 0;
+  hipLaunchKernelGGL(lvl_eos_kernel, lvl_grid(ngrid), dim3(256), 0, nullptr, A, g_eos, p->smallr, p->gamma);
+  HCHK(hipGetLastError(), "cooling_fine launch");
+  capi_eos_called();
   return 0;
 }
 

@@ -705,6 +705,28 @@ int ramses_amd_resident_synchro_f90(const ramses_amd_hydro_params *p, int ilevel
   return 0;
 }
 
+// cooling_fine(ilevel) of a barotropic run without cooling (hydro/cooling_fine.f90:162-181,264-308,537-540,563-579; csrc/eos_core.hpp)
+// on the resident level: every cell of the level is a leaf, the total energy of each is rewritten
+int ramses_amd_resident_cooling_fine_f90(const ramses_amd_hydro_params *p, int ilevel) {
+  HostCtx &H = g_host;
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  const EosConst *C = capi_eos();
+  if (!C) return fail(RAMSES_AMD_EINVAL, "cooling_fine: no equation of state set (ramses_amd_eos_set)");
+  if (int rc = resident_level_is(ilevel, "cooling_fine")) return rc;
+  if (H.res_nener > 0) return fail(RAMSES_AMD_EUNSUPPORTED, "cooling_fine: NENER=%d with an equation of state is not on the device", H.res_nener);
+  if (H.res_new_ready) return fail(RAMSES_AMD_EINVAL, "cooling_fine between godunov_fine and set_uold");
+  const int n = 1 << ilevel;
+  EosBrickArgs A;
+  A.u = H.bold.as<double>(); A.nx = A.ny = A.nz = n;
+  A.off = 0; A.pitch_y = n; A.pitch_z = (long)n * n; A.pitch_var = resident_cells();
+  A.smallr = p->smallr; A.gamma = p->gamma; A.C = *C;
+  hipError_t e = launch_eos_brick(A, nullptr);
+  if (e != hipSuccess) return hipfail(e, "cooling_fine launch");
+  capi_eos_called();
+  H.res_host_stale = true;
+  return 0;
+}
+
 // courant_fine with the gravity term of cmpdt (hydro/courant_fine.f90:77-85)
 int ramses_amd_resident_courant_grav_f90(const ramses_amd_hydro_params *p, int ilevel, int ngrid,
                                          const int *igrid, const double *xg, int64_t ngridmax,

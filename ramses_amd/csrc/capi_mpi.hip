@@ -28,6 +28,7 @@
 #include "host_util.hpp"
 #include "misc_args.hpp"
 #include "pack_args.hpp"
+#include "capi_shared.hpp"
 
 using namespace ramses_amd;
 
@@ -568,6 +569,31 @@ int ramses_amd_mpires_set_uold_pdv(const ramses_amd_hydro_params *p, double dx, 
   if (M.prefetched) return fail(RAMSES_AMD_EINVAL, "set_uold with pdV: the new state's halo already left (overlap with NENER > 0)");
   if (int rc = ramses_amd_pdv_brick(p, &M.brick, M.bold.as<double>(), M.bnew.as<double>(), dx, dt, M.s_comp)) return rc;
   return mpires_swap(M);
+}
+
+// cooling_fine(ilevel) of a barotropic run without cooling (hydro/cooling_fine.f90:162-181,264-308,537-540,563-579; csrc/eos_core.hpp)
+// on the rank's brick: the total energy of the interior cells (all leaves) is rewritten; the ghost layers get the neighbours' new
+// energies with the make_virtual_fine_dp that follows (amr/amr_step.f90:505).  A halo of the state that the overlap sent ahead
+// behind the interior sweep carries the energies from BEFORE this call: it is dropped, and that exchange packs again.
+int ramses_amd_mpires_cooling_fine(const ramses_amd_hydro_params *p) {
+  NEED_VALID("cooling_fine");
+  if (!p) return fail(RAMSES_AMD_EINVAL, "NULL argument");
+  const EosConst *C = capi_eos();
+  if (!C) return fail(RAMSES_AMD_EINVAL, "cooling_fine: no equation of state set (ramses_amd_eos_set)");
+  MpiRes &M = g_mr;
+  if (M.nener > 0) return fail(RAMSES_AMD_EUNSUPPORTED, "cooling_fine: NENER=%d with an equation of state is not on the device", M.nener);
+  if (M.new_ready) return fail(RAMSES_AMD_EINVAL, "cooling_fine between godunov_fine and set_uold");
+  if (int rc = join_comm(M)) return rc;
+  M.prefetched = 0;
+  const HaloPlan &P = M.plan;
+  EosBrickArgs A;
+  A.u = M.bold.as<double>(); A.nx = P.nx; A.ny = P.ny; A.nz = P.nz;
+  A.off = 2 + 2 * P.pitch_y + 2 * P.pitch_z; A.pitch_y = P.pitch_y; A.pitch_z = P.pitch_z; A.pitch_var = P.pitch_var;
+  A.smallr = p->smallr; A.gamma = p->gamma; A.C = *C;
+  HCHK(launch_eos_brick(A, M.s_comp), "cooling_fine launch");
+  capi_eos_called();
+  M.host_stale = true;
+  return 0;
 }
 
 // make_virtual_fine_dp(uold(1,1:nvar),ilevel) over RCCL: pack -> one grouped send/recv -> unpack -> periodic self-fill

@@ -90,5 +90,9 @@ int capi_resident_release(const char *who);
 // capi_amr.hip: what ramses_amd_gravana_set stored (csrc/gravana_core.hpp), or null before it
 struct GravAna;
 const GravAna *capi_gravana();
+// capi_amr.hip: what ramses_amd_eos_set stored (csrc/eos_core.hpp), or null before it
+struct EosConst;
+const EosConst *capi_eos();
+void capi_eos_called();      // one more cooling_fine ran on the device (the RAMSES_AMD_STATS exit line counts them)
 
 }  // namespace ramses_amd

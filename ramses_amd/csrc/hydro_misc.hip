@@ -442,6 +442,20 @@ __global__ __launch_bounds__(256) void gravana_brick_kernel(GravAna G, int n, do
   }
 }
 
+// ---------------------------------------------------------------------------
+// cooling_fine of a barotropic run without cooling on a level brick (csrc/eos_core.hpp): every cell of a fully refined level is
+// a leaf, so the total energy of each interior cell is rewritten from its density and momenta.  One lane per cell, 4 reads and 1
+// write; the ghost layers (a brick of the MPI-resident level has them) and every other variable are left alone.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void eos_brick_kernel(EosBrickArgs A) {
+  const long N = (long)A.nx * A.ny * A.nz;
+  for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < N; c += (long)gridDim.x * blockDim.x) {
+    const int i = (int)(c % A.nx), j = (int)((c / A.nx) % A.ny), k = (int)(c / ((long)A.nx * A.ny));
+    double *u = A.u + A.off + i + (long)j * A.pitch_y + (long)k * A.pitch_z;
+    u[4 * A.pitch_var] = eos_energy(A.C, u[0], u[A.pitch_var], u[2 * A.pitch_var], u[3 * A.pitch_var], A.smallr, A.gamma);
+  }
+}
+
 static inline int misc_grid(long work) {
   long g = (work + 255) / 256;
   if (g < 1) g = 1;
@@ -459,6 +473,11 @@ hipError_t launch_add_gravity_source(double *unew, const double *uold, const dou
 }
 hipError_t launch_gravana_brick(const GravAna &G, int n, double dx, double *f, hipStream_t s) {
   hipLaunchKernelGGL(gravana_brick_kernel, dim3(misc_grid((long)n * n * n)), dim3(256), 0, s, G, n, dx, f);
+  return hipGetLastError();
+}
+hipError_t launch_eos_brick(const EosBrickArgs &A, hipStream_t s) {
+  if (A.nx < 1 || A.ny < 1 || A.nz < 1) return hipSuccess;
+  hipLaunchKernelGGL(eos_brick_kernel, dim3(misc_grid((long)A.nx * A.ny * A.nz)), dim3(256), 0, s, A);
   return hipGetLastError();
 }
 

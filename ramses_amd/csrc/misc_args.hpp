@@ -2,6 +2,7 @@
 #pragma once
 #include "hydro_core.hpp"
 #include "gravana_core.hpp"
+#include "eos_core.hpp"
 
 namespace ramses_amd {
 
@@ -84,5 +85,17 @@ hipError_t launch_force_diag(const double *f, const double *rho, const int *leaf
 // force_fine's analytic branch (poisson/force_fine.f90:58-103, gravity_type 1 | 2) on an n^3 level brick: f[3][n^3] = gravana at
 // the cell centres ((i + 0.5) dx is exact, so it is the reference's xg + xc)
 hipError_t launch_gravana_brick(const GravAna &G, int n, double dx, double *f, hipStream_t s);
+
+// cooling_fine of a barotropic run without cooling (csrc/eos_core.hpp) on the (nx,ny,nz) interior of a level brick whose first
+// interior cell is at u + off: every cell of the level is a leaf; variable 5 of the interior is rewritten, ghost cells and the
+// other variables are not touched
+struct EosBrickArgs {
+  double *u;
+  int nx, ny, nz;
+  long off, pitch_y, pitch_z, pitch_var;
+  double smallr, gamma;
+  EosConst C;
+};
+hipError_t launch_eos_brick(const EosBrickArgs &A, hipStream_t s);
 
 }  // namespace ramses_amd

@@ -164,3 +164,22 @@ class HydroLevel:
         self.godunov_fine(dt)
         self.set_uold()
         self.make_virtual_fine_dp()
+
+
+def eos_set(T2c, scale_nH, scale_T2):
+    """The barotropic equation of state of constant temperature for every cooling_fine on the device (ramses_amd_eos_set):
+    T2c = T2_eos of barotropic_eos_form='isothermal' or T2_star of the legacy form with g_star = 1 (hydro/eos.f90:14-15,
+    hydro/cooling_fine.f90:344); scale_nH, scale_T2 of the program's units()."""
+    check(lib().ramses_amd_eos_set(float(T2c), float(scale_nH), float(scale_T2)))
+
+
+def eos_energy(params, u5):
+    """cooling_fine's new total energy of leaf cells (hydro/cooling_fine.f90:576-579 without cooling) from u5[5][n] = rho, the
+    three momenta and the old total energy (not read), evaluated on the host by csrc/eos_core.hpp (ramses_amd_eos_eval)."""
+    import numpy as np
+    u5 = np.ascontiguousarray(u5, np.float64)
+    if u5.ndim != 2 or u5.shape[0] != 5:
+        raise _capi.RamsesAmdError("u5 must be (5, n)")
+    out = np.empty(u5.shape[1])
+    check(lib().ramses_amd_eos_eval(C.byref(params), u5.shape[1], u5.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out

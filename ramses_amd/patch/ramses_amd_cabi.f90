@@ -902,6 +902,37 @@ module ramses_amd_cabi
        real(c_double), value :: dteff
        integer(c_int) :: rc
      end function ramses_amd_amrres_synchro
+     ! barotropic EOS with a constant temperature: cooling_fine on the device
+     function ramses_amd_eos_set(T2c, scale_nH, scale_T2) bind(C, name='ramses_amd_eos_set') result(rc)
+       import :: c_int, c_double
+       real(c_double), value :: T2c, scale_nH, scale_T2
+       integer(c_int) :: rc
+     end function ramses_amd_eos_set
+     function ramses_amd_eos_eval(p, n, u5, e) bind(C, name='ramses_amd_eos_eval') result(rc)
+       import :: ramses_amd_hydro_params, c_int, c_int64_t, c_double
+       type(ramses_amd_hydro_params), intent(in) :: p
+       integer(c_int64_t), value :: n
+       real(c_double) :: u5(*), e(*)
+       integer(c_int) :: rc
+     end function ramses_amd_eos_eval
+     function ramses_amd_amrres_cooling_fine(p, ngrid, igrid) bind(C, name='ramses_amd_amrres_cooling_fine') result(rc)
+       import :: ramses_amd_hydro_params, c_int
+       type(ramses_amd_hydro_params), intent(in) :: p
+       integer(c_int), value :: ngrid
+       integer(c_int) :: igrid(*)
+       integer(c_int) :: rc
+     end function ramses_amd_amrres_cooling_fine
+     function ramses_amd_resident_cooling_fine_f90(p, ilevel) bind(C, name='ramses_amd_resident_cooling_fine_f90') result(rc)
+       import :: ramses_amd_hydro_params, c_int
+       type(ramses_amd_hydro_params), intent(in) :: p
+       integer(c_int), value :: ilevel
+       integer(c_int) :: rc
+     end function ramses_amd_resident_cooling_fine_f90
+     function ramses_amd_mpires_cooling_fine(p) bind(C, name='ramses_amd_mpires_cooling_fine') result(rc)
+       import :: ramses_amd_hydro_params, c_int
+       type(ramses_amd_hydro_params), intent(in) :: p
+       integer(c_int) :: rc
+     end function ramses_amd_mpires_cooling_fine
      function ramses_amd_amrres_set_uold_grav(p, ngrid, igrid, dt) bind(C, name='ramses_amd_amrres_set_uold_grav') result(rc)
        import :: ramses_amd_hydro_params, c_int, c_double
        type(ramses_amd_hydro_params), intent(in) :: p

@@ -332,6 +332,7 @@ contains
 #endif
     character(len=16) :: val
     integer :: stat
+    logical :: eos
     if (.not. ramses_amd_res_checked) then
        ramses_amd_res_on = ramses_amd_enabled()
        call get_environment_variable('RAMSES_AMD_RESIDENT', val, status=stat)
@@ -355,9 +356,15 @@ contains
           end if
        end if
        if (tracer .or. MC_tracer .or. clumpfind .or. lightcone .or. movie .or. aton) ramses_amd_res_on = .false.
-       if (static .or. static_gas .or. neq_chem .or. barotropic_eos .or. isothermal .or. metal) ramses_amd_res_on = .false.
+       ! a barotropic EOS of constant temperature: only with RAMSES_AMD_EOS=1 and the self-check (ramses_amd_eos_on, which
+       ! implies none of static, static_gas, neq_chem, metal); its legacy form is the one that sets T2_star
+       eos = .false.
+       if (barotropic_eos .or. isothermal) eos = ramses_amd_eos_on()
+       if (.not. eos) then
+          if (static .or. static_gas .or. neq_chem .or. barotropic_eos .or. isothermal .or. metal) ramses_amd_res_on = .false.
+       end if
        if (difmag > 0.0d0) ramses_amd_res_on = .false.
-       if (pressure_fix .or. T2_star > 0.0d0 .or. momentum_feedback > 0 .or. strict_equilibrium > 0) &
+       if (pressure_fix .or. (T2_star > 0.0d0 .and. .not. eos) .or. momentum_feedback > 0 .or. strict_equilibrium > 0) &
             & ramses_amd_res_on = .false.
        if (ndim /= 3) ramses_amd_res_on = .false.
        ! the dense brick entry points cover a box with nx=ny=nz=1
@@ -392,6 +399,7 @@ contains
 #endif
     character(len=16) :: val
     integer :: stat, ok, okall, info
+    logical :: eos
     if (.not. ramses_amd_mpi_checked) then
        ramses_amd_mpi_checked = .true.
        ramses_amd_mpi_on = ramses_amd_enabled() .and. ncpu > 1
@@ -408,8 +416,13 @@ contains
        if (levelmin /= nlevelmax .or. nboundary > 0 .or. nremap > 0) ramses_amd_mpi_on = .false.
        if (.not. hydro .or. poisson .or. pic .or. rt .or. cooling .or. star .or. sink .or. stellar) ramses_amd_mpi_on = .false.
        if (tracer .or. MC_tracer .or. clumpfind .or. lightcone .or. movie .or. aton) ramses_amd_mpi_on = .false.
-       if (static .or. static_gas .or. neq_chem .or. barotropic_eos .or. isothermal .or. metal) ramses_amd_mpi_on = .false.
-       if (difmag > 0.0d0 .or. pressure_fix .or. T2_star > 0.0d0 .or. momentum_feedback > 0 .or. strict_equilibrium > 0) &
+       ! a barotropic EOS of constant temperature: as in ramses_amd_resident
+       eos = .false.
+       if (barotropic_eos .or. isothermal) eos = ramses_amd_eos_on()
+       if (.not. eos) then
+          if (static .or. static_gas .or. neq_chem .or. barotropic_eos .or. isothermal .or. metal) ramses_amd_mpi_on = .false.
+       end if
+       if (difmag > 0.0d0 .or. pressure_fix .or. (T2_star > 0.0d0 .and. .not. eos) .or. momentum_feedback > 0 .or. strict_equilibrium > 0) &
             & ramses_amd_mpi_on = .false.
        if (ndim /= 3) ramses_amd_mpi_on = .false.
        if (icoarse_max - icoarse_min /= 0 .or. jcoarse_max - jcoarse_min /= 0 .or. kcoarse_max - kcoarse_min /= 0) &
@@ -617,6 +630,7 @@ contains
 #endif
     character(len=16) :: val
     integer :: stat, l
+    logical :: eos
     if (.not. ramses_amd_amr_checked) then
        ramses_amd_amr_checked = .true.
        ramses_amd_amr_ok = ramses_amd_enabled()
@@ -709,8 +723,13 @@ contains
           end if
        end if
        if (tracer .or. MC_tracer .or. clumpfind .or. lightcone .or. movie .or. aton) ramses_amd_amr_ok = .false.
-       if (static .or. static_gas .or. neq_chem .or. barotropic_eos .or. isothermal .or. metal) ramses_amd_amr_ok = .false.
-       if (T2_star > 0.0d0 .or. momentum_feedback > 0 .or. strict_equilibrium > 0) ramses_amd_amr_ok = .false.
+       ! a barotropic EOS of constant temperature: as in ramses_amd_resident
+       eos = .false.
+       if (barotropic_eos .or. isothermal) eos = ramses_amd_eos_on()
+       if (.not. eos) then
+          if (static .or. static_gas .or. neq_chem .or. barotropic_eos .or. isothermal .or. metal) ramses_amd_amr_ok = .false.
+       end if
+       if ((T2_star > 0.0d0 .and. .not. eos) .or. momentum_feedback > 0 .or. strict_equilibrium > 0) ramses_amd_amr_ok = .false.
        if (ndim /= 3 .or. levelmin < 3) ramses_amd_amr_ok = .false.
        if (icoarse_max - icoarse_min /= 0 .or. jcoarse_max - jcoarse_min /= 0 .or. kcoarse_max - kcoarse_min /= 0) &
             & ramses_amd_amr_ok = .false.
@@ -826,6 +845,77 @@ contains
     end if
     ramses_amd_gravana_on = on
   end function ramses_amd_gravana_on
+
+  !---------------------------------------------------------------------------
+  ! The barotropic equation of state on the device (RAMSES_AMD_EOS=1, opt-in): cooling_fine of a run with barotropic_eos and
+  ! without cooling rewrites the total energy of the leaf cells on the resident state (csrc/eos_core.hpp, cooling_fine.f90 of this
+  ! directory), so such a run keeps the resident paths.  True only if the switch is set, the temperature law is a CONSTANT --
+  ! barotropic_eos_form = 'isothermal' (T2c = T2_eos, hydro/eos.f90:14-15), or 'legacy' with g_star = 1 exactly and without
+  ! jeans_ncells (T2c = T2_star: the exponent of hydro/cooling_fine.f90:344 is +0.0) --, nothing else of cooling_fine is active
+  ! (cooling, neq_chem, metal, delayed_cooling, static_gas, NENER > 0) and the SELF-CHECK passes: for the 'isothermal' form
+  ! whatever barotropic_eos_temperature is linked into this program -- the reference's, or a user's patched eos.f90 -- is called
+  ! on nvector densities from smallr to 1e6 smallr, in H/cc as cooling_fine hands them over, and must return T2c bit for bit.
+  ! Otherwise rank 1 says why in one line and the run stays staged, as without the switch.  Every other form ('polytrope',
+  ! 'double_polytrope', 'custom', legacy with g_star /= 1 or jeans_ncells > 0) raises the density to a power: a pow call of the
+  ! runtime library, like gravity_type 3.  Decided once, after read_hydro_params has set T2_eos.
+  !---------------------------------------------------------------------------
+  logical function ramses_amd_eos_on()
+    use amr_commons
+    use hydro_parameters, only: nener, smallr
+    character(len=16) :: val
+    character(len=20) :: form
+    integer :: stat, rc, i, nbad
+    logical, save :: first = .true., on = .false.
+    external :: barotropic_eos_temperature, units
+    real(dp) :: scale_l, scale_t, scale_d, scale_v, scale_nH, scale_T2, T2c, dens, temp
+    if (first) then
+       first = .false.
+       call get_environment_variable('RAMSES_AMD_EOS', val, status=stat)
+       if (stat /= 0) val = '0'
+       if (trim(val) == '1' .and. ramses_amd_enabled() .and. hydro .and. barotropic_eos) then
+          form = barotropic_eos_form
+          if (ndim /= 3 .or. nener /= 0 .or. cooling .or. neq_chem .or. metal .or. delayed_cooling .or. static .or. static_gas &
+               & .or. rt .or. cosmo) then
+             if (myid == 1) write(*,*) 'ramses_amd: RAMSES_AMD_EOS=1 but cooling_fine does more than the equation of state here ', &
+                  & '(cooling, neq_chem, metal, delayed_cooling, static, static_gas, rt, cosmo, NENER > 0 or NDIM /= 3): the run stays staged'
+          else if (trim(form) /= 'isothermal' .and. trim(form) /= 'legacy') then
+             if (myid == 1) write(*,*) 'ramses_amd: RAMSES_AMD_EOS=1 but barotropic_eos_form='''//trim(form)// &
+                  & ''' is not evaluated on the device (''isothermal'', and ''legacy'' with g_star=1, are): the run stays staged'
+          else if (trim(form) == 'legacy' .and. (jeans_ncells > 0 .or. g_star /= 1.0d0)) then
+             if (myid == 1) write(*,*) 'ramses_amd: RAMSES_AMD_EOS=1 but barotropic_eos_form=''legacy'' with g_star=', g_star, &
+                  & ' jeans_ncells=', jeans_ncells, ' is not evaluated on the device (g_star=1 without jeans_ncells is): the run stays staged'
+          else
+             call units(scale_l, scale_t, scale_d, scale_v, scale_nH, scale_T2)
+             nbad = 0
+             if (trim(form) == 'isothermal') then
+                T2c = T2_eos
+                do i = 1, nvector
+                   dens = (smallr * 1.0d6**(dble(i - 1) / dble(max(nvector - 1, 1)))) * scale_nH
+                   temp = -1.0d0
+                   call barotropic_eos_temperature(dens, temp)
+                   if (transfer(temp, 1_8) /= transfer(T2c, 1_8)) nbad = nbad + 1
+                end do
+             else
+                T2c = T2_star
+             end if
+             if (nbad > 0) then
+                if (myid == 1) write(*,*) 'ramses_amd: RAMSES_AMD_EOS=1 but the barotropic_eos_temperature of this program differs from T2_eos in ', &
+                     & nbad, ' of ', nvector, ' sample densities (a patched eos.f90?): the run stays staged'
+             else
+                rc = ramses_amd_eos_set(T2c, scale_nH, scale_T2)
+                if (rc /= 0) then
+                   if (myid == 1) write(*,*) 'ramses_amd: RAMSES_AMD_EOS=1 but T2c=', T2c, ' scale_nH=', scale_nH, ' scale_T2=', scale_T2, &
+                        & ' are not usable: the run stays staged'
+                else
+                   on = .true.
+                   if (myid == 1) write(*,*) 'ramses_amd: barotropic EOS ('//trim(form)//') is evaluated on the GPU'
+                end if
+             end if
+          end if
+       end if
+    end if
+    ramses_amd_eos_on = on
+  end function ramses_amd_eos_on
 
   ! f of the levels whose acceleration lives on the device only, back into the host array (backup_poisson, load_balance;
   ! one level: refine_fine, whose new octs inherit their father cell's f)
